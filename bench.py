@@ -12,6 +12,9 @@ A "step" is one SIRT iteration: A.rec, residual, A^T(W*res), all-reduce of the v
 angle shards (RCCL over xGMI; strong scaling: the 1024 angles are split across the N GPUs), update.
 Inputs are resident in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times exactly --steps steps, writes the outputs if --dump-outputs is given and prints the line.
+--full adds every side measurement below (runs of their own: other poses, volumes, solvers, the CPU baselines).
+
 Extra objects in the line:
   roofline     the projector kernel that takes most of a step: work counted per launch by unit (VALU execution cycles, LDS-array
                cycles, HBM bytes -- rocprofv3 PMC passes of THIS command, committed under profiles/) / mean launch time
@@ -19,7 +22,9 @@ Extra objects in the line:
                (MI355X_MICROARCH.md); `bound` is the unit with the highest utilisation.  The algorithmic-HBM figure of
                SURVEY 8d (volume re-read per angle) is kept as `hbm_algorithmic` -- it exceeds the HBM peak for the LDS-tile
                kernels, which read the volume from HBM once per CALL, and is therefore not the roofline.
+               With --full it also carries `measured_d2d_copy_GBps` (a device copy timed after the steps).
   dense_volume the same SIRT step on a volume without zero regions (the tile kernels skip all-zero tiles; Shepp-Logan has many)
+               (--full, like tilted_poses, cgls, alignment_gradient, align_rigid_e2e and cpu_baseline)
   cpu_baseline the CPU oracle (oracle/: plain-C port of the reference algorithm) timed on this box's host cores on a bounded
                sample of the same workload, extrapolated linearly in the number of rays / angles
 """
@@ -151,6 +156,13 @@ def main():
                                                    "else bench_detail.json next to this file); stdout carries the contract line only")
     ap.add_argument("--fwd-variant", type=int, default=None)
     ap.add_argument("--adj-variant", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement as well (tilted poses, dense volume, CGLS, alignment gradient, align_rigid "
+                         "end to end, device copy rate, CPU baselines); the --no-* options above pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy: reconstruction.npy (float32 rows of the volume along "
+                         "its last axis; all of them in order, or a fixed seeded sample of %d MB when the volume is larger) and rms_error.npy "
+                         "(float64, one value per timed step)" % (RECON_SAMPLE_VALUES * 4 >> 20))
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -258,6 +270,8 @@ def main():
     elapsed = comm.allreduce_max(elapsed)
     if k_done != args.steps:
         raise SystemExit("bench.py: solver stopped after %d of %d steps (semi-convergence rule fired)" % (k_done, args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver.d_rec, N, rms)
 
     # ---- per-kernel timing of the timed region (HIP events on the stream each kernel / collective runs on)
     kern = {}
@@ -377,15 +391,15 @@ def main():
             res["roofline_other_kernel"] = other_r
         return res
 
-    if not args.no_tilted and not args.perturbed and not args.dense:
+    if args.full and not args.no_tilted and not args.perturbed and not args.dense:
         # side measurement (not `value`): alpha, beta ~ U(+-1 deg), tx, tz ~ U(+-2 px), default_rng(0) -- SURVEY 8d's perturbed run:
         # these take the general tile kernels, which is what SIRT runs on once an alignment pass has moved the poses
         out["tilted_poses"] = side_run(True, False, "same workload, alpha, beta ~ U(+-1 deg), tx, tz ~ U(+-2 px): general tile kernels")
-    if not args.no_dense and not args.dense:
+    if args.full and not args.no_dense and not args.dense:
         # side measurement: the same object + 0.05 everywhere, so that no tile is all zero (the headline leans on
         # the zero-tile exits of the tile kernels; Shepp-Logan is exactly zero outside its ellipsoid)
         out["dense_volume"] = side_run(args.perturbed, True, "same workload on a volume with no zero voxel (Shepp-Logan + 0.05): no all-zero tile exits")
-    if not args.no_cgls and not args.perturbed and not args.dense:
+    if args.full and not args.no_cgls and not args.perturbed and not args.dense:
         # side measurement: CGLS iterations per second on the same workload, on every world size.  One GPU, plain:
         # recon/cgls.py:54-82 -- two forward projections (A p, and A rec for its ||b - A rec|| restart test) and one back-projection per
         # iteration.  Sharded (world > 1 or --force-sharded): recon/cgls_mpi.py:70-107 -- its monitor is ||b - A p||, so ONE forward and one
@@ -426,17 +440,17 @@ def main():
         out["value_dense_volume"] = out["dense_volume"]["value"]
     if "tilted_poses" in out:
         out["value_tilted_poses"] = out["tilted_poses"]["value"]
-    if not args.no_align:
+    if args.full and not args.no_align:
         del solver
         out["alignment_gradient"] = align_rate(comm, ctx, rank, world, N=min(512, max(32, N // 2)), n_proj=720 if N >= 1024 else max(8, n_proj // 2))
-    if not args.no_align and not args.no_e2e:
+    if args.full and not args.no_align and not args.no_e2e:
         # config 5 end to end: two outer iterations of examples/align_rigid.py's loop -- on every world size (every rank
         # runs the same legs in the same order, rank 0 prints); world > 1 or --force-sharded take the sharded code path
         out["align_rigid_e2e"] = align_rigid_e2e(comm, ctx, rank, world, sharded=(world > 1 or args.force_sharded),
                                                  N=min(512, max(32, N // 2)), n_proj=720 if N >= 1024 else max(8, n_proj // 2))
-    if roofline is not None:
+    if args.full and roofline is not None:
         roofline["measured_d2d_copy_GBps"] = copy_probe(ctx, be)        # read + write of a 2 GiB hipMemcpy D2D, same run
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         d_ref = be.phantom(be.empty(N ** 3), (N, N, N), SHEPP_LOGAN)
         out["cpu_baseline"] = cpu_baseline(be, d_ref, N, n_proj, phi)
     if rank == 0:
@@ -1045,6 +1059,34 @@ def copy_probe(ctx, be, n_bytes=1 << 31):
         b.copy_from(a)
     ms = ctx.timer_stop()
     return round(4 * 2.0 * n_bytes / (ms * 1e-3) / 1e9, 1)
+
+
+# --dump-outputs: what a caller of the timed path receives (recon/sirt.py::run_main_iteration returns the reconstruction and the rms-error
+# history).  64 MB at most in all: a volume of more than RECON_SAMPLE_VALUES voxels is written as a fixed, seeded sample of its rows.
+RECON_SAMPLE_VALUES = 8 << 20
+
+
+def recon_rows(n_rows, row_len):
+    """Indices of the volume rows (along its last, contiguous axis) --dump-outputs writes: all of them, or a sorted default_rng(0) sample."""
+    k = max(1, RECON_SAMPLE_VALUES // row_len)
+    if k >= n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(path, d_rec, N, rms):
+    """DIR/reconstruction.npy (float32 [rows, N]) and DIR/rms_error.npy (float64, one value per timed step) after the timed steps."""
+    os.makedirs(path, exist_ok=True)
+    n_rows = d_rec.size // N
+    rows = recon_rows(n_rows, N)
+    if rows.size == n_rows:
+        rec = np.asarray(d_rec.download(), np.float32).reshape(n_rows, N)
+    else:
+        rec = np.empty((rows.size, N), np.float32)
+        for i, r in enumerate(rows):
+            rec[i] = d_rec.view(int(r) * N, N).download()
+    np.save(os.path.join(path, "reconstruction.npy"), rec)
+    np.save(os.path.join(path, "rms_error.npy"), np.asarray(rms, np.float64))
 
 
 if __name__ == "__main__":

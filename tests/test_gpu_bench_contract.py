@@ -1,6 +1,7 @@
-"""bench.py prints ONE JSON line with the driver's contract fields plus a compact `roofline` and `cpu_baseline` -- under 4 KB, whatever legs
-ran -- and writes everything it measured to the `--detail` file (checked on a tiny workload so the test takes seconds; the line's size at
-the full-size counters is held by tests/test_host_logic.py::test_bench_contract_line_stays_small_at_the_full_size_counters)."""
+"""bench.py prints ONE JSON line with the driver's contract fields plus a compact `roofline` (and, with --full, `cpu_baseline`) -- under 4 KB,
+whatever legs ran -- and writes everything it measured to the `--detail` file (checked on a tiny workload so the test takes seconds; the line's
+size at the full-size counters is held by tests/test_host_logic.py::test_bench_contract_line_stays_small_at_the_full_size_counters).  A plain
+run times the headline only; --dump-outputs writes what its timed steps computed."""
 import json
 import os
 import subprocess
@@ -29,7 +30,7 @@ def _run(extra, want_line=False):
 
 
 def test_bench_json_contract():
-    line, d = _run([], want_line=True)
+    line, d = _run(["--full"], want_line=True)
     # the stdout line: the driver's keys, typed, and the compact blocks
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
                      ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict), ("roofline", dict), ("cpu_baseline", dict)):
@@ -80,11 +81,11 @@ def test_bench_gpus_2_on_a_one_gpu_box_fails_cleanly():
 
 
 def test_bench_sharded_legs_print_the_same_keys_as_the_plain_run():
-    """`bench.py --gpus 1 --force-sharded` runs every leg a `--gpus 8` run will -- SIRT, dense / tilted side runs, CGLS
+    """`bench.py --full --gpus 1 --force-sharded` runs every leg a `--gpus 8` run will -- SIRT, dense / tilted side runs, CGLS
     (sharded, pipelined), alignment gradient, align_rigid end to end through sirt_mpi.SIRT + align_projections_sharded -- and prints the
     key set of the plain run."""
-    plain = _run(["--no-cpu-baseline"])
-    shard = _run(["--no-cpu-baseline", "--force-sharded"])
+    plain = _run(["--full", "--no-cpu-baseline"])
+    shard = _run(["--full", "--no-cpu-baseline", "--force-sharded"])
     assert set(shard) == set(plain), set(shard) ^ set(plain)
     e = shard["align_rigid_e2e"]
     assert e["sharded_code_path"] is True and e["ranks"] == 1 and len(e["outer"]) == 2 and set(e) == set(plain["align_rigid_e2e"])
@@ -98,3 +99,36 @@ def test_bench_sharded_legs_print_the_same_keys_as_the_plain_run():
 def test_bench_sharded_code_path_on_one_gpu():
     d = _run(["--force-sharded", "--no-cpu-baseline", "--no-align", "--perturbed"])
     assert d["value"] > 0 and d["kernels"]["k_adj_tile"]["launches_per_step"] >= 2      # x-slab pipelined back-projection
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_its_steps_computed(tmp_path):
+    """A plain run (no --full) times the headline only -- no side measurement, no device copy probe, no CPU baseline -- and
+    `--dump-outputs DIR` writes what its timed steps computed: the reconstruction after warm-up + steps and the rms history of the steps,
+    equal to the same SIRT on the same synthetic data run here in-process."""
+    import numpy as np
+    from conftest import rel_max
+    from tomography_alignment_amd import _lib
+    from tomography_alignment_amd.backend import HipBackend
+    from tomography_alignment_amd.recon import sirt
+    from tomography_alignment_amd.utilities.geometry import Geometry
+    from tomography_alignment_amd.utilities.generate_phantom import SHEPP_LOGAN
+    dump = str(tmp_path / "out")
+    line, d = _run(["--dump-outputs", dump], want_line=True)
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-2 and line["roofline"]["avg_launch_ms"] > 0
+    for k in ("tilted_poses", "dense_volume", "cgls", "alignment_gradient", "align_rigid_e2e", "cpu_baseline"):
+        assert k not in d and k not in line, k
+    assert "measured_d2d_copy_GBps" not in d["roofline"]
+    assert sorted(os.listdir(dump)) == ["reconstruction.npy", "rms_error.npy"]
+    rec, rms = np.load(os.path.join(dump, "reconstruction.npy")), np.load(os.path.join(dump, "rms_error.npy"))
+    N, n_proj = 64, 48
+    assert rec.dtype == np.float32 and rec.shape == (N * N, N) and rms.dtype == np.float64 and rms.shape == (2,)
+    assert rms[-1] == d["config"]["rms_error_last"]
+    geo = Geometry(n_proj, np.array([N, N, N]), np.ones(3), np.array([N, N]), np.ones(2))
+    be = HipBackend(geo)
+    phi, z = np.linspace(0., np.pi, n_proj), np.zeros(n_proj)
+    d_true = be.phantom(be.empty(N ** 3), (N, N, N), SHEPP_LOGAN)
+    d_b = be.forward(_lib.poses_array(phi, z, z, np.zeros((n_proj, 3)), np.zeros(3)), d_true, be.empty(n_proj * N * N))
+    s = sirt.SIRT(geo, d_b, np.array([phi, z, z]).T, np.zeros((n_proj, 3)), {"_backend": be})
+    s.iterate_device(niter=1)
+    k, rms_here = s.iterate_device(niter=2)
+    assert k == 2 and rel_max(rec, be.download(s.d_rec).reshape(N * N, N)) < 1e-5 and np.allclose(rms, rms_here, rtol=1e-5)
