@@ -275,6 +275,33 @@ TOMO_API int tomo_vec_soft_threshold(tomo_ctx *ctx, float *d_out, const float *d
 TOMO_API int tomo_tv_denoise_fista(tomo_ctx *ctx, const float *d_im, float *d_out, int nx, int ny, int nz, double weight, int niter, double eps,
                           int check_gap_frequency, int *h_iters, double *h_dual_gap);
 TOMO_API int tomo_tv_norm_3d(tomo_ctx *ctx, const float *d_x, int nx, int ny, int nz, double *h_norm);
+/* ---------------------------------------------------------------- RegularizedRecon's fused per-iteration passes (csrc/tomo_reg.hip)
+ * One streaming pass each over float32 volumes of n elements; the scalars of the pass are summed in float64 and ADDED to the
+ * accumulators d_acc[slot], d_acc[slot + 1] (tomo_acc_zero / tomo_acc_fetch above) -- deterministically: a grid that depends on n only,
+ * block partials in a fixed order, then one single-block pass.  Same bits in -> same bits out, on every call and every rank.
+ * Elementwise arithmetic in float32 in the reference's operation order (no contraction).  n = 0 is a no-op; operands of any 4-byte
+ * alignment (16-byte loads where all operands share their offset from a 16-byte boundary).
+ *   tomo_vec_fista_momentum   rec = u + c (u - u_old); slot += ||gt - rec||^2 (gt nullable)     recon/regularized.py:102,113
+ *   tomo_vec_tikh_grad        bp <- -bp + lambda rec (in place); slot += ||grad||^2, slot+1 += ||rec||^2      :180,188
+ *   tomo_vec_trial            out = x + a d; slot += ||out||^2   (Armijo's trial point and my_tikh_f's |x|^2)  :189,416-422
+ *   tomo_vec_clamp_err        rec[rec < 0] = 0 when positivity; slot += ||gt - rec||^2 (gt nullable)         :200-207
+ *   tomo_vec_prox_l1_trial    xp = soft(x - t g, t_lambda); Gt = x - xp; slot += g.Gt, slot+1 += ||Gt||^2    :317-326
+ *   tomo_vec_prox_l1_momentum out = soft(v - a g, a_lambda), v = x1 + c (x1 - x0) never stored; slot += ||gt - out||^2 (gt
+ *                             nullable); out may alias x0                                                     :374-375,383
+ *   tomo_vec_residual_acc     out = ax - b (negate: b - ax), out nullable and may alias ax; slot += ||out||^2  :85-86,177,267,324
+ * tomo_tv_prox_det: the computation of tomo_tv_denoise_fista (same arguments, same dual-field kernels) whose dual-gap and TV sums
+ *   are deterministic, so the gap stop (utilities/tv_denoise.py:165-166) is a function of the input bits -- the TV proximal step of
+ *   recon/regularized.py:93, which every rank of a sharded run computes redundantly on the same all-reduced gradient. */
+TOMO_API int tomo_vec_fista_momentum(tomo_ctx *ctx, float *d_rec, const float *d_u, const float *d_u_old, const float *d_gt, int64_t n, float c, int slot);
+TOMO_API int tomo_vec_tikh_grad(tomo_ctx *ctx, float *d_bp, const float *d_rec, int64_t n, float lambda, int slot);
+TOMO_API int tomo_vec_trial(tomo_ctx *ctx, float *d_out, const float *d_x, const float *d_d, int64_t n, float a, int slot);
+TOMO_API int tomo_vec_clamp_err(tomo_ctx *ctx, float *d_rec, const float *d_gt, int64_t n, int positivity, int slot);
+TOMO_API int tomo_vec_prox_l1_trial(tomo_ctx *ctx, float *d_xp, const float *d_x, const float *d_g, int64_t n, float t, float t_lambda, int slot);
+TOMO_API int tomo_vec_prox_l1_momentum(tomo_ctx *ctx, float *d_out, const float *d_x0, const float *d_x1, const float *d_g, const float *d_gt, int64_t n,
+                              float c, float a, float a_lambda, int slot);
+TOMO_API int tomo_vec_residual_acc(tomo_ctx *ctx, float *d_out, const float *d_ax, const float *d_b, int64_t n, int negate, int slot);
+TOMO_API int tomo_tv_prox_det(tomo_ctx *ctx, const float *d_im, float *d_out, int nx, int ny, int nz, double weight, int niter, double eps,
+                     int check_gap_frequency, int *h_iters, double *h_dual_gap);
 /* tomo_tv_denoise_fista keeps its workspace (7 volumes: the dual fields and two images) in the context between calls, grow-only;
  * tomo_release_workspace frees it (synchronises the stream first).  The next call that needs it allocates it again. */
 TOMO_API int tomo_release_workspace(tomo_ctx *ctx);

@@ -89,6 +89,16 @@ SIGNATURES = {
     "tomo_tv_denoise_fista": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int), _c_dp]),
     "tomo_tv_norm_3d": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp]),
+    "tomo_vec_fista_momentum": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_int]),
+    "tomo_vec_tikh_grad": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_int]),
+    "tomo_vec_trial": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_int]),
+    "tomo_vec_clamp_err": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.c_int]),
+    "tomo_vec_prox_l1_trial": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_int]),
+    "tomo_vec_prox_l1_momentum": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                 ctypes.c_int]),
+    "tomo_vec_residual_acc": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.c_int]),
+    "tomo_tv_prox_det": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int), _c_dp]),
     "tomo_release_workspace": (ctypes.c_int, [_c_vp]),
     "tomo_csr_assemble": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "tomo_csr_fetch": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp]),

@@ -292,5 +292,47 @@ class HipBackend(object):
         self.ctx.check(self.lib.tomo_tv_norm_3d(self.ctx.handle, x.ptr, nx, ny, nz, ctypes.byref(v)))
         return v.value
 
+    # ---- RegularizedRecon's fused passes (recon/regularized.py): each ADDS its scalars to accumulator slots (deterministic sums)
+    @staticmethod
+    def _p(buf):
+        return buf.ptr if buf is not None else None
+
+    def fista_momentum(self, rec, u, u_old, c, gt=None, slot=0):
+        """rec = u + c (u - u_old); slot += ||gt - rec||^2."""
+        self.ctx.check(self.lib.tomo_vec_fista_momentum(self.ctx.handle, rec.ptr, u.ptr, u_old.ptr, self._p(gt), rec.size, float(c), int(slot)))
+
+    def tikh_grad(self, bp, rec, lam, slot=0):
+        """bp <- -bp + lam rec in place; slot += ||grad||^2, slot + 1 += ||rec||^2."""
+        self.ctx.check(self.lib.tomo_vec_tikh_grad(self.ctx.handle, bp.ptr, rec.ptr, bp.size, float(lam), int(slot)))
+
+    def trial(self, out, x, d, a, slot=0):
+        """out = x + a d; slot += ||out||^2."""
+        self.ctx.check(self.lib.tomo_vec_trial(self.ctx.handle, out.ptr, x.ptr, d.ptr, out.size, float(a), int(slot)))
+
+    def clamp_err(self, rec, positivity=False, gt=None, slot=0):
+        """rec[rec < 0] = 0 when positivity; slot += ||gt - rec||^2."""
+        self.ctx.check(self.lib.tomo_vec_clamp_err(self.ctx.handle, rec.ptr, self._p(gt), rec.size, 1 if positivity else 0, int(slot)))
+
+    def prox_l1_trial(self, xp, x, g, t, t_lambda, slot=0):
+        """xp = soft(x - t g, t_lambda); Gt = x - xp; slot += g.Gt, slot + 1 += ||Gt||^2."""
+        self.ctx.check(self.lib.tomo_vec_prox_l1_trial(self.ctx.handle, xp.ptr, x.ptr, g.ptr, xp.size, float(t), float(t_lambda), int(slot)))
+
+    def prox_l1_momentum(self, out, x0, x1, g, c, a, a_lambda, gt=None, slot=0):
+        """out = soft(x1 + c (x1 - x0) - a g, a_lambda) (out may be x0); slot += ||gt - out||^2."""
+        self.ctx.check(self.lib.tomo_vec_prox_l1_momentum(self.ctx.handle, out.ptr, x0.ptr, x1.ptr, g.ptr, self._p(gt), out.size, float(c), float(a),
+                                                          float(a_lambda), int(slot)))
+
+    def residual_acc(self, out, ax, b, negate=False, slot=0):
+        """out = ax - b (negate: b - ax; out None: not stored); slot += ||out||^2."""
+        self.ctx.check(self.lib.tomo_vec_residual_acc(self.ctx.handle, self._p(out), ax.ptr, b.ptr, ax.size, 1 if negate else 0, int(slot)))
+
+    def tv_prox_det(self, im, out, shape, weight=50, niter=200, eps=1.e-5, check_gap_frequency=3):
+        """tv_denoise_fista with deterministic gap sums -> (iterations done, last dual gap)."""
+        nx, ny, nz = (int(v) for v in shape)
+        it, gap = ctypes.c_int(0), ctypes.c_double(0)
+        self.ctx.check(self.lib.tomo_tv_prox_det(self.ctx.handle, im.ptr, out.ptr, nx, ny, nz, float(weight), int(niter), float(eps),
+                                                 int(check_gap_frequency), ctypes.byref(it), ctypes.byref(gap)))
+        return it.value, gap.value
+
     def sync(self):
         self.ctx.sync()
