@@ -1,0 +1,885 @@
+// libtomo_xcorr.so: FFT cross-correlation pre-alignment (tomography_alignment_amd/align/align_cc.py) on gfx950.
+// 2-D FFTs are hipFFT Z2Z plans on the handle's stream; everything else is the kernels below.  A chain is one upload, n-1 steps
+// enqueued on one stream whose peaks and shifts stay in device memory, and one download.  All reductions are deterministic: a fixed
+// grid writes block partials, one block reduces them in a fixed order; no atomics.
+#include <hip/hip_runtime.h>
+#include <hipfft/hipfft.h>
+
+#include <atomic>
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <map>
+#include <string>
+#include <tuple>
+
+#include "../../../include/tomo_xcorr.h"
+
+namespace {
+
+constexpr int TPB = 256;        // threads per block of every kernel
+constexpr int G = 256;          // blocks of every first-stage reduction (== TPB: the second stage is one block, one partial per thread)
+constexpr double PI = 3.141592653589793238462643383279502884;
+
+std::atomic<int64_t> g_device_bytes{0};
+thread_local std::string g_err;
+
+// ---------------------------------------------------------------------------------------------------------------------- kernels
+
+template <class T>
+__device__ inline double ld(const T *p, long i) { return (double)p[i]; }
+
+// Block tree reduction of a sum in LDS, fixed order; every thread gets the total.
+__device__ inline double block_sum(double v, double *sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = TPB / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// Partial sums of B planes of N values (dtype T): part[b * G + blk].
+template <class T>
+__global__ __launch_bounds__(TPB) void k_sum_partial(const T *x, long N, double *part) {
+    __shared__ double sh[TPB];
+    const long b = blockIdx.y;
+    const long chunk = (N + G - 1) / G;
+    const long lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+    double s = 0.0;
+    for (long i = lo + threadIdx.x; i < hi; i += TPB) s += ld(x + b * N, i);
+    double t = block_sum(s, sh);
+    if (threadIdx.x == 0) part[b * G + blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(TPB) void k_sumsq_partial(const double2 *x, long N, double *part) {
+    __shared__ double sh[TPB];
+    const long b = blockIdx.y;
+    const long chunk = (N + G - 1) / G;
+    const long lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+    double s = 0.0;
+    for (long i = lo + threadIdx.x; i < hi; i += TPB) {
+        double2 z = x[b * N + i];
+        s += z.x * z.x + z.y * z.y;
+    }
+    double t = block_sum(s, sh);
+    if (threadIdx.x == 0) part[b * G + blockIdx.x] = t;
+}
+
+// out[b] = complex((x[b] - mean_b) * W, 0), mean_b reduced from part[b * G ..] (null part: no mean, null W: no window).
+template <class T>
+__global__ __launch_bounds__(TPB) void k_load_window(const T *x, long N, const double *part, const double *W, double2 *out) {
+    __shared__ double sh[TPB];
+    const long b = blockIdx.y;
+    double mean = 0.0;
+    if (part) {
+        double t = block_sum(part[b * G + threadIdx.x], sh);
+        mean = t / (double)N;
+    }
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    double v = ld(x + b * N, i) - mean;
+    if (W) v *= W[i];
+    out[b * N + i] = make_double2(v, 0.0);
+}
+
+// Cross-power spectrum of B pairs.  mode 0 (numpy path): conj(Fm) * Fr * K.  mode 1: Fr * conj(Fm) / max(|.|, 100 eps) ("phase").
+// mode 2: Fr * conj(Fm) (normalization None).  Fr may be shared by every pair (fr_stride 0).
+__global__ __launch_bounds__(TPB) void k_cross_power(const double2 *Fr, long fr_stride, const double2 *Fm, const double *K, int mode,
+                                                     long N, double2 *P) {
+    const long b = blockIdx.y;
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    const double2 r = Fr[b * fr_stride + i], m = Fm[b * N + i];
+    double2 p;
+    if (mode == 0) {
+        double2 c = make_double2(m.x * r.x + m.y * r.y, m.x * r.y - m.y * r.x);     // conj(m) * r
+        p = make_double2(c.x * K[i], c.y * K[i]);
+    } else {
+        p = make_double2(r.x * m.x + r.y * m.y, r.y * m.x - r.x * m.y);             // r * conj(m)
+        if (mode == 1) {
+            const double d = fmax(hypot(p.x, p.y), 100.0 * 2.220446049250313e-16);
+            p = make_double2(p.x / d, p.y / d);
+        }
+    }
+    P[b * N + i] = p;
+}
+
+// First stage of |z| argmax over B planes of N values: per block the largest |z| and its first index (numpy's tie-break).
+__device__ inline bool better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+__device__ inline void block_argmax(double &v, int &i, double *sv, int *si) {
+    sv[threadIdx.x] = v;
+    si[threadIdx.x] = i;
+    __syncthreads();
+    for (int s = TPB / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s && better(sv[threadIdx.x + s], si[threadIdx.x + s], sv[threadIdx.x], si[threadIdx.x])) {
+            sv[threadIdx.x] = sv[threadIdx.x + s];
+            si[threadIdx.x] = si[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    v = sv[0];
+    i = si[0];
+}
+
+__global__ __launch_bounds__(TPB) void k_absmax_partial(const double2 *x, long N, double *pv, int *pi) {
+    __shared__ double sv[TPB];
+    __shared__ int si[TPB];
+    const long b = blockIdx.y;
+    const long chunk = (N + G - 1) / G;
+    const long lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+    double bv = -1.0;
+    int bi = INT_MAX;
+    for (long i = lo + threadIdx.x; i < hi; i += TPB) {
+        double2 z = x[b * N + i];
+        double v = hypot(z.x, z.y);
+        if (v > bv) { bv = v; bi = (int)i; }             // i increases: the first of equal values stays
+    }
+    block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) { pv[b * G + blockIdx.x] = bv; pi[b * G + blockIdx.x] = bi; }
+}
+
+enum { PEAK_NUMPY = 0, PEAK_COARSE = 1, PEAK_FINE = 2 };
+
+struct PeakArgs {
+    int mode, nx, nz, upsample, region;
+    double dftshift;
+    const double2 *x;       // the plane(s) reduced: B x len
+    long len;
+    double *out;            // B x 2: numpy: raw peak; coarse: (rounded) coarse shift; fine: += refinement
+    long out_stride;        // doubles between consecutive pairs' out
+    int *peak;              // numpy: B x 2 integer peak (roll)
+    double2 *ccmax;         // coarse (upsample 1) / fine: the peak's value (coarse scaled by 1/len, as ifft does)
+};
+
+// Second stage: one block per pair reduces the G partials, then thread 0 turns the peak index into the step's shift.
+__global__ __launch_bounds__(TPB) void k_absmax_final(const double *pv, const int *pi, PeakArgs a) {
+    __shared__ double sv[TPB];
+    __shared__ int si[TPB];
+    const long b = blockIdx.x;
+    double v = pv[b * G + threadIdx.x];
+    int i = pi[b * G + threadIdx.x];
+    block_argmax(v, i, sv, si);
+    if (threadIdx.x != 0) return;
+    if (i < 0 || i >= a.len) i = 0;          // no finite maximum (NaN input): keep every index in bounds
+    double *o = a.out + b * a.out_stride;
+    if (a.mode == PEAK_NUMPY) {
+        const int px = i / a.nz, pz = i % a.nz;
+        o[0] = px;
+        o[1] = pz;
+        a.peak[2 * b] = px;
+        a.peak[2 * b + 1] = pz;
+    } else if (a.mode == PEAK_COARSE) {
+        double s0 = i / a.nz, s1 = i % a.nz;
+        if (s0 > trunc(a.nx / 2.0)) s0 -= a.nx;
+        if (s1 > trunc(a.nz / 2.0)) s1 -= a.nz;
+        if (a.upsample > 1) {
+            const double u = a.upsample;
+            s0 = rint(s0 * u) / u;          // np.round: half to even
+            s1 = rint(s1 * u) / u;
+        } else {
+            if (a.nx == 1) s0 = 0.0;
+            if (a.nz == 1) s1 = 0.0;
+            if (a.ccmax) {
+                double2 c = a.x[b * a.len + i];
+                a.ccmax[b] = make_double2(c.x / (double)a.len, c.y / (double)a.len);
+            }
+        }
+        o[0] = s0;
+        o[1] = s1;
+    } else {
+        const double u = a.upsample;
+        const double m0 = i / a.region, m1 = i % a.region;
+        double s0 = o[0] + (m0 - a.dftshift) / u, s1 = o[1] + (m1 - a.dftshift) / u;
+        if (a.nx == 1) s0 = 0.0;
+        if (a.nz == 1) s1 = 0.0;
+        o[0] = s0;
+        o[1] = s1;
+        if (a.ccmax) a.ccmax[b] = a.x[b * a.len + i];
+    }
+}
+
+// The upsampled DFT's two kernels around each pair's coarse shift, conjugated (skimage conjugates the product, transforms with
+// exp(-2 pi i ...) and conjugates back; conj(sum(k * conj(p))) == sum(conj(k) * p) exactly):
+//   E0[b][a][j] = exp(+2 pi i (a - off0) f0_j),  off0 = dftshift - shift0 * u,  f0 = fftfreq(nx, u); likewise E1 over nz.
+__global__ __launch_bounds__(TPB) void k_updft_kernels(const double *shift, long shift_stride, int nx, int nz, int upsample,
+                                                       int region, double dftshift, double2 *E0, double2 *E1) {
+    const long b = blockIdx.y;
+    const long t = (long)blockIdx.x * TPB + threadIdx.x;
+    const long n0 = (long)region * nx, n1 = (long)region * nz;
+    if (t >= n0 + n1) return;
+    const int axis = t < n0 ? 0 : 1;
+    const long tt = axis == 0 ? t : t - n0;
+    const int n = axis == 0 ? nx : nz;
+    const int a = (int)(tt / n), j = (int)(tt % n);
+    const double u = upsample;
+    const double off = dftshift - shift[b * shift_stride + axis] * u;
+    const int k = j < (n - 1) / 2 + 1 ? j : j - n;                   // numpy.fft.fftfreq's integer grid
+    const double f = k * (1.0 / (n * u));
+    const double kern = ((double)a - off) * f;
+    double s, c;
+    sincos(-2.0 * PI * kern, &s, &c);
+    const double2 e = make_double2(c, -s);
+    if (axis == 0) E0[b * n0 + tt] = e; else E1[b * n1 + tt] = e;
+}
+
+// Batched strided complex GEMM: C(z, m, n) = sum_k A(z, m, k) * B(z, n, k); 16 x 16 output tile per block, K in steps of 16 through LDS.
+struct Gemm {
+    const double2 *A; long sAz, sAm, sAk;
+    const double2 *B; long sBz, sBn, sBk;
+    double2 *C; long sCz, sCm, sCn;
+    int M, N, K;
+};
+
+__global__ __launch_bounds__(TPB) void k_zgemm(Gemm g) {
+    __shared__ double2 As[16][17];
+    __shared__ double2 Bs[16][17];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const long z = blockIdx.z;
+    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+    const double2 *A = g.A + z * g.sAz, *B = g.B + z * g.sBz;
+    double re = 0.0, im = 0.0;
+    for (int k0 = 0; k0 < g.K; k0 += 16) {
+        const int k = k0 + tx;
+        As[ty][tx] = (m0 + ty < g.M && k < g.K) ? A[(long)(m0 + ty) * g.sAm + (long)k * g.sAk] : make_double2(0.0, 0.0);
+        Bs[ty][tx] = (n0 + ty < g.N && k < g.K) ? B[(long)(n0 + ty) * g.sBn + (long)k * g.sBk] : make_double2(0.0, 0.0);
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const double2 a = As[ty][kk], bb = Bs[tx][kk];
+            re += a.x * bb.x - a.y * bb.y;
+            im += a.x * bb.y + a.y * bb.x;
+        }
+        __syncthreads();
+    }
+    if (m0 + ty < g.M && n0 + tx < g.N) g.C[z * g.sCz + (long)(m0 + ty) * g.sCm + (long)(n0 + tx) * g.sCn] = make_double2(re, im);
+}
+
+// Integer roll of pair b's plane by its device peak: out[(x + px) % nx][(z + pz) % nz] = in[x][z], in gather form.
+template <class T>
+__global__ __launch_bounds__(TPB) void k_roll(const T *in, const int *peak, int nx, int nz, T *out) {
+    const long N = (long)nx * nz;
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    const int x = (int)(i / nz), zz = (int)(i % nz);
+    const int sx = ((x - peak[0]) % nx + nx) % nx, sz = ((zz - peak[1]) % nz + nz) % nz;
+    out[i] = in[(long)sx * nz + sz];
+}
+
+// scipy.ndimage's cubic B-spline prefilter of one line (ni_splines.c, mirror boundary -- what mode 'constant' uses): gain, then the
+// causal and anticausal recursions of the pole sqrt(3) - 2 with mirror initialisation.  One thread per line, `stride` apart.
+__device__ void spline_line(double *c, int n, long stride) {
+    if (n < 2) return;
+    const double zp = sqrt(3.0) - 2.0;
+    const double lambda = (1.0 - zp) * (1.0 - 1.0 / zp);
+    for (int i = 0; i < n; ++i) c[i * stride] *= lambda;
+    const double zn1 = pow(zp, (double)(n - 1));
+    double c0 = c[0] + zn1 * c[(long)(n - 1) * stride];
+    double zi = zp;
+    for (int i = 1; i < n - 1; ++i) {
+        c0 += zi * (c[i * stride] + zn1 * c[(long)(n - 1 - i) * stride]);
+        zi *= zp;
+    }
+    c0 /= 1.0 - zn1 * zn1;
+    c[0] = c0;
+    double prev = c0;
+    for (int i = 1; i < n; ++i) {
+        prev = c[i * stride] + zp * prev;
+        c[i * stride] = prev;
+    }
+    double last = (zp * c[(long)(n - 2) * stride] + prev) * zp / (zp * zp - 1.0);
+    c[(long)(n - 1) * stride] = last;
+    for (int i = n - 2; i >= 0; --i) {
+        last = zp * (last - c[i * stride]);
+        c[i * stride] = last;
+    }
+}
+
+// Axis 0 (scipy filters axis 0 first): one thread per column; the plane is converted to float64 on the way in.
+template <class T>
+__global__ __launch_bounds__(TPB) void k_spline_axis0(const T *in, int nx, int nz, double *c) {
+    const long b = blockIdx.y;
+    const int col = blockIdx.x * TPB + threadIdx.x;
+    if (col >= nz) return;
+    const long N = (long)nx * nz;
+    const T *p = in + b * N + col;
+    double *q = c + b * N + col;
+    for (int x = 0; x < nx; ++x) q[(long)x * nz] = (double)p[(long)x * nz];
+    spline_line(q, nx, nz);
+}
+
+__global__ __launch_bounds__(TPB) void k_spline_axis1(int nx, int nz, double *c) {
+    const long b = blockIdx.y;
+    const int row = blockIdx.x * TPB + threadIdx.x;
+    if (row >= nx) return;
+    spline_line(c + b * (long)nx * nz + (long)row * nz, nz, 1);
+}
+
+__device__ inline int mirror_index(int i, int n) {
+    if (n <= 1) return 0;
+    const int s2 = 2 * n - 2;
+    if (i < 0) {
+        i = s2 * (-i / s2) + i;
+        i = i <= 1 - n ? i + s2 : -i;
+    } else if (i >= n) {
+        i -= s2 * (i / s2);
+        if (i >= n) i = s2 - i;
+    }
+    return i;
+}
+
+__device__ inline void cubic_weights(double x, double w[4]) {
+    const double y = x - floor(x), z = 1.0 - y;
+    w[0] = z * z * z / 6.0;
+    w[1] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0;
+    w[2] = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0;
+    w[3] = 1.0 - w[0] - w[1] - w[2];
+}
+
+// ndimage.shift(order=3, mode='constant', cval=0) from prefiltered coefficients: an output point whose source coordinate lies outside
+// [0, n-1] on either axis is 0; inside, the 4 x 4 cubic B-spline sum over mirror-extended coefficients, rounded to T.
+template <class T>
+__global__ __launch_bounds__(TPB) void k_shift_interp(const double *c, const double *shift, long shift_stride, int nx, int nz, T *out) {
+    const long b = blockIdx.y;
+    const long N = (long)nx * nz;
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    const int x = (int)(i / nz), zz = (int)(i % nz);
+    const double cx = x - shift[b * shift_stride], cz = zz - shift[b * shift_stride + 1];
+    double t = 0.0;
+    if (cx >= 0.0 && cx <= nx - 1 && cz >= 0.0 && cz <= nz - 1) {
+        double wx[4], wz[4];
+        cubic_weights(cx, wx);
+        cubic_weights(cz, wz);
+        const int sx = (int)floor(cx) - 1, sz = (int)floor(cz) - 1;
+        int iz[4];
+        for (int q = 0; q < 4; ++q) iz[q] = mirror_index(sz + q, nz);
+        const double *cb = c + b * N;
+        for (int p = 0; p < 4; ++p) {
+            const double *row = cb + (long)mirror_index(sx + p, nx) * nz;
+            for (int q = 0; q < 4; ++q) t += row[iz[q]] * wx[p] * wz[q];
+        }
+    }
+    out[b * N + i] = (T)t;
+}
+
+// error = sqrt(|1 - |CCmax|^2 / (src_amp * target_amp)|), phasediff = atan2(Im, Re); amps reduced from the |F|^2 partials
+// (divided by N for upsample 1, as skimage does).
+__global__ __launch_bounds__(TPB) void k_pcc_scalars(const double *part_src, const double *part_tgt, const double2 *ccmax, long N,
+                                                     int upsample, double *err, double *phase) {
+    __shared__ double sh[TPB];
+    const long b = blockIdx.x;
+    double sa = block_sum(part_src[b * G + threadIdx.x], sh);
+    __syncthreads();
+    double ta = block_sum(part_tgt[b * G + threadIdx.x], sh);
+    if (threadIdx.x != 0) return;
+    if (upsample == 1) { sa /= (double)N; ta /= (double)N; }
+    const double2 c = ccmax[b];
+    err[b] = sqrt(fabs(1.0 - (c.x * c.x + c.y * c.y) / (sa * ta)));
+    phase[b] = atan2(c.y, c.x);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- host side
+
+struct Buf {
+    void *p = nullptr;
+    size_t n = 0;
+};
+
+}  // namespace
+
+struct tomo_xcorr {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::string err;
+    std::map<std::tuple<int, int, int>, hipfftHandle> plans;
+    std::map<std::string, Buf> bufs;
+    double t_plan = 0.0;
+    double timing[4] = {0, 0, 0, 0};
+};
+
+namespace {
+
+int fail(tomo_xcorr *h, int code, const std::string &msg) {
+    if (h) h->err = msg; else g_err = msg;
+    return code;
+}
+
+#define HIPCHK(h, call)                                                                                                 \
+    do {                                                                                                                \
+        hipError_t e_ = (call);                                                                                         \
+        if (e_ != hipSuccess) return fail(h, TOMO_XCORR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+#define FFTCHK(h, call)                                                                                                 \
+    do {                                                                                                                \
+        hipfftResult r_ = (call);                                                                                       \
+        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_XCORR_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
+    } while (0)
+#define CHK(expr)                    \
+    do {                             \
+        int rc_ = (expr);            \
+        if (rc_ != TOMO_XCORR_OK) return rc_; \
+    } while (0)
+
+// A named work buffer of at least `bytes`, grown (never shrunk) on demand and counted in g_device_bytes.
+int buf(tomo_xcorr *h, const char *name, size_t bytes, void **out) {
+    Buf &b = h->bufs[name];
+    if (b.n < bytes) {
+        if (b.p) {
+            HIPCHK(h, hipFree(b.p));
+            g_device_bytes -= (int64_t)b.n;
+            b.p = nullptr;
+            b.n = 0;
+        }
+        HIPCHK(h, hipMalloc(&b.p, bytes));
+        b.n = bytes;
+        g_device_bytes += (int64_t)bytes;
+    }
+    *out = b.p;
+    return TOMO_XCORR_OK;
+}
+
+template <class P>
+int bufp(tomo_xcorr *h, const char *name, size_t count, P **out) {
+    void *p = nullptr;
+    CHK(buf(h, name, count * sizeof(P) > 0 ? count * sizeof(P) : 16, &p));
+    *out = (P *)p;
+    return TOMO_XCORR_OK;
+}
+
+int plan(tomo_xcorr *h, int nx, int nz, int batch, hipfftHandle *out) {
+    auto key = std::make_tuple(nx, nz, batch);
+    auto it = h->plans.find(key);
+    if (it != h->plans.end()) { *out = it->second; return TOMO_XCORR_OK; }
+    auto t0 = std::chrono::steady_clock::now();
+    hipfftHandle p;
+    FFTCHK(h, hipfftCreate(&p));
+    // a plane with an axis of length 1 is a 1-D transform along the other axis
+    int n[2] = {nx, nz};
+    int n1[1] = {nx * nz};
+    const int dist = nx * nz;
+    const bool flat = nx == 1 || nz == 1;
+    hipfftResult r = hipfftPlanMany(&p, flat ? 1 : 2, flat ? n1 : n, nullptr, 1, dist, nullptr, 1, dist, HIPFFT_Z2Z, batch);
+    if (r == HIPFFT_SUCCESS) r = hipfftSetStream(p, h->stream);
+    if (r != HIPFFT_SUCCESS) {
+        hipfftDestroy(p);
+        return fail(h, TOMO_XCORR_ERR_FFT, "hipfftPlanMany(Z2Z " + std::to_string(nx) + "x" + std::to_string(nz) + ", batch " +
+                                               std::to_string(batch) + "): hipfft error " + std::to_string((int)r));
+    }
+    h->plans[key] = p;
+    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out = p;
+    return TOMO_XCORR_OK;
+}
+
+inline dim3 grid1(long n, int b = 1) { return dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)b); }
+
+int check_launch(tomo_xcorr *h) {
+    HIPCHK(h, hipGetLastError());
+    return TOMO_XCORR_OK;
+}
+
+int check_shape(tomo_xcorr *h, int n, int nx, int nz, int dtype) {
+    if (!h) return fail(nullptr, TOMO_XCORR_ERR_ARG, "NULL handle");
+    if (n < 0 || nx < 1 || nz < 1) return fail(h, TOMO_XCORR_ERR_ARG, "bad shape");
+    if ((long)nx * nz > (long)INT_MAX / 4) return fail(h, TOMO_XCORR_ERR_ARG, "plane too large");
+    if (dtype != 0 && dtype != 1) return fail(h, TOMO_XCORR_ERR_ARG, "dtype must be 0 (float32) or 1 (float64)");
+    return TOMO_XCORR_OK;
+}
+
+// Moving-image spectra are computed ahead in batches of this many planes (bounded memory: 256 MiB of spectra).
+int chunk_planes(long N, int n) {
+    long c = (256L << 20) / (N * (long)sizeof(double2));
+    if (c < 1) c = 1;
+    if (c > 4096) c = 4096;
+    if (c > n) c = n;
+    return (int)c;
+}
+
+template <class T>
+void launch_sum_partial(const T *x, long N, int B, double *part, hipStream_t s) {
+    k_sum_partial<T><<<dim3(G, B), TPB, 0, s>>>(x, N, part);
+}
+
+// (x - mean) * W of B planes (dtype), or a plain float64 -> complex load (no mean, no window), into out (B x N complex).
+int load_planes(tomo_xcorr *h, const void *x, int dtype, long N, int B, bool mean, const double *W, double2 *out) {
+    double *part = nullptr;
+    if (mean) CHK(bufp(h, "mean_part", (size_t)G * B, &part));
+    if (dtype == 0) {
+        if (mean) launch_sum_partial((const float *)x, N, B, part, h->stream);
+        k_load_window<float><<<grid1(N, B), TPB, 0, h->stream>>>((const float *)x, N, part, W, out);
+    } else {
+        if (mean) launch_sum_partial((const double *)x, N, B, part, h->stream);
+        k_load_window<double><<<grid1(N, B), TPB, 0, h->stream>>>((const double *)x, N, part, W, out);
+    }
+    return check_launch(h);
+}
+
+int argmax(tomo_xcorr *h, const double2 *x, long len, int B, const PeakArgs &a) {
+    double *pv = nullptr;
+    int *pi = nullptr;
+    CHK(bufp(h, "amax_v", (size_t)G * B, &pv));
+    CHK(bufp(h, "amax_i", (size_t)G * B, &pi));
+    k_absmax_partial<<<dim3(G, B), TPB, 0, h->stream>>>(x, len, pv, pi);
+    k_absmax_final<<<B, TPB, 0, h->stream>>>(pv, pi, a);
+    return check_launch(h);
+}
+
+// skimage's phase cross-correlation of B pairs from their spectra, all on the stream: the cross-power spectrum, its inverse FFT,
+// the coarse peak and, for upsample > 1, the upsampled DFT around it and the refined peak.  shifts: device, pair b at
+// shifts[b * shift_stride]; ccmax (optional): device, B values.
+int pcc_spectra(tomo_xcorr *h, const double2 *Fr, long fr_stride, const double2 *Fm, int B, int nx, int nz, int upsample, int mode,
+                double *shifts, long shift_stride, double2 *ccmax) {
+    const long N = (long)nx * nz;
+    double2 *P = nullptr, *X = nullptr;
+    CHK(bufp(h, "P", (size_t)N * B, &P));
+    CHK(bufp(h, "X", (size_t)N * B, &X));
+    hipfftHandle pl;
+    CHK(plan(h, nx, nz, B, &pl));
+    k_cross_power<<<grid1(N, B), TPB, 0, h->stream>>>(Fr, fr_stride, Fm, nullptr, mode, N, P);
+    CHK(check_launch(h));
+    FFTCHK(h, hipfftExecZ2Z(pl, (hipfftDoubleComplex *)P, (hipfftDoubleComplex *)X, HIPFFT_BACKWARD));
+    PeakArgs a{};
+    a.mode = PEAK_COARSE;
+    a.nx = nx;
+    a.nz = nz;
+    a.upsample = upsample;
+    a.x = X;
+    a.len = N;
+    a.out = shifts;
+    a.out_stride = shift_stride;
+    a.ccmax = upsample == 1 ? ccmax : nullptr;
+    CHK(argmax(h, X, N, B, a));
+    if (upsample == 1) return TOMO_XCORR_OK;
+    const int region = (int)std::ceil(upsample * 1.5);
+    const double dftshift = std::trunc(region / 2.0);
+    double2 *E0 = nullptr, *E1 = nullptr, *Tt = nullptr, *CC = nullptr;
+    CHK(bufp(h, "E0", (size_t)region * nx * B, &E0));
+    CHK(bufp(h, "E1", (size_t)region * nz * B, &E1));
+    CHK(bufp(h, "T", (size_t)region * nx * B, &Tt));
+    CHK(bufp(h, "CC", (size_t)region * region * B, &CC));
+    k_updft_kernels<<<grid1((long)region * (nx + nz), B), TPB, 0, h->stream>>>(shifts, shift_stride, nx, nz, upsample, region, dftshift,
+                                                                                E0, E1);
+    CHK(check_launch(h));
+    // T[b][a1][j] = sum_k P[b][j][k] * E1[b][a1][k]   (the last axis first, as skimage does)
+    Gemm g1{P, N, nz, 1, E1, (long)region * nz, nz, 1, Tt, (long)region * nx, 1, nx, nx, region, nz};
+    k_zgemm<<<dim3((region + 15) / 16, (nx + 15) / 16, B), TPB, 0, h->stream>>>(g1);
+    // CC[b][a0][a1] = sum_j E0[b][a0][j] * T[b][a1][j]
+    Gemm g2{E0, (long)region * nx, nx, 1, Tt, (long)region * nx, nx, 1, CC, (long)region * region, region, 1, region, region, nx};
+    k_zgemm<<<dim3((region + 15) / 16, (region + 15) / 16, B), TPB, 0, h->stream>>>(g2);
+    CHK(check_launch(h));
+    a.mode = PEAK_FINE;
+    a.region = region;
+    a.dftshift = dftshift;
+    a.x = CC;
+    a.len = (long)region * region;
+    a.ccmax = ccmax;
+    return argmax(h, CC, (long)region * region, B, a);
+}
+
+int spline_shift_planes(tomo_xcorr *h, const void *in, int dtype, int B, int nx, int nz, const double *shift, long shift_stride,
+                        void *out) {
+    const long N = (long)nx * nz;
+    double *c = nullptr;
+    CHK(bufp(h, "coef", (size_t)N * B, &c));
+    if (dtype == 0) k_spline_axis0<float><<<grid1(nz, B), TPB, 0, h->stream>>>((const float *)in, nx, nz, c);
+    else k_spline_axis0<double><<<grid1(nz, B), TPB, 0, h->stream>>>((const double *)in, nx, nz, c);
+    k_spline_axis1<<<grid1(nx, B), TPB, 0, h->stream>>>(nx, nz, c);
+    if (dtype == 0) k_shift_interp<float><<<grid1(N, B), TPB, 0, h->stream>>>(c, shift, shift_stride, nx, nz, (float *)out);
+    else k_shift_interp<double><<<grid1(N, B), TPB, 0, h->stream>>>(c, shift, shift_stride, nx, nz, (double *)out);
+    return check_launch(h);
+}
+
+int begin(tomo_xcorr *h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    h->t_plan = 0.0;
+    for (double &t : h->timing) t = 0.0;
+    return TOMO_XCORR_OK;
+}
+
+int finish_timing(tomo_xcorr *h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms;
+    for (int k = 0; k < 3; ++k) {
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+        h->timing[k + 1] = ms;
+    }
+    h->timing[0] = h->t_plan;
+    return TOMO_XCORR_OK;
+}
+
+// The two chains share everything but the step.
+int chain(tomo_xcorr *h, const void *proj, int dtype, int n, int nx, int nz, bool numpy_path, const double *rfilt, const double *kfilt,
+          int upsample, double *offsets, void *aligned) {
+    CHK(check_shape(h, n, nx, nz, dtype));
+    if (n > 0 && (!proj || !offsets || !aligned)) return fail(h, TOMO_XCORR_ERR_ARG, "NULL array");
+    if (numpy_path && (!rfilt || !kfilt)) return fail(h, TOMO_XCORR_ERR_ARG, "NULL filter");
+    if (!numpy_path && upsample < 1) return fail(h, TOMO_XCORR_ERR_ARG, "upsample_factor must be >= 1");
+    CHK(begin(h));
+    const long N = (long)nx * nz;
+    const size_t esz = dtype == 0 ? 4 : 8;
+    if (n == 0) return TOMO_XCORR_OK;
+    // every allocation and plan before the upload, so that nothing between upload and download synchronises
+    const int C = chunk_planes(N, n > 1 ? n - 1 : 1);
+    void *din = nullptr, *dout = nullptr;
+    double *doff = nullptr, *dW = nullptr, *dK = nullptr;
+    double2 *Fm = nullptr, *Fr = nullptr;
+    int *peak = nullptr;
+    CHK(buf(h, "in", esz * N * n, &din));
+    CHK(buf(h, "out", esz * N * n, &dout));
+    CHK(bufp(h, "off", (size_t)2 * n, &doff));
+    CHK(bufp(h, "Fm", (size_t)N * C, &Fm));
+    CHK(bufp(h, "Fr", (size_t)N, &Fr));
+    CHK(bufp(h, "peak", 2, &peak));
+    if (numpy_path) {
+        CHK(bufp(h, "W", (size_t)N, &dW));
+        CHK(bufp(h, "K", (size_t)N, &dK));
+    }
+    hipfftHandle p1, pc, plast;
+    CHK(plan(h, nx, nz, 1, &p1));
+    CHK(plan(h, nx, nz, C, &pc));
+    const int rem = (n - 1) % C;
+    CHK(plan(h, nx, nz, rem ? rem : C, &plast));
+    if (!numpy_path) {
+        // pcc_spectra's buffers, sized now (batch 1)
+        void *tmp;
+        const int region = (int)std::ceil(upsample * 1.5);
+        CHK(buf(h, "P", sizeof(double2) * N, &tmp));
+        CHK(buf(h, "X", sizeof(double2) * N, &tmp));
+        CHK(buf(h, "amax_v", sizeof(double) * G, &tmp));
+        CHK(buf(h, "amax_i", sizeof(int) * G, &tmp));
+        CHK(buf(h, "coef", sizeof(double) * N, &tmp));
+        if (upsample > 1) {
+            CHK(buf(h, "E0", sizeof(double2) * region * nx, &tmp));
+            CHK(buf(h, "E1", sizeof(double2) * region * nz, &tmp));
+            CHK(buf(h, "T", sizeof(double2) * region * nx, &tmp));
+            CHK(buf(h, "CC", sizeof(double2) * region * region, &tmp));
+        }
+    } else {
+        void *tmp;
+        CHK(buf(h, "P", sizeof(double2) * N, &tmp));
+        CHK(buf(h, "amax_v", sizeof(double) * G, &tmp));
+        CHK(buf(h, "amax_i", sizeof(int) * G, &tmp));
+        CHK(buf(h, "mean_part", sizeof(double) * G * C, &tmp));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, hipMemcpyAsync(din, proj, esz * N * n, hipMemcpyHostToDevice, h->stream));
+    if (numpy_path) {
+        HIPCHK(h, hipMemcpyAsync(dW, rfilt, sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dK, kfilt, sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipMemsetAsync(doff, 0, sizeof(double) * 2 * n, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dout, din, esz * N, hipMemcpyDeviceToDevice, h->stream));
+    for (int c0 = 1; c0 < n; c0 += C) {
+        const int m = std::min(C, n - c0);
+        const char *src = (const char *)din + esz * N * c0;
+        // the moving images' spectra for this chunk, batched
+        CHK(load_planes(h, src, dtype, N, m, numpy_path, dW, Fm));
+        FFTCHK(h, hipfftExecZ2Z(m == C ? pc : plast, (hipfftDoubleComplex *)Fm, (hipfftDoubleComplex *)Fm, HIPFFT_FORWARD));
+        for (int i = c0; i < c0 + m; ++i) {
+            const void *ref = (const char *)dout + esz * N * (i - 1);
+            const void *mov = (const char *)din + esz * N * i;
+            void *dst = (char *)dout + esz * N * i;
+            const double2 *fm = Fm + N * (i - c0);
+            CHK(load_planes(h, ref, dtype, N, 1, numpy_path, dW, Fr));
+            FFTCHK(h, hipfftExecZ2Z(p1, (hipfftDoubleComplex *)Fr, (hipfftDoubleComplex *)Fr, HIPFFT_FORWARD));
+            if (numpy_path) {
+                double2 *P = nullptr;
+                CHK(bufp(h, "P", (size_t)N, &P));
+                k_cross_power<<<grid1(N), TPB, 0, h->stream>>>(Fr, 0, fm, dK, 0, N, P);
+                CHK(check_launch(h));
+                FFTCHK(h, hipfftExecZ2Z(p1, (hipfftDoubleComplex *)P, (hipfftDoubleComplex *)P, HIPFFT_BACKWARD));
+                PeakArgs a{};
+                a.mode = PEAK_NUMPY;
+                a.nx = nx;
+                a.nz = nz;
+                a.x = P;
+                a.len = N;
+                a.out = doff + 2 * i;
+                a.peak = peak;
+                CHK(argmax(h, P, N, 1, a));
+                if (dtype == 0) k_roll<float><<<grid1(N), TPB, 0, h->stream>>>((const float *)mov, peak, nx, nz, (float *)dst);
+                else k_roll<double><<<grid1(N), TPB, 0, h->stream>>>((const double *)mov, peak, nx, nz, (double *)dst);
+                CHK(check_launch(h));
+            } else {
+                CHK(pcc_spectra(h, Fr, 0, fm, 1, nx, nz, upsample, 1, doff + 2 * i, 2, nullptr));
+                CHK(spline_shift_planes(h, mov, dtype, 1, nx, nz, doff + 2 * i, 2, dst));
+            }
+        }
+    }
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(offsets, doff, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(aligned, dout, esz * N * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    return finish_timing(h);
+}
+
+}  // namespace
+
+extern "C" {
+
+TOMO_API int tomo_xcorr_abi_version(void) { return 1; }
+
+TOMO_API int tomo_xcorr_device_count(int *n) {
+    if (!n) return fail(nullptr, TOMO_XCORR_ERR_ARG, "NULL");
+    *n = 0;
+    hipError_t e = hipGetDeviceCount(n);
+    if (e != hipSuccess) {
+        *n = 0;
+        return fail(nullptr, TOMO_XCORR_ERR_NODEV, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+    }
+    return TOMO_XCORR_OK;
+}
+
+TOMO_API int tomo_xcorr_create(int device, tomo_xcorr **out) {
+    if (!out) return fail(nullptr, TOMO_XCORR_ERR_ARG, "NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_XCORR_ERR_NODEV, "no HIP device");
+    if (device < 0 || device >= n) return fail(nullptr, TOMO_XCORR_ERR_ARG, "device out of range");
+    tomo_xcorr *h = new tomo_xcorr();
+    h->device = device;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&h->ev[k]);
+    if (e != hipSuccess) {
+        tomo_xcorr_destroy(h);
+        return fail(nullptr, TOMO_XCORR_ERR_HIP, std::string("stream/event creation: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return TOMO_XCORR_OK;
+}
+
+TOMO_API int tomo_xcorr_destroy(tomo_xcorr *h) {
+    if (!h) return TOMO_XCORR_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (auto &kv : h->plans) hipfftDestroy(kv.second);
+    for (auto &kv : h->bufs) {
+        if (kv.second.p) {
+            (void)hipFree(kv.second.p);
+            g_device_bytes -= (int64_t)kv.second.n;
+        }
+    }
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return TOMO_XCORR_OK;
+}
+
+TOMO_API const char *tomo_xcorr_last_error(tomo_xcorr *h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+TOMO_API int64_t tomo_xcorr_device_bytes(void) { return g_device_bytes.load(); }
+
+TOMO_API int tomo_xcorr_last_timing(tomo_xcorr *h, double *t4) {
+    if (!h || !t4) return fail(h, TOMO_XCORR_ERR_ARG, "NULL");
+    for (int k = 0; k < 4; ++k) t4[k] = h->timing[k];
+    return TOMO_XCORR_OK;
+}
+
+TOMO_API int tomo_xcorr_chain_numpy(tomo_xcorr *h, const void *proj, int dtype, int n, int nx, int nz, const double *rfilt,
+                                    const double *kfilt, double *offsets, void *aligned) {
+    return chain(h, proj, dtype, n, nx, nz, true, rfilt, kfilt, 1, offsets, aligned);
+}
+
+TOMO_API int tomo_xcorr_chain_skimage(tomo_xcorr *h, const void *proj, int dtype, int n, int nx, int nz, int upsample,
+                                      double *offsets, void *aligned) {
+    return chain(h, proj, dtype, n, nx, nz, false, nullptr, nullptr, upsample, offsets, aligned);
+}
+
+TOMO_API int tomo_xcorr_pcc_batch(tomo_xcorr *h, const double *refs, const double *movs, int B, int nx, int nz, int upsample,
+                                  int normalization, double *shifts, double *error, double *phasediff) {
+    CHK(check_shape(h, B, nx, nz, 1));
+    if (upsample < 1) return fail(h, TOMO_XCORR_ERR_ARG, "upsample_factor must be >= 1");
+    if (B > 0 && (!refs || !movs || !shifts || !error || !phasediff)) return fail(h, TOMO_XCORR_ERR_ARG, "NULL array");
+    CHK(begin(h));
+    if (B == 0) return TOMO_XCORR_OK;
+    const long N = (long)nx * nz;
+    const int C = chunk_planes(N, B);
+    const int region = (int)std::ceil(upsample * 1.5);
+    double *dref = nullptr, *dmov = nullptr, *dsh = nullptr, *derr = nullptr, *dph = nullptr, *psrc = nullptr, *ptgt = nullptr;
+    double2 *Fr = nullptr, *Fm = nullptr, *cc = nullptr;
+    CHK(bufp(h, "bref", (size_t)N * C, &dref));
+    CHK(bufp(h, "bmov", (size_t)N * C, &dmov));
+    CHK(bufp(h, "Fr", (size_t)N * C, &Fr));
+    CHK(bufp(h, "Fm", (size_t)N * C, &Fm));
+    CHK(bufp(h, "bsh", (size_t)2 * B, &dsh));
+    CHK(bufp(h, "berr", (size_t)B, &derr));
+    CHK(bufp(h, "bph", (size_t)B, &dph));
+    CHK(bufp(h, "bcc", (size_t)B, &cc));
+    CHK(bufp(h, "psrc", (size_t)G * C, &psrc));
+    CHK(bufp(h, "ptgt", (size_t)G * C, &ptgt));
+    void *tmp;
+    CHK(buf(h, "P", sizeof(double2) * N * C, &tmp));
+    CHK(buf(h, "X", sizeof(double2) * N * C, &tmp));
+    CHK(buf(h, "amax_v", sizeof(double) * G * C, &tmp));
+    CHK(buf(h, "amax_i", sizeof(int) * G * C, &tmp));
+    if (upsample > 1) {
+        CHK(buf(h, "E0", sizeof(double2) * region * nx * C, &tmp));
+        CHK(buf(h, "E1", sizeof(double2) * region * nz * C, &tmp));
+        CHK(buf(h, "T", sizeof(double2) * region * nx * C, &tmp));
+        CHK(buf(h, "CC", sizeof(double2) * region * region * C, &tmp));
+    }
+    hipfftHandle pc, plast;
+    CHK(plan(h, nx, nz, C, &pc));
+    const int rem = B % C;
+    CHK(plan(h, nx, nz, rem ? rem : C, &plast));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    for (int c0 = 0; c0 < B; c0 += C) {
+        const int m = std::min(C, B - c0);
+        hipfftHandle pl = m == C ? pc : plast;
+        HIPCHK(h, hipMemcpyAsync(dref, refs + N * c0, sizeof(double) * N * m, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dmov, movs + N * c0, sizeof(double) * N * m, hipMemcpyHostToDevice, h->stream));
+        CHK(load_planes(h, dref, 1, N, m, false, nullptr, Fr));
+        CHK(load_planes(h, dmov, 1, N, m, false, nullptr, Fm));
+        FFTCHK(h, hipfftExecZ2Z(pl, (hipfftDoubleComplex *)Fr, (hipfftDoubleComplex *)Fr, HIPFFT_FORWARD));
+        FFTCHK(h, hipfftExecZ2Z(pl, (hipfftDoubleComplex *)Fm, (hipfftDoubleComplex *)Fm, HIPFFT_FORWARD));
+        CHK(pcc_spectra(h, Fr, N, Fm, m, nx, nz, upsample, normalization ? 1 : 2, dsh + 2 * c0, 2, cc + c0));
+        k_sumsq_partial<<<dim3(G, m), TPB, 0, h->stream>>>(Fr, N, psrc);
+        k_sumsq_partial<<<dim3(G, m), TPB, 0, h->stream>>>(Fm, N, ptgt);
+        k_pcc_scalars<<<m, TPB, 0, h->stream>>>(psrc, ptgt, cc + c0, N, upsample, derr + c0, dph + c0);
+        CHK(check_launch(h));
+    }
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(shifts, dsh, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(error, derr, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(phasediff, dph, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    return finish_timing(h);
+}
+
+TOMO_API int tomo_xcorr_spline_shift(tomo_xcorr *h, const void *img, int dtype, int B, int nx, int nz, const double *shifts,
+                                     void *out) {
+    CHK(check_shape(h, B, nx, nz, dtype));
+    if (B > 0 && (!img || !shifts || !out)) return fail(h, TOMO_XCORR_ERR_ARG, "NULL array");
+    CHK(begin(h));
+    if (B == 0) return TOMO_XCORR_OK;
+    const long N = (long)nx * nz;
+    const size_t esz = dtype == 0 ? 4 : 8;
+    void *din = nullptr, *dout = nullptr, *tmp = nullptr;
+    double *dsh = nullptr;
+    CHK(buf(h, "sin", esz * N * B, &din));
+    CHK(buf(h, "sout", esz * N * B, &dout));
+    CHK(bufp(h, "ssh", (size_t)2 * B, &dsh));
+    CHK(buf(h, "coef", sizeof(double) * N * B, &tmp));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, hipMemcpyAsync(din, img, esz * N * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dsh, shifts, sizeof(double) * 2 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    CHK(spline_shift_planes(h, din, dtype, B, nx, nz, dsh, 2, dout));
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, dout, esz * N * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    return finish_timing(h);
+}
+
+}  // extern "C"
