@@ -127,6 +127,9 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
 /* HIP's current device is per thread: a thread other than the context's creator calls this once before it uses the context
  * (entry points that need a geometry also do it themselves).  One context must still not be used by two threads at the same time. */
 TOMO_API int tomo_ctx_make_current(tomo_ctx *ctx);
+/* The context's compute stream (a hipStream_t), for work another library enqueues in order with this context's kernels (libtomo_fbp.so's
+ * filter before tomo_adjoint).  tomo_ctx_set_cu_mask replaces the stream: ask again after it. */
+TOMO_API int tomo_ctx_stream(tomo_ctx *ctx, void **stream);
 TOMO_API int tomo_set_option(tomo_ctx *ctx, const char *key, int value);
 /* Restrict the context's compute stream to a subset of the CUs (hipExtStreamCreateWithCUMask: bit i of the mask = CU i in the HIP
  * runtime's numbering; n_words 32-bit words; n_words = 0 restores the unrestricted stream; an all-zero mask is refused).  Work queued on

@@ -52,6 +52,7 @@ SIGNATURES = {
     "tomo_memset0": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_size_t]),
     "tomo_sync": (ctypes.c_int, [_c_vp]),
     "tomo_ctx_make_current": (ctypes.c_int, [_c_vp]),
+    "tomo_ctx_stream": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_vp)]),
     "tomo_set_option": (ctypes.c_int, [_c_vp, ctypes.c_char_p, ctypes.c_int]),
     "tomo_ctx_set_cu_mask": (ctypes.c_int, [_c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]),
     "tomo_check_geometry": (ctypes.c_int, [ctypes.POINTER(TomoGeom), ctypes.POINTER(ctypes.c_int)]),
@@ -239,6 +240,13 @@ class Context(object):
         for c in cus:
             m[c // 32] |= 1 << (c % 32)
         self.check(self.lib.tomo_ctx_set_cu_mask(self.handle, m, words))
+
+    def stream(self):
+        """The compute stream (hipStream_t as an int; 0 = the null stream), for libraries that enqueue in order with this context's work
+        (recon/fbp.py).  Ask again after set_cu_mask, which replaces it."""
+        s = _c_vp()
+        self.check(self.lib.tomo_ctx_stream(self.handle, ctypes.byref(s)))
+        return s.value or 0
 
     def make_current(self):
         """Bind the CALLING thread to this context's GPU (HIP's current device is per thread; a new thread starts on device 0)."""

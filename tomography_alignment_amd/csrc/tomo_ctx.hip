@@ -152,6 +152,13 @@ extern "C" int tomo_ctx_make_current(tomo_ctx *ctx)
     return TOMO_OK;
 }
 
+extern "C" int tomo_ctx_stream(tomo_ctx *ctx, void **stream)
+{
+    if (!ctx || !stream) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_ctx_stream: null argument");
+    *stream = reinterpret_cast<void *>(ctx->stream);
+    return TOMO_OK;
+}
+
 extern "C" int tomo_ctx_set_cu_mask(tomo_ctx *ctx, const uint32_t *mask, int n_words)
 {
     if (!ctx || n_words < 0 || (n_words > 0 && !mask)) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_ctx_set_cu_mask: bad args");

@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 from .. import alignment
-from ..recon import sirt, sirt_mpi
+from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
 
 DEFAULT_BOUNDS = ((-3., 3.), (-3., 3.), (-0.02, 0.02), (-0.02, 0.02))        # examples/align_rigid.py:48
@@ -73,15 +73,27 @@ class OuterLoop(object):
         self.alpha_rec, self.beta_rec, self.xyz_rec = np.zeros(n_proj), np.zeros(n_proj), np.zeros((n_proj, 3))
         self.d_rec, self.solver = None, None
 
-    def reconstruct(self, sirt_iters=50, positivity=True):
+    def reconstruct(self, sirt_iters=50, positivity=True, init="zero"):
         """SIRT at the current pose estimates, warm-started from the previous reconstruction where it lies (examples/align_rigid.py:37-39,42).
-        -> (iterations done, rms_error[:k]); the reconstruction is self.d_rec."""
+        init: the start of the FIRST reconstruction -- "zero" (the reference's) or "fbp" (the filtered back-projection at the current pose
+        estimates, recon/fbp.py).  -> (iterations done, rms_error[:k]); the reconstruction is self.d_rec."""
+        if init not in ("zero", "fbp"):
+            raise ValueError("align_rigid: init must be 'zero' or 'fbp', not %r" % (init,))
         opts = {"_backend": self.be}
         if self.d_gt is not None:
             opts["ground_truth"] = self.d_gt
+        angles = np.array([self.phi, self.alpha_rec, self.beta_rec]).T
+        if self.d_rec is None and init == "fbp":
+            f_opts = {"_backend": self.be}
+            if self.comm is None:
+                f = fbp.FBP(self.geom, self.d_b, angles, self.xyz_rec, options=f_opts)
+            else:
+                f = fbp_mpi.FBP(self.comm, self.geom, self.d_b, angles, self.xyz_rec, options=f_opts)
+            f.run(positivity=positivity)
+            self.d_rec = f.d_rec
+            f = None
         if self.d_rec is not None:
             opts["rec"] = self.d_rec                                          # in place, in HBM
-        angles = np.array([self.phi, self.alpha_rec, self.beta_rec]).T
         self.solver = None              # drop the previous solver's buffers BEFORE the next one allocates its own (d_rec is held separately)
         if self.comm is None:
             self.solver = sirt.SIRT(self.geom, self.d_b, angles, self.xyz_rec, options=opts)
@@ -117,8 +129,9 @@ class OuterLoop(object):
 
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
-        kernel_names=None, download=True, return_loop=False):
+        kernel_names=None, download=True, return_loop=False, init="zero"):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
+    init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
     kernel_names   with a HIP context: the history carries the HIP-event kernel time of each half of each outer iteration for these names.
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
@@ -129,7 +142,7 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     for it in range(n_outer):
         k0 = _kernel_ms(ctx, kernel_names)
         t0 = time.perf_counter()
-        k_done, err = loop.reconstruct(sirt_iters)
+        k_done, err = loop.reconstruct(sirt_iters, init=init)
         if ctx is not None:
             ctx.sync()
         t1 = time.perf_counter()
@@ -163,13 +176,14 @@ def main():
     ap.add_argument("data")
     ap.add_argument("--outer", type=int, default=5)
     ap.add_argument("--sirt-iters", type=int, default=50)
+    ap.add_argument("--init", choices=("zero", "fbp"), default="zero", help="start of the first SIRT: zero or the FBP")
     a = ap.parse_args()
     import os
     comm = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:       # launched one process per GPU: python -m torch.distributed.run --nproc-per-node N -m ...
         from ..comm import RcclComm
         comm = RcclComm.from_env()
-    run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm)
+    run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init)
     if comm is not None:
         comm.close()
 

@@ -22,11 +22,12 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0):
     geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2))
     phi = np.linspace(0.0, np.pi, n_proj)
     a100, s100 = int(round(100 * ang_deg)), int(round(100 * shift_px))
-    alpha = np.deg2rad(rng.randint(-a100, a100, n_proj) / 100)          # examples/generate_data.py:17-18
-    beta = np.deg2rad(rng.randint(-a100, a100, n_proj) / 100)
+    jitter = lambda m: rng.randint(-m, m, n_proj) / 100 if m > 0 else np.zeros(n_proj)      # noqa: E731 (m = 0: nominal poses)
+    alpha = np.deg2rad(jitter(a100))                                    # examples/generate_data.py:17-18
+    beta = np.deg2rad(jitter(a100))
     xyz = np.zeros((n_proj, 3))
-    xyz[:, 0] = rng.randint(-s100, s100, n_proj) / 100                  # :22-23 (motion along the beam is invisible)
-    xyz[:, 2] = rng.randint(-s100, s100, n_proj) / 100
+    xyz[:, 0] = jitter(s100)                                            # :22-23 (motion along the beam is invisible)
+    xyz[:, 2] = jitter(s100)
     proj_obj = projection_operators.ProjectionMatrix(geom, precision=np.float32)
     pmat = proj_obj.projection_matrix(alpha=alpha, beta=beta, phi=phi, xyz_shift=xyz)
     proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
