@@ -1,0 +1,142 @@
+"""CPU tests of tomography_alignment_amd/preprocess.py: the numpy models (tests/prep_model.py), their pinned effect, argument validation
+before any launch, the ctypes table against include/tomo_prep.h, and the argument handling of examples/preprocess.py."""
+import os
+import re
+
+import numpy as np
+import pytest
+from scipy import ndimage
+
+import prep_model as pm
+from conftest import ROOT
+
+from tomography_alignment_amd import _prep_lib, preprocess
+from tomography_alignment_amd.examples import generate_data
+from tomography_alignment_amd.examples import preprocess as ex_pre
+from tomography_alignment_amd.utilities import generate_phantom
+
+
+def test_normalize_model_follows_the_order_of_operations():
+    raw = np.array([[[0, 50, 100, 1000, 65535]]], np.uint16)
+    flats = np.array([[[1000, 1000, 100, 1000, 1000]]], np.uint16)
+    darks = np.array([[[100, 100, 100, 100, 100]]], np.uint16)
+    r = pm.normalize(raw, flats, darks, minus_log=False)[0, :, 0]
+    f32 = np.float32
+    den = np.array([900, 900, 1e-6, 900, 900], f32)
+    np.testing.assert_array_equal(r, ((np.array([0, 50, 100, 1000, 65535], f32) - f32(100)) / den).astype(f32))
+    out = pm.normalize(raw, flats, darks, cutoff=1.0)[0, :, 0]
+    assert np.all(np.isfinite(out))
+    assert out[0] == -np.log(f32(1e-6)) and out[3] == out[4] == -np.log(f32(1.0))     # below-dark clamps to min_ratio; saturation cut
+    t = pm.normalize(np.zeros((2, 3, 4), np.float32) + 5, np.full((3, 4), 9, np.float32), np.ones((3, 4), np.float32),
+                     crop=((1, 3), (0, 2)))
+    assert t.shape == (2, 2, 2)
+
+
+def test_reference_models():
+    f = np.array([[[3.0]], [[1.0]], [[7.0]], [[2.0]]], np.float32)
+    assert pm.reference_median(f)[0, 0] == np.float32(2.5)
+    assert pm.reference_median(f[:3])[0, 0] == np.float32(3.0)
+    assert pm.reference_mean(f)[0, 0] == np.float32(13.0 / 4)
+
+
+def test_stripe_model_matches_a_direct_restatement_of_vo_algorithm_3():
+    rng = np.random.default_rng(0)
+    for n, nx, size in ((180, 128, 21), (37, 20, 3), (64, 63, 63)):
+        s = rng.standard_normal((n, nx)).astype(np.float32)          # continuous: no ties
+        assert np.array_equal(pm.remove_stripe_sorting(s[:, :, None], size)[:, :, 0], pm.remove_stripe_sorting_vo(s, size))
+
+
+def test_stripe_model_orders_ties_stably_and_the_two_zeros_as_one():
+    p = np.array([-0.0, 0.0, -0.0, 1.0, 0.0], np.float32)[:, None, None]
+    order = np.argsort(pm.stripe_keys(p), axis=0, kind="stable")[:, 0, 0]
+    assert list(order) == [0, 1, 2, 4, 3]
+    k = pm.stripe_keys(np.array([-np.inf, -1.0, 0.0, 1.0, np.inf, np.nan], np.float32))
+    assert np.all(np.diff(k) > 0)
+
+
+def test_stripe_model_pinned_effect_on_a_phantom_sinogram():
+    N, n = 128, 180
+    ph = generate_phantom.shepp3d(N)[:, :, N // 2].astype(np.float64)
+    sino = np.stack([ndimage.rotate(ph, a, reshape=False, order=1).sum(0) for a in np.linspace(0, 180, n, endpoint=False)])
+    rng = np.random.default_rng(1)
+    mu, i0 = 4.0 / N, 2e4
+    gain = np.ones(N)
+    cols = rng.choice(N, 12, replace=False)
+    gain[cols] += 0.05 * rng.choice([-1, 1], 12)
+    p = (-np.log(np.maximum(rng.poisson(i0 * gain * np.exp(-mu * sino)) / i0, 1e-6))).astype(np.float32)
+    q = pm.remove_stripe_sorting(p[:, :, None], 21)[:, :, 0]
+    a0, a1 = pm.stripe_amplitude(p), pm.stripe_amplitude(q)
+    assert a1 * 10 <= a0, (a0, a1)                  # measured: 1.8e-2 -> 3.8e-4 (48x)
+    clean = (-np.log(np.maximum(rng.poisson(i0 * np.exp(-mu * sino)) / i0, 1e-6))).astype(np.float32)
+    qc = pm.remove_stripe_sorting(clean[:, :, None], 21)[:, :, 0]
+    assert np.linalg.norm(qc - clean) / np.linalg.norm(clean) < 0.1      # measured: 0.055 (mostly Poisson noise removed along x)
+
+
+@pytest.mark.parametrize("kw, msg", [
+    (dict(size=4), "odd"), (dict(size=1), "odd"), (dict(size=65), "odd"), (dict(size=21.5), "odd integer"),
+    (dict(max_scratch_bytes=-1), "max_scratch_bytes"),
+])
+def test_stripe_arguments_are_checked_before_any_launch(kw, msg):
+    with pytest.raises(ValueError, match=msg):
+        preprocess.remove_stripe_sorting(np.zeros((4, 64, 3), np.float32), **kw)
+
+
+def test_stripe_rejects_bad_shapes_and_dtypes():
+    with pytest.raises(ValueError, match="odd"):
+        preprocess.remove_stripe_sorting(np.zeros((4, 10, 3), np.float32), size=11)      # size > nx
+    with pytest.raises(ValueError, match="float32"):
+        preprocess.remove_stripe_sorting(np.zeros((4, 10, 3), np.uint16), size=3)
+    with pytest.raises(ValueError, match="dimensions"):
+        preprocess.remove_stripe_sorting(np.zeros((4, 10), np.float32), size=3)
+
+
+def test_normalize_arguments_are_checked_before_any_launch():
+    fr = np.zeros((2, 4, 5), np.uint16)
+    ok = np.zeros((4, 5), np.uint16)
+    with pytest.raises(ValueError, match="frame shape|frames' shape"):
+        preprocess.normalize(fr, np.zeros((3, 4, 6), np.uint16), ok)
+    with pytest.raises(ValueError, match="same frame shape"):
+        preprocess.normalize(fr, ok, np.zeros((4, 6), np.uint16))
+    with pytest.raises(ValueError, match="uint16 or float32"):
+        preprocess.normalize(fr.astype(np.int32), ok, ok)
+    with pytest.raises(ValueError, match="outside"):
+        preprocess.normalize(fr, ok, ok, crop=((0, 5), (0, 5)))
+    with pytest.raises(ValueError, match="outside"):
+        preprocess.normalize(fr, ok, ok, crop=(slice(2, 2), slice(None)))
+    with pytest.raises(ValueError, match="min_ratio"):
+        preprocess.normalize(fr, ok, ok, min_ratio=0.0)
+    with pytest.raises(ValueError, match="method"):
+        preprocess.normalize(fr, ok, ok, method="max")
+    with pytest.raises(ValueError, match="dimensions"):
+        preprocess.normalize(fr[0], ok, ok)
+    with pytest.raises(_prep_lib.PrepUnsupported):
+        preprocess.reference_frames(np.zeros((65, 4, 5), np.uint16), ok, method="median")
+
+
+def test_ctypes_table_matches_the_header():
+    hdr = open(os.path.join(ROOT, "include", "tomo_prep.h")).read()
+    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]+?\b(tomo_prep_\w+)\s*\(", hdr))
+    assert declared == set(_prep_lib.SIGNATURES)
+    for name, value in (("TOMO_PREP_MAX_NPROJ", _prep_lib.MAX_NPROJ), ("TOMO_PREP_ERR_UNSUPPORTED", _prep_lib.ERR_UNSUPPORTED)):
+        assert re.search(r"%s\s*=?\s*%d\b" % (name, value), hdr), name
+
+
+def test_example_cli_arguments():
+    a = ex_pre.parse_args(["raw.npz", "--out", "d.npz", "--stripe-size", "11", "--method", "median", "--crop", "0", "8", "2", "10"])
+    assert (a.data, a.out, a.stripe_size, a.method, a.crop) == ("raw.npz", "d.npz", 11, "median", ((0, 8), (2, 10)))
+    assert ex_pre.parse_args(["raw.npz", "--stripe-size", "0"]).stripe_size == 0
+    for bad in (["raw.npz", "--stripe-size", "4"], ["raw.npz", "--method", "max"], ["raw.npz", "--crop", "1", "2"]):
+        with pytest.raises(SystemExit):
+            ex_pre.parse_args(bad)
+    with pytest.raises(ValueError, match="counts"):
+        ex_pre.run({"projections": np.zeros((1, 1, 1))})
+
+
+def test_make_raw_frames():
+    proj = np.random.default_rng(0).uniform(0, 16, (6, 32, 5))
+    d = generate_data.make_raw(proj, seed=3)
+    assert d["counts"].shape == (6, 5, 32) and d["counts"].dtype == np.uint16
+    assert d["flats"].shape[1:] == (5, 32) and d["darks"].shape[1:] == (5, 32)
+    assert d["mu"] == 4.0 / 32
+    est = -np.log((d["counts"] - d["darks"].mean(0)) / (d["flats"].mean(0) - d["darks"].mean(0)))
+    assert abs(np.median(est / d["mu"] - proj.transpose(0, 2, 1))) < 0.5

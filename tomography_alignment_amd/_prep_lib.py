@@ -1,0 +1,141 @@
+"""
+ctypes binding of libtomo_prep.so (include/tomo_prep.h): flat-field normalisation and stripe removal of preprocess.py.
+
+As with _lib, there is NO CPU fallback: if the library or a device is missing, every entry point raises.
+"""
+import ctypes
+import os
+import threading
+
+from ._lib import TomoError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("TOMO_PREP_LIB") or os.path.join(_HERE, "libtomo_prep.so")   # override: development builds only
+
+_c_vp = ctypes.c_void_p
+_c_int = ctypes.c_int
+_c_float = ctypes.c_float
+_c_fp = ctypes.POINTER(ctypes.c_float)
+
+ERR_UNSUPPORTED = 4       # TOMO_PREP_ERR_UNSUPPORTED
+U16, F32 = 0, 1           # TOMO_PREP_U16, TOMO_PREP_F32
+MEAN, MEDIAN = 0, 1       # TOMO_PREP_MEAN, TOMO_PREP_MEDIAN
+MAX_NPROJ = 8192          # TOMO_PREP_MAX_NPROJ
+MAX_MEDIAN_FRAMES = 64
+MAX_STRIPE_SIZE = 63
+
+# every symbol include/tomo_prep.h declares: name -> (restype, argtypes)
+SIGNATURES = {
+    "tomo_prep_abi_version": (_c_int, []),
+    "tomo_prep_create": (_c_int, [_c_int, ctypes.POINTER(_c_vp)]),
+    "tomo_prep_destroy": (_c_int, [_c_vp]),
+    "tomo_prep_last_error": (ctypes.c_char_p, [_c_vp]),
+    "tomo_prep_reference": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
+    "tomo_prep_normalize": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
+                                     _c_int, _c_float, _c_int, _c_float, _c_vp]),
+    "tomo_prep_stripe_chunk": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_size_t, ctypes.POINTER(_c_int)]),
+    "tomo_prep_stripe_sorting": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, ctypes.c_size_t, _c_fp]),
+}
+
+_lib = None
+_lock = threading.Lock()
+
+
+class PrepUnsupported(TomoError):
+    """A shape the kernels do not support: more than 8192 angles for the stripe removal, or a median over more than 64 frames."""
+
+
+def load():
+    """Load libtomo_prep.so and bind every symbol; raises TomoError (never falls back) on failure."""
+    global _lib
+    with _lock:
+        if _lib is None:
+            if not os.path.exists(LIB_PATH):
+                raise TomoError("libtomo_prep.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
+                                "`make -C tomography_alignment_amd/csrc/prep`; there is no CPU fallback" % LIB_PATH)
+            try:
+                lib = ctypes.CDLL(LIB_PATH)
+            except OSError as e:
+                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
+            for name, (res, args) in SIGNATURES.items():
+                fn = getattr(lib, name)          # AttributeError if include/tomo_prep.h and the .so disagree
+                fn.restype = res
+                fn.argtypes = args
+            if lib.tomo_prep_abi_version() != 1:
+                raise TomoError("libtomo_prep.so ABI version mismatch")
+            _lib = lib
+    return _lib
+
+
+def stripe_chunk(n_proj, ndx, ndz, max_scratch_bytes=0):
+    """The z rows per chunk tomo_prep_stripe_sorting uses for this shape and scratch budget (0: no limit)."""
+    lib = load()
+    zc = _c_int(0)
+    if lib.tomo_prep_stripe_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)) != 0:
+        raise TomoError("tomo_prep_stripe_chunk: %s" % (lib.tomo_prep_last_error(None) or b"").decode(errors="replace"))
+    return zc.value
+
+
+class PrepHandle(object):
+    """One tomo_prep handle: a device, the stripe scratch and the last error.  A context manager; close() frees everything.  device: the
+    tomo context's (ctx.device) -- every call is enqueued on the stream it is given, in practice that context's."""
+
+    def __init__(self, device=0):
+        self._h = None
+        self.lib = load()
+        h = _c_vp()
+        self._check(self.lib.tomo_prep_create(int(device), ctypes.byref(h)), None)
+        self._h = h
+        self.device = int(device)
+
+    def _check(self, rc, h="self"):
+        if rc != 0:
+            msg = (self.lib.tomo_prep_last_error(self._h if h == "self" else h) or b"").decode(errors="replace")
+            raise (PrepUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_prep error %d: %s" % (rc, msg))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise TomoError("prep handle closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self.lib.tomo_prep_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+    def reference(self, stream, d_frames, dtype, n, rows, cols, method, d_out):
+        self._check(self.lib.tomo_prep_reference(self.handle, _ptr(stream), _ptr(d_frames), int(dtype), int(n), int(rows), int(cols),
+                                                 int(method), _ptr(d_out)))
+
+    def normalize(self, stream, d_raw, dtype, n, rows, cols, d_flat, d_dark, crop, cutoff, minus_log, min_ratio, d_out):
+        (z0, z1), (x0, x1) = crop
+        self._check(self.lib.tomo_prep_normalize(self.handle, _ptr(stream), _ptr(d_raw), int(dtype), int(n), int(rows), int(cols),
+                                                 _ptr(d_flat), _ptr(d_dark), int(z0), int(z1), int(x0), int(x1), 0 if cutoff is None else 1,
+                                                 0.0 if cutoff is None else float(cutoff), 1 if minus_log else 0, float(min_ratio),
+                                                 _ptr(d_out)))
+
+    def stripe_sorting(self, stream, d_in, d_out, n_proj, ndx, ndz, size, max_scratch_bytes=0, timed=False):
+        """Enqueue the stripe removal; timed=True synchronises and returns the device ms of the sort, median and scatter passes."""
+        ms = (ctypes.c_float * 3)() if timed else None
+        self._check(self.lib.tomo_prep_stripe_sorting(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
+                                                      int(size), int(max_scratch_bytes), ms))
+        return tuple(ms) if timed else None
+
+
+def _ptr(p):
+    if isinstance(p, ctypes.c_void_p):
+        return p
+    return _c_vp(int(p)) if p else None

@@ -1,0 +1,506 @@
+// libtomo_prep.so: preprocessing of raw projections (tomography_alignment_amd/preprocess.py) on gfx950.
+//
+// k_reference_mean     one thread per pixel: a float64 sum over the frames in frame order, / n, rounded once to float32.
+// k_reference_median   one thread per pixel, the pixel's n <= 64 values as orderable keys in LDS (column per thread: conflict-free); the
+//                      value of rank k is the one whose count of smaller keys is <= k and of smaller-or-equal keys is > k (exact, and the
+//                      same value whichever of several equal keys is taken).
+// k_normalize          a 64 x 64 (z, x) tile per work-group: frame rows read coalesced along x, normalised on the way into LDS, written
+//                      coalesced along z from the transposed tile (row stride 65: the column reads hit distinct banks).
+// stripe removal, per chunk of z rows (scratch: sorted values S and median M as float32, the permutation P as uint16, all [rank][x][zl]):
+//   k_stripe_sort      (K1) one work-group per x and group of ZC adjacent z columns: the n angles of each column go to LDS as 64-bit
+//                      keys (orderable value bits << 32 | angle), padded with ~0 to a power of two Np, and are sorted by a bitonic
+//                      network over all ZC segments at once; sorted values and angles are written with rank in place of angle.
+//   k_stripe_median    (K2) a z-coalesced stencil: a (64 z) x (64 x) tile plus the reflected halo staged in LDS, one thread per z and
+//                      16 x, the window of `size` keys in registers, exact selection by counting.
+//   k_stripe_scatter   (K3) the inverse of K1: the filtered values are scattered to their angles in LDS and written coalesced.
+// Every key is unique (the angle is part of it), so the sort is the stable order numpy's argsort(kind='stable') gives.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../../include/tomo_prep.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+constexpr int SORT_KEYS = 8192;        // 64-bit keys per K1 work-group (64 KiB of LDS)
+constexpr int SCATTER_VALS = 16384;    // float32 values per K3 work-group (64 KiB of LDS)
+constexpr int MAX_ZC = 64;             // z columns per K1 / K3 work-group
+constexpr int SORT_T = 512;
+constexpr int SCATTER_T = 256;
+constexpr int MED_TZ = 64, MED_TX = 64, MED_T = 256;      // K2 tile: 64 z x 64 x, 4 threads along x each doing 16
+constexpr int NORM_TILE = 64, NORM_T = 256, NORM_FR = 16;     // k_normalize: 64 x 64 tile, 16 frames per work-group
+constexpr int REF_T = 256;
+constexpr int MAX_LDS = (SORT_KEYS + MAX_ZC) * 8;         // the largest dynamic LDS any kernel here asks for
+
+// orderable bits: unsigned order = float order; -0 is canonicalised to +0 first, every NaN maps to one key above +inf
+__device__ __forceinline__ uint32_t ord_bits(float v) {
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float from_ord(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
+
+template <typename T>
+__device__ __forceinline__ float to_f(T v) { return (float)v; }
+
+// ---- reference frames
+template <typename T>
+__global__ __launch_bounds__(REF_T) void k_reference_mean(const T *__restrict__ in, float *__restrict__ out, int n, size_t npix) {
+    const size_t p = (size_t)blockIdx.x * REF_T + threadIdx.x;
+    if (p >= npix) return;
+    double s = 0.0;
+    for (int j = 0; j < n; ++j) s += (double)in[(size_t)j * npix + p];
+    out[p] = (float)(s / (double)n);
+}
+
+template <typename T>
+__global__ __launch_bounds__(REF_T) void k_reference_median(const T *__restrict__ in, float *__restrict__ out, int n, size_t npix) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint32_t *keys = reinterpret_cast<uint32_t *>(smem);
+    const size_t p = (size_t)blockIdx.x * REF_T + threadIdx.x;
+    const bool live = p < npix;
+    for (int j = 0; j < n; ++j) keys[j * REF_T + threadIdx.x] = live ? ord_bits(to_f(in[(size_t)j * npix + p])) : 0u;
+    if (!live) return;                    // no barrier below: each thread reads only its own column
+    const int k1 = (n - 1) / 2, k2 = n / 2;
+    uint32_t a = 0, b = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t ki = keys[i * REF_T + threadIdx.x];
+        int lt = 0, le = 0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t kj = keys[j * REF_T + threadIdx.x];
+            lt += kj < ki;
+            le += kj <= ki;
+        }
+        if (lt <= k1 && k1 < le) a = ki;
+        if (lt <= k2 && k2 < le) b = ki;
+    }
+    out[p] = (k1 == k2) ? from_ord(a) : (float)(0.5 * ((double)from_ord(a) + (double)from_ord(b)));
+}
+
+// ---- normalisation with the transpose; grid: tiles_z * tiles_x * frame groups, tile fastest.  A work-group keeps its tile's flat and
+// dark (16 values per thread) in registers across NORM_FR frames, so they are read once per group, not once per frame.
+template <typename T>
+__global__ __launch_bounds__(NORM_T) void k_normalize(const T *__restrict__ raw, const float *__restrict__ flat, const float *__restrict__ dark,
+                                                      float *__restrict__ out, int n, int rows, int cols, int z0, int x0, int nz, int nx,
+                                                      int tiles_z, int tiles_x, int use_cutoff, float cutoff, int minus_log, float min_ratio) {
+    constexpr int PER = NORM_TILE * NORM_TILE / NORM_T;
+    __shared__ float tile[NORM_TILE][NORM_TILE + 1];
+    const int tiles = tiles_z * tiles_x;
+    const int i0 = (int)(blockIdx.x / (unsigned)tiles) * NORM_FR;
+    const int t = (int)(blockIdx.x % (unsigned)tiles);
+    const int zt = (t / tiles_x) * NORM_TILE, xt = (t % tiles_x) * NORM_TILE;
+    const int tx = threadIdx.x % NORM_TILE, ty = threadIdx.x / NORM_TILE;
+    float dk[PER], den[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int z = zt + ty + q * (NORM_T / NORM_TILE), x = xt + tx;
+        dk[q] = 0.f;
+        den[q] = 1.f;
+        if (z < nz && x < nx) {
+            const size_t o = (size_t)(z0 + z) * cols + (x0 + x);
+            dk[q] = dark[o];
+            const float d = flat[o] - dk[q];
+            den[q] = d < 1e-6f ? 1e-6f : d;
+        }
+    }
+    const int i1 = min(n, i0 + NORM_FR);
+    for (int i = i0; i < i1; ++i) {
+        const T *fr = raw + (size_t)i * rows * cols;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int zz = ty + q * (NORM_T / NORM_TILE), z = zt + zz, x = xt + tx;
+            float v = 0.f;
+            if (z < nz && x < nx) {
+                float r = (to_f(fr[(size_t)(z0 + z) * cols + (x0 + x)]) - dk[q]) / den[q];
+                if (use_cutoff) r = fminf(r, cutoff);
+                v = minus_log ? -logf(fmaxf(r, min_ratio)) : r;
+            }
+            tile[zz][tx] = v;
+        }
+        __syncthreads();
+        float *po = out + (size_t)i * nx * nz;
+        for (int xx = ty; xx < NORM_TILE; xx += NORM_T / NORM_TILE) {
+            const int x = xt + xx, z = zt + tx;
+            if (x < nx && z < nz) po[(size_t)x * nz + z] = tile[tx][xx];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- stripe removal
+// K1.  grid: (ndx, groups of ZC z columns of the chunk).  lds index of (segment c, rank r): c (Np + 1) + r.
+__global__ __launch_bounds__(SORT_T) void k_stripe_sort(const float *__restrict__ p, float *__restrict__ S, uint16_t *__restrict__ P, int n,
+                                                         int ndx, int ndz, int zb, int zw, int logNp, int ZC) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t *keys = reinterpret_cast<uint64_t *>(smem);
+    const int Np = 1 << logNp;
+    const int x = blockIdx.x, zg = blockIdx.y * ZC;
+    const int total = ZC * Np;
+    for (int e = threadIdx.x; e < total; e += SORT_T) {
+        const int c = e % ZC, a = e / ZC, zl = zg + c;
+        uint64_t key = ~0ull;
+        if (a < n && zl < zw) key = ((uint64_t)ord_bits(p[((size_t)a * ndx + x) * ndz + zb + zl]) << 32) | (uint32_t)a;
+        keys[c * (Np + 1) + a] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= Np; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < total / 2; t += SORT_T) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));     // i has bit j clear; its partner is i + j, in the same segment
+                const int pi = i + (i >> logNp), pl = pi + j;
+                const bool asc = (i & k & (Np - 1)) == 0;
+                const uint64_t u = keys[pi], v = keys[pl];
+                if ((u > v) == asc) {
+                    keys[pi] = v;
+                    keys[pl] = u;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int e = threadIdx.x; e < ZC * n; e += SORT_T) {
+        const int c = e % ZC, r = e / ZC, zl = zg + c;
+        if (zl < zw) {
+            const uint64_t key = keys[c * (Np + 1) + r];
+            const size_t o = ((size_t)r * ndx + x) * zw + zl;
+            S[o] = from_ord((uint32_t)(key >> 32));
+            P[o] = (uint16_t)(key & 0xffffu);
+        }
+    }
+}
+
+// K2.  grid: (tiles of 64 z of the chunk, tiles of 64 x, n).  W: the compile-time window (>= size); the slots past `size` hold the
+// largest key, so they are never counted as smaller than a real value.
+__device__ __forceinline__ int reflect(int i, int n) {
+    if (i < 0) i = -i - 1;
+    if (i >= n) i = 2 * n - i - 1;
+    return i < 0 ? 0 : (i >= n ? n - 1 : i);      // halo rows of a ragged last tile: any valid row (their outputs are not written)
+}
+
+template <int W>
+__global__ __launch_bounds__(MED_T) void k_stripe_median(const float *__restrict__ S, float *__restrict__ M, int ndx, int zw, int size) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *tile = reinterpret_cast<float *>(smem);         // [MED_TX + size - 1][MED_TZ]
+    const int h = size / 2, k = size / 2;
+    const int zt = blockIdx.x * MED_TZ, xt = blockIdx.y * MED_TX;
+    const size_t plane = (size_t)blockIdx.z * ndx * zw;
+    const int rows = MED_TX + 2 * h;
+    const int tz = threadIdx.x % MED_TZ, tx = threadIdx.x / MED_TZ;
+    const int z = zt + tz;
+    for (int rr = tx; rr < rows; rr += MED_T / MED_TZ) {
+        const int x = reflect(xt - h + rr, ndx);
+        tile[rr * MED_TZ + tz] = z < zw ? S[plane + (size_t)x * zw + z] : 0.f;
+    }
+    __syncthreads();
+    if (z >= zw) return;
+    for (int xx = tx * (MED_TX / 4); xx < (tx + 1) * (MED_TX / 4); ++xx) {
+        const int x = xt + xx;
+        if (x >= ndx) break;
+        float v[W];
+        uint32_t o[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            v[j] = j < size ? tile[(xx + j) * MED_TZ + tz] : __uint_as_float(0x7fffffffu);
+            o[j] = j < size ? ord_bits(v[j]) : 0xffffffffu;
+        }
+        float res = 0.f;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {       // a padding candidate has size smaller keys (> k): never taken, unless NaNs reach rank k
+            int lt = 0, le = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                lt += o[j] < o[i];
+                le += o[j] <= o[i];
+            }
+            if (lt <= k && k < le) res = v[i];
+        }
+        M[plane + (size_t)x * zw + z] = res;
+    }
+}
+
+// K3.  grid: (ndx, groups of ZC z columns of the chunk).  lds index of (column c, angle a): c (n + 1) + a.
+__global__ __launch_bounds__(SCATTER_T) void k_stripe_scatter(const float *__restrict__ M, const uint16_t *__restrict__ P, float *out, int n,
+                                                               int ndx, int ndz, int zb, int zw, int ZC) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *vals = reinterpret_cast<float *>(smem);
+    const int x = blockIdx.x, zg = blockIdx.y * ZC;
+    for (int e = threadIdx.x; e < ZC * n; e += SCATTER_T) {
+        const int c = e % ZC, r = e / ZC, zl = zg + c;
+        if (zl < zw) {
+            const size_t o = ((size_t)r * ndx + x) * zw + zl;
+            vals[c * (n + 1) + P[o]] = M[o];
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < ZC * n; e += SCATTER_T) {
+        const int c = e % ZC, a = e / ZC, zl = zg + c;
+        if (zl < zw) out[((size_t)a * ndx + x) * ndz + zb + zl] = vals[c * (n + 1) + a];
+    }
+}
+
+}  // namespace
+
+struct tomo_prep {
+    int device = 0;
+    std::string err;
+    void *d_scratch = nullptr;                 // stripe scratch: S, M (float32) and P (uint16) of one chunk
+    size_t scratch_cap = 0;
+    hipStream_t last_stream = nullptr;         // the stream the scratch was last used on
+    hipEvent_t ev_done = nullptr;              // after the last use of the scratch
+    hipEvent_t ev_pass[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool pending = false;
+};
+
+namespace {
+
+int fail(tomo_prep *h, int code, const std::string &msg) {
+    if (h) h->err = msg; else g_err = msg;
+    return code;
+}
+
+#define HIPCHK(h, call)                                                                                               \
+    do {                                                                                                              \
+        hipError_t e_ = (call);                                                                                       \
+        if (e_ != hipSuccess) return fail(h, TOMO_PREP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
+    } while (0)
+
+template <typename K>
+int allow_lds(tomo_prep *h, K kernel) {
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
+    return TOMO_PREP_OK;
+}
+
+int drain(tomo_prep *h) {
+    if (h->pending) {
+        HIPCHK(h, hipEventSynchronize(h->ev_done));
+        h->pending = false;
+    }
+    return TOMO_PREP_OK;
+}
+
+int ilog2_ceil(int n) {
+    int l = 0;
+    while ((1 << l) < n) ++l;
+    return l;
+}
+
+int chunk_for(int n_proj, int ndx, int ndz, size_t budget) {
+    if (budget == 0) return ndz;
+    const size_t per_z = (size_t)10 * (size_t)n_proj * (size_t)ndx;
+    size_t zc = budget / per_z;
+    if (zc >= (size_t)ndz) return ndz;
+    if (zc >= 64) zc -= zc % 64;               // whole 64-wide tiles for the median pass
+    return zc < 1 ? 1 : (int)zc;
+}
+
+template <int W>
+int launch_median(tomo_prep *h, hipStream_t st, const float *S, float *M, int n, int ndx, int zw, int size) {
+    static bool attr = false;
+    if (!attr) {
+        int rc = allow_lds(h, k_stripe_median<W>);
+        if (rc) return rc;
+        attr = true;
+    }
+    const size_t lds = (size_t)(MED_TX + size - 1) * MED_TZ * sizeof(float);
+    dim3 grid((unsigned)((zw + MED_TZ - 1) / MED_TZ), (unsigned)((ndx + MED_TX - 1) / MED_TX), (unsigned)n);
+    hipLaunchKernelGGL(k_stripe_median<W>, grid, dim3(MED_T), lds, st, S, M, ndx, zw, size);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+int median(tomo_prep *h, hipStream_t st, const float *S, float *M, int n, int ndx, int zw, int size) {
+    if (size <= 3) return launch_median<3>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 7) return launch_median<7>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 11) return launch_median<11>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 15) return launch_median<15>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 21) return launch_median<21>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 31) return launch_median<31>(h, st, S, M, n, ndx, zw, size);
+    if (size <= 41) return launch_median<41>(h, st, S, M, n, ndx, zw, size);
+    return launch_median<63>(h, st, S, M, n, ndx, zw, size);
+}
+
+template <typename T>
+int reference_t(tomo_prep *h, hipStream_t st, const T *in, int n, size_t npix, int method, float *out) {
+    const unsigned blocks = (unsigned)((npix + REF_T - 1) / REF_T);
+    if (method == TOMO_PREP_MEAN) {
+        hipLaunchKernelGGL(k_reference_mean<T>, dim3(blocks), dim3(REF_T), 0, st, in, out, n, npix);
+    } else {
+        static bool attr = false;
+        if (!attr) {
+            int rc = allow_lds(h, k_reference_median<T>);
+            if (rc) return rc;
+            attr = true;
+        }
+        hipLaunchKernelGGL(k_reference_median<T>, dim3(blocks), dim3(REF_T), (size_t)n * REF_T * sizeof(uint32_t), st, in, out, n, npix);
+    }
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TOMO_API int tomo_prep_abi_version(void) { return 1; }
+
+TOMO_API int tomo_prep_create(int device, tomo_prep **out) {
+    if (!out) return fail(nullptr, TOMO_PREP_ERR_ARG, "NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_PREP_ERR_NODEV, "no HIP device");
+    if (device < 0 || device >= n) return fail(nullptr, TOMO_PREP_ERR_ARG, "device out of range");
+    tomo_prep *h = new tomo_prep();
+    h->device = device;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev_pass[i]);
+    if (e != hipSuccess) {
+        tomo_prep_destroy(h);
+        return fail(nullptr, TOMO_PREP_ERR_HIP, std::string("event creation: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_destroy(tomo_prep *h) {
+    if (!h) return TOMO_PREP_OK;
+    (void)hipSetDevice(h->device);
+    if (h->pending) (void)hipEventSynchronize(h->ev_done);
+    if (h->d_scratch) (void)hipFree(h->d_scratch);
+    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    for (hipEvent_t ev : h->ev_pass)
+        if (ev) (void)hipEventDestroy(ev);
+    delete h;
+    return TOMO_PREP_OK;
+}
+
+TOMO_API const char *tomo_prep_last_error(tomo_prep *h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+TOMO_API int tomo_prep_reference(tomo_prep *h, void *stream, const void *d_frames, int dtype, int n, int rows, int cols, int method,
+                                 float *d_out) {
+    if (!h) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: NULL handle");
+    if (n < 1 || rows < 1 || cols < 1) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: bad shape");
+    if (dtype != TOMO_PREP_U16 && dtype != TOMO_PREP_F32) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: dtype must be uint16 or float32");
+    if (method != TOMO_PREP_MEAN && method != TOMO_PREP_MEDIAN) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: unknown method");
+    if (method == TOMO_PREP_MEDIAN && n > TOMO_PREP_MAX_MEDIAN_FRAMES)
+        return fail(h, TOMO_PREP_ERR_UNSUPPORTED, "tomo_prep_reference: median over " + std::to_string(n) + " > 64 frames");
+    if (!d_frames || !d_out) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: NULL pointer");
+    const size_t npix = (size_t)rows * (size_t)cols;
+    if ((npix + REF_T - 1) / REF_T >= (1ull << 31)) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_reference: frame too large");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == TOMO_PREP_U16) return reference_t(h, st, static_cast<const uint16_t *>(d_frames), n, npix, method, d_out);
+    return reference_t(h, st, static_cast<const float *>(d_frames), n, npix, method, d_out);
+}
+
+TOMO_API int tomo_prep_normalize(tomo_prep *h, void *stream, const void *d_raw, int dtype, int n, int rows, int cols, const float *d_flat,
+                                 const float *d_dark, int z0, int z1, int x0, int x1, int use_cutoff, float cutoff, int minus_log,
+                                 float min_ratio, float *d_out) {
+    if (!h) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: NULL handle");
+    if (n < 0 || rows < 1 || cols < 1) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: bad shape");
+    if (dtype != TOMO_PREP_U16 && dtype != TOMO_PREP_F32) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: dtype must be uint16 or float32");
+    if (z0 < 0 || z1 > rows || z0 >= z1 || x0 < 0 || x1 > cols || x0 >= x1)
+        return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: crop window outside the frame or empty");
+    if (n == 0) return TOMO_PREP_OK;
+    if (!d_raw || !d_flat || !d_dark || !d_out) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: NULL pointer");
+    const int nz = z1 - z0, nx = x1 - x0;
+    const int tiles_z = (nz + NORM_TILE - 1) / NORM_TILE, tiles_x = (nx + NORM_TILE - 1) / NORM_TILE;
+    const int groups = (n + NORM_FR - 1) / NORM_FR;
+    if ((long long)tiles_z * tiles_x * groups >= (1LL << 31)) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_normalize: too many work-groups");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(tiles_z * tiles_x * groups));
+    if (dtype == TOMO_PREP_U16)
+        hipLaunchKernelGGL(k_normalize<uint16_t>, grid, dim3(NORM_T), 0, st, static_cast<const uint16_t *>(d_raw), d_flat, d_dark, d_out, n,
+                           rows, cols, z0, x0, nz, nx, tiles_z, tiles_x, use_cutoff, cutoff, minus_log, min_ratio);
+    else
+        hipLaunchKernelGGL(k_normalize<float>, grid, dim3(NORM_T), 0, st, static_cast<const float *>(d_raw), d_flat, d_dark, d_out, n,
+                           rows, cols, z0, x0, nz, nx, tiles_z, tiles_x, use_cutoff, cutoff, minus_log, min_ratio);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_stripe_chunk(int n_proj, int ndx, int ndz, size_t max_scratch_bytes, int *chunk_z) {
+    if (!chunk_z || n_proj < 1 || ndx < 1 || ndz < 1) return fail(nullptr, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_chunk: bad args");
+    *chunk_z = chunk_for(n_proj, ndx, ndz, max_scratch_bytes);
+    return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_stripe_sorting(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, int size,
+                                      size_t max_scratch_bytes, float *pass_ms) {
+    if (!h) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_sorting: NULL handle");
+    if (n_proj > TOMO_PREP_MAX_NPROJ)
+        return fail(h, TOMO_PREP_ERR_UNSUPPORTED, "tomo_prep_stripe_sorting: n_proj " + std::to_string(n_proj) + " > " +
+                                                      std::to_string(TOMO_PREP_MAX_NPROJ) + " (one 64-bit key per angle in LDS); nothing was written");
+    if (n_proj < 1 || ndx < 1 || ndz < 1) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_sorting: bad shape");
+    if (size < 3 || size % 2 == 0 || size > TOMO_PREP_MAX_STRIPE_SIZE || size > ndx)
+        return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_sorting: size must be odd with 3 <= size <= min(ndx, 63)");
+    if (!d_in || !d_out) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_sorting: NULL pointer");
+    if ((long long)n_proj * ndx >= (1LL << 31) / 10 || ndz > 65535)
+        return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_sorting: shape too large (n_proj * ndx < 2^31 / 10, ndz <= 65535)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int zc = chunk_for(n_proj, ndx, ndz, max_scratch_bytes);
+    const size_t nchunk = (size_t)n_proj * ndx * zc;
+    const size_t need = nchunk * 10;
+    if (h->pending && (need > h->scratch_cap || st != h->last_stream)) {     // the scratch is replaced or used on another stream
+        int rc = drain(h);
+        if (rc) return rc;
+    }
+    if (need > h->scratch_cap) {
+        if (h->d_scratch) HIPCHK(h, hipFree(h->d_scratch));
+        h->d_scratch = nullptr;
+        h->scratch_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_scratch, need));
+        h->scratch_cap = need;
+    }
+    static bool attr = false;
+    if (!attr) {
+        int rc = allow_lds(h, k_stripe_sort);
+        if (!rc) rc = allow_lds(h, k_stripe_scatter);
+        if (rc) return rc;
+        attr = true;
+    }
+    float *S = static_cast<float *>(h->d_scratch);
+    float *M = S + nchunk;
+    uint16_t *P = reinterpret_cast<uint16_t *>(M + nchunk);
+    const int logNp = ilog2_ceil(n_proj), Np = 1 << logNp;
+    const int zc1 = std::min(MAX_ZC, std::max(1, SORT_KEYS / Np));
+    const int zc3 = std::min(MAX_ZC, std::max(1, SCATTER_VALS / n_proj));
+    const size_t lds1 = (size_t)zc1 * (Np + 1) * sizeof(uint64_t), lds3 = (size_t)zc3 * (n_proj + 1) * sizeof(float);
+    if (pass_ms) pass_ms[0] = pass_ms[1] = pass_ms[2] = 0.f;
+    for (int zb = 0; zb < ndz; zb += zc) {
+        const int zw = std::min(zc, ndz - zb);
+        if (pass_ms) HIPCHK(h, hipEventRecord(h->ev_pass[0], st));
+        hipLaunchKernelGGL(k_stripe_sort, dim3((unsigned)ndx, (unsigned)((zw + zc1 - 1) / zc1)), dim3(SORT_T), lds1, st, d_in, S, P, n_proj,
+                           ndx, ndz, zb, zw, logNp, zc1);
+        HIPCHK(h, hipGetLastError());
+        if (pass_ms) HIPCHK(h, hipEventRecord(h->ev_pass[1], st));
+        int rc = median(h, st, S, M, n_proj, ndx, zw, size);
+        if (rc) return rc;
+        if (pass_ms) HIPCHK(h, hipEventRecord(h->ev_pass[2], st));
+        hipLaunchKernelGGL(k_stripe_scatter, dim3((unsigned)ndx, (unsigned)((zw + zc3 - 1) / zc3)), dim3(SCATTER_T), lds3, st, M, P, d_out,
+                           n_proj, ndx, ndz, zb, zw, zc3);
+        HIPCHK(h, hipGetLastError());
+        if (pass_ms) {
+            HIPCHK(h, hipEventRecord(h->ev_pass[3], st));
+            HIPCHK(h, hipEventSynchronize(h->ev_pass[3]));
+            for (int p = 0; p < 3; ++p) {
+                float ms = 0.f;
+                HIPCHK(h, hipEventElapsedTime(&ms, h->ev_pass[p], h->ev_pass[p + 1]));
+                pass_ms[p] += ms;
+            }
+        }
+    }
+    HIPCHK(h, hipEventRecord(h->ev_done, st));
+    h->pending = true;
+    h->last_stream = st;
+    return TOMO_PREP_OK;
+}
+
+}  // extern "C"

@@ -6,7 +6,13 @@ the projections computed by the GPU forward projector and, unlike the reference 
 (.npz with the key names of the HDF5 layout examples/align_rigid.py:11-17 reads: projections, alpha, beta, xyz, phi,
 phantom).
 
+With raw=True (--raw) the file also holds what a detector gives for the same projections, for examples/preprocess.py: `counts`
+(uint16 [n_proj][z][x]), `flats` and `darks` (uint16 stacks of frames) and `mu`, the attenuation per unit of `projections` (the line
+integral the counts encode is mu * projections).  counts = Poisson(I0 * gain * exp(-mu p)) + dark, with a per-pixel gain shared by flats
+and projections, and a few detector columns whose gain in the projections differs from the flats' by a few percent: the stripes.
+
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --out data.npz
+    python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --out raw.npz
 """
 import argparse
 
@@ -15,7 +21,30 @@ import numpy as np
 from ..utilities import generate_phantom, geometry, projection_operators
 
 
-def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0):
+def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03):
+    """Detector frames of the projections proj [n_proj][nx][nz]: dict(counts, flats, darks, mu) (module docstring).  mu defaults to
+    4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor."""
+    rng = np.random.default_rng(seed)
+    n_proj, nx, nz = proj.shape
+    mu = 4.0 / nx if mu is None else float(mu)
+    gain = 1.0 + 0.02 * rng.standard_normal((nz, nx))                    # fixed pattern: flats and projections share it
+    n_stripes = max(2, nx // 16) if n_stripes is None else int(n_stripes)
+    cols = rng.choice(nx, size=min(n_stripes, nx), replace=False)
+    drift = np.ones(nx)
+    drift[cols] += stripe_gain * rng.choice([-1.0, 1.0], size=cols.size) * rng.uniform(0.5, 1.0, size=cols.size)
+    dark_mean = dark_level + 2.0 * rng.standard_normal((nz, nx))
+
+    def frames(mean):
+        return np.clip(rng.poisson(mean) + np.rint(dark_mean), 0, 65535).astype(np.uint16)
+
+    att = np.exp(-mu * np.asarray(proj, np.float64)).transpose(0, 2, 1)   # [n][z][x]
+    counts = frames(i0 * gain * drift * att)
+    flats = frames(np.broadcast_to(i0 * gain, (n_flat, nz, nx)))
+    darks = np.clip(rng.poisson(np.broadcast_to(np.maximum(dark_mean, 0), (n_dark, nz, nx))), 0, 65535).astype(np.uint16)
+    return dict(counts=counts, flats=flats, darks=darks, mu=np.float64(mu))
+
+
+def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False):
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
     shepp = generate_phantom.shepp3d(nx)
@@ -31,7 +60,10 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0):
     proj_obj = projection_operators.ProjectionMatrix(geom, precision=np.float32)
     pmat = proj_obj.projection_matrix(alpha=alpha, beta=beta, phi=phi, xyz_shift=xyz)
     proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
-    return dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
+    d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
+    if raw:
+        d.update(make_raw(proj, seed=None if seed is None else seed + 1))   # a generator of its own: the other keys do not change
+    return d
 
 
 def main():
@@ -40,8 +72,9 @@ def main():
     ap.add_argument("--angles", type=int, default=90)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="data.npz")
+    ap.add_argument("--raw", action="store_true", help="also write detector counts, flats and darks (examples/preprocess.py)")
     a = ap.parse_args()
-    d = make(a.size, a.angles, a.seed)
+    d = make(a.size, a.angles, a.seed, raw=a.raw)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""
+Raw detector frames to the projections examples/align_rigid.py reads: flat-field normalisation, -log and sorting-based stripe removal
+on the GPU (tomography_alignment_amd.preprocess).  The input is a file with `counts` ([n_proj][z][x], uint16 or float32), `flats` and
+`darks` (stacks of frames in the same layout), such as `generate_data --raw` writes; an optional `mu` (the attenuation per unit of
+projection) divides the line integrals back into the phantom's units.  Every other key (phi, alpha, beta, xyz, phantom, ...) is carried
+through; counts, flats and darks are dropped.
+
+The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
+on the full stack on one GPU (it needs every angle of a column).
+
+    python -m tomography_alignment_amd.examples.generate_data --raw --out raw.npz
+    python -m tomography_alignment_amd.examples.preprocess raw.npz --out data.npz
+    python -m tomography_alignment_amd.examples.align_rigid data.npz --init fbp
+"""
+import argparse
+
+import numpy as np
+
+from .. import _lib, preprocess
+
+RAW_KEYS = ("counts", "flats", "darks", "mu")
+
+
+def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False):
+    """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
+    removal, or 0 / None to skip it."""
+    for k in ("counts", "flats", "darks"):
+        if k not in data:
+            raise ValueError("preprocess: the data has no %r (write it with generate_data --raw)" % k)
+    counts = np.asarray(data["counts"])
+    own = ctx is None
+    ctx = _lib.Context() if own else ctx
+    p = preprocess.Preprocessor(ctx)
+    d_frames = sino = None
+    try:
+        d_frames = ctx.to_device(counts, counts.dtype if counts.dtype in (np.uint16, np.float32) else np.float32)     # uploaded once
+        sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop)
+        d_frames.free()
+        if stripe_size:
+            p.remove_stripe_sorting(sino, size=stripe_size, out=sino)                                    # in place, on the device
+        proj = sino.download()
+    finally:
+        for d in (d_frames, sino):
+            if d is not None:
+                d.free()
+        p.close()
+        if own:
+            ctx.close()
+    if "mu" in data:
+        proj = (proj / np.float32(data["mu"])).astype(np.float32)
+    out = {k: v for k, v in data.items() if k not in RAW_KEYS}
+    out["projections"] = proj
+    if verbose:
+        print("preprocess: %s counts -> projections %s (stripe window %s)" % (counts.shape, proj.shape, stripe_size or "off"))
+    return out
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="raw detector frames -> projections for align_rigid")
+    ap.add_argument("data", help=".npz with counts, flats, darks (generate_data --raw)")
+    ap.add_argument("--out", default="data.npz")
+    ap.add_argument("--stripe-size", type=int, default=21, help="odd window of the stripe removal; 0 skips it")
+    ap.add_argument("--method", choices=("mean", "median"), default="mean", help="how flats and darks are reduced")
+    ap.add_argument("--cutoff", type=float, default=None, help="upper bound of the flat-field ratio before the log")
+    ap.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Z0", "Z1", "X0", "X1"), help="detector window")
+    a = ap.parse_args(argv)
+    if a.stripe_size and (a.stripe_size < 3 or a.stripe_size % 2 == 0):
+        ap.error("--stripe-size must be 0 or an odd number >= 3")
+    if a.crop is not None:
+        a.crop = ((a.crop[0], a.crop[1]), (a.crop[2], a.crop[3]))
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True)
+    np.savez(a.out, **d)
+    print("wrote %s" % a.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,275 @@
+"""
+Preprocessing of raw projections on the GPU (libtomo_prep.so, include/tomo_prep.h): reference frames, flat-field normalisation with the
+transpose into the package's sinogram layout, and sorting-based stripe removal.  The first step of the pipeline
+
+    raw counts --normalize--> sinogram --remove_stripe_sorting--> align.align_cc / recon.fbp / examples.align_rigid
+
+Layouts.  Raw frames, flats and darks are [n][rows = z][cols = x] (x fastest), uint16 or float32, uploaded in their own dtype.  The
+sinogram is float32 p[n_proj][nx][nz] with z, the rotation axis, fastest -- what FBP, SIRT and OuterLoop read (OuterLoop takes the
+device buffer as it is, with projections_shape).
+
+Reference frames (reference_frames): each of the flat and dark stacks becomes one float32 frame.
+    mean     float32(sum_j double(f_j) / n): the float64 sum runs in frame order, with no atomics, so the result is deterministic.
+    median   n <= 64: exact selection per pixel; for an even n, float32(0.5 * (double(a) + double(b))) of the two middle values.
+
+Normalisation (normalize), per pixel of the crop window z0:z1, x0:x1 (default the whole frame), all in float32 in this order:
+    den = flat - dark;  den = den < 1e-6 ? 1e-6 : den
+    r   = (float(raw) - dark) / den            IEEE division (the library is built without fast-math reciprocals)
+    r   = fmin(r, cutoff)                      if a cutoff is given
+    out = -log(fmax(r, min_ratio))             if minus_log (the default); else r
+min_ratio (default 1e-6) keeps the output finite for zero, below-dark and dead-pixel counts: -log(1e-6) = 13.8.  The frame is written
+transposed, out[i][x - x0][z - z0], through LDS tiles, so frame rows and sinogram rows are both read and written coalesced.
+
+Stripe removal (remove_stripe_sorting): Vo, Atwood & Drakopoulos, Opt. Express 26 (2018), algorithm 3.  For every detector row z:
+    1. sort each column (x, z) along the angle axis;
+    2. median-filter the sorted array along x, at equal rank, with an odd window `size` and scipy.ndimage's mode='reflect'
+       (half-sample symmetric: d c b a | a b c d | d c b a);
+    3. put every filtered value back at the angle it came from.
+The order is defined exactly, so the GPU matches a numpy model bit for bit:
+    - the sort key is (orderable bits of v, angle index): every key is unique, and the order is numpy's argsort(kind='stable');
+    - -0.0 is canonicalised to +0.0 before the key is built.  -log(1.0f) is -0.0f, so air pixels produce it; kept apart from +0.0 the two
+      zeros would order differently from numpy's comparison, and the tie order decides which angle receives which filtered value;
+    - every NaN maps to one key above +inf;
+    - the median is an exact selection: the output is always one of the window's input values.
+Limits: n_proj <= 8192 (one 64-bit key per angle in LDS; more raises PrepUnsupported before any launch), size odd with
+3 <= size <= min(nx, 63).  z is processed in chunks whose scratch (10 bytes per sinogram value: sorted values, filtered values, uint16
+permutation) fits max_scratch_bytes (default 2 GiB); the result does not depend on the chunking.  The removal needs every angle of a
+column, so it runs on the full stack on one GPU; ranks that each hold a block of angles can still call normalize on their own frames.
+
+The kernels live in their own library, like libtomo_fbp.so and libtomo_xcorr.so, so that the projector's sources and the kernel-source
+hash that keys the committed PMC counters do not change.  Host arrays and _lib.DeviceArrays are both accepted; a device input gives a
+device output, with no host round trip, and every temporary buffer is freed before a call returns.  Arguments are checked (ValueError)
+before anything is uploaded or launched.
+"""
+import numpy as np
+
+from . import _lib, _prep_lib
+from ._prep_lib import PrepUnsupported  # noqa: F401  (re-exported)
+
+DEFAULT_SCRATCH_BYTES = 2 << 30
+METHODS = {"mean": _prep_lib.MEAN, "median": _prep_lib.MEDIAN}
+_DTYPES = {np.dtype(np.uint16): _prep_lib.U16, np.dtype(np.float32): _prep_lib.F32}
+
+
+def _is_dev(a):
+    return isinstance(a, _lib.DeviceArray)
+
+
+def _shape_dtype(a, what, ndims):
+    shape = tuple(a.shape) if _is_dev(a) else np.shape(a)
+    dtype = a.dtype if _is_dev(a) else np.asarray(a).dtype
+    if len(shape) not in ndims:
+        raise ValueError("%s must have %s dimensions, got shape %s" % (what, " or ".join(str(d) for d in ndims), shape))
+    if np.dtype(dtype) not in _DTYPES:
+        raise ValueError("%s must be uint16 or float32, got %s" % (what, dtype))
+    if any(s < 1 for s in shape):
+        raise ValueError("%s must not be empty, got shape %s" % (what, shape))
+    return shape, np.dtype(dtype)
+
+
+def _crop(crop, rows, cols):
+    if crop is None:
+        return (0, rows), (0, cols)
+    try:
+        cz, cx = crop
+    except (TypeError, ValueError):
+        raise ValueError("crop must be ((z0, z1), (x0, x1)) or (slice, slice)")
+    out = []
+    for c, n, name in ((cz, rows, "z"), (cx, cols, "x")):
+        if isinstance(c, slice):
+            if c.step not in (None, 1):
+                raise ValueError("crop: slices must have step 1")
+            c = (0 if c.start is None else c.start, n if c.stop is None else c.stop)
+        a, b = (int(v) for v in c)
+        if not (0 <= a < b <= n):
+            raise ValueError("crop %s window %d:%d lies outside the frame (0:%d) or is empty" % (name, a, b, n))
+        out.append((a, b))
+    return tuple(out)
+
+
+class Preprocessor(object):
+    """One libtomo_prep handle and its scratch, reused across calls.  ctx: the _lib.Context whose device and stream the work uses (work
+    is enqueued on ctx.stream(), in order with the projector work that follows); default the context of the first DeviceArray passed in,
+    or a context of the handle's own.  Arguments are checked before the context or the handle is made."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+        self.handle = None
+        self._own_ctx = None
+
+    def _ready(self, like):
+        if self.ctx is None:
+            if _is_dev(like):
+                self.ctx = like.ctx
+            else:
+                self.ctx = self._own_ctx = _lib.Context()
+        if self.handle is None:
+            self.handle = _prep_lib.PrepHandle(self.ctx.device)
+
+    def close(self):
+        if self.handle is not None:
+            self.handle.close()
+            self.handle = None
+        if self._own_ctx is not None:
+            self._own_ctx.close()
+            self._own_ctx = self.ctx = None
+
+    def _upload(self, a, temps):
+        if _is_dev(a):
+            return a
+        a = np.ascontiguousarray(a)
+        d = self.ctx.to_device(a, a.dtype)
+        temps.append(d)
+        return d
+
+    @staticmethod
+    def _free(temps):
+        for t in temps:
+            t.free()
+        del temps[:]
+
+    def _reference(self, d, shape, dtype, method):
+        n = 1 if len(shape) == 2 else shape[0]
+        rows, cols = shape[-2:]
+        out = self.ctx.empty((rows, cols), np.float32)
+        try:
+            self.handle.reference(self.ctx.stream(), d.ptr, _DTYPES[dtype], n, rows, cols, METHODS[method], out.ptr)
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def _check_reference_args(self, stacks, method):
+        if method not in METHODS:
+            raise ValueError("method must be 'mean' or 'median', got %r" % (method,))
+        infos = []
+        for a, what in stacks:
+            shape, dtype = _shape_dtype(a, what, (2, 3))
+            n = 1 if len(shape) == 2 else shape[0]
+            if method == "median" and n > _prep_lib.MAX_MEDIAN_FRAMES:
+                raise PrepUnsupported("%s: the median supports at most %d frames, got %d" % (what, _prep_lib.MAX_MEDIAN_FRAMES, n))
+            infos.append((shape, dtype))
+        if infos[0][0][-2:] != infos[1][0][-2:]:
+            raise ValueError("flats and darks must have the same frame shape, got %s and %s" % (infos[0][0][-2:], infos[1][0][-2:]))
+        return infos
+
+    def reference_frames(self, flats, darks, method="mean"):
+        """(flat, dark): float32 [rows][cols] frames reduced from the stacks flats, darks ([n][rows][cols] or one [rows][cols] frame).
+        DeviceArrays when flats is one, ndarrays otherwise."""
+        infos = self._check_reference_args(((flats, "flats"), (darks, "darks")), method)
+        self._ready(flats)
+        temps, res = [], []
+        try:
+            for a, (shape, dtype) in zip((flats, darks), infos):
+                res.append(self._reference(self._upload(a, temps), shape, dtype, method))
+        except Exception:
+            self._free(res)
+            raise
+        finally:
+            self._free(temps)
+        if _is_dev(flats):
+            return tuple(res)
+        out = tuple(r.download() for r in res)
+        self._free(res)
+        return out
+
+    def normalize(self, frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6, method="mean", crop=None, out=None):
+        """The (n_proj, nx, nz) float32 sinogram of raw frames [n_proj][rows][cols] (module docstring): an ndarray for host frames, a
+        DeviceArray for device frames (`out`, a float32 DeviceArray of that shape, if given)."""
+        shape, dtype = _shape_dtype(frames, "frames", (3,))
+        n, rows, cols = shape
+        infos = self._check_reference_args(((flats, "flats"), (darks, "darks")), method)
+        if infos[0][0][-2:] != (rows, cols):
+            raise ValueError("flats and darks must have the frames' shape %s, got %s" % ((rows, cols), infos[0][0][-2:]))
+        (z0, z1), (x0, x1) = _crop(crop, rows, cols)
+        if not (np.isfinite(min_ratio) and min_ratio > 0):
+            raise ValueError("min_ratio must be finite and > 0, got %r" % (min_ratio,))
+        if cutoff is not None and not np.isfinite(cutoff):
+            raise ValueError("cutoff must be finite or None, got %r" % (cutoff,))
+        oshape = (n, x1 - x0, z1 - z0)
+        if out is not None and not (_is_dev(out) and out.dtype == np.float32 and out.size == int(np.prod(oshape))):
+            raise ValueError("out must be a float32 DeviceArray of %d values %s" % (int(np.prod(oshape)), oshape))
+        self._ready(frames)
+        temps = []
+        try:
+            d_raw = self._upload(frames, temps)
+            d_flat, d_dark = (self._reference(self._upload(a, temps), s, dt, method) for a, (s, dt) in zip((flats, darks), infos))
+            temps += [d_flat, d_dark]
+            res = out if out is not None else self.ctx.empty(oshape, np.float32)
+            if out is None and not _is_dev(frames):
+                temps.append(res)
+            self.handle.normalize(self.ctx.stream(), d_raw.ptr, _DTYPES[dtype], n, rows, cols, d_flat.ptr, d_dark.ptr,
+                                  ((z0, z1), (x0, x1)), cutoff, minus_log, min_ratio, res.ptr)
+            return res if _is_dev(frames) else res.download()
+        finally:
+            self._free(temps)
+
+    def remove_stripe_sorting(self, proj, size=21, out=None, max_scratch_bytes=None, timed=False):
+        """Stripe removal of the sinogram proj [n_proj][nx][nz] (float32; module docstring).  Host in: an ndarray out.  Device in: the
+        result goes to `out` (a float32 DeviceArray of the same size; `out=proj` works in place) or a new DeviceArray.
+        timed=True (benchmarks): returns (result, (sort_ms, median_ms, scatter_ms)) after a synchronisation."""
+        shape, dtype = _shape_dtype(proj, "proj", (3,))
+        if dtype != np.float32:
+            raise ValueError("proj must be float32, got %s" % dtype)
+        n, nx, nz = shape
+        if isinstance(size, (bool, np.bool_)) or int(size) != size:
+            raise ValueError("size must be an odd integer, got %r" % (size,))
+        size = int(size)
+        if size % 2 == 0 or size < 3 or size > min(nx, _prep_lib.MAX_STRIPE_SIZE):
+            raise ValueError("size must be odd with 3 <= size <= min(nx, 63) = %d, got %d" % (min(nx, _prep_lib.MAX_STRIPE_SIZE), size))
+        budget = DEFAULT_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+        if budget < 0:
+            raise ValueError("max_scratch_bytes must be >= 0 (0: no limit)")
+        if out is not None:
+            if not (_is_dev(out) and out.dtype == np.float32 and out.size == n * nx * nz):
+                raise ValueError("out must be a float32 DeviceArray of %d values" % (n * nx * nz))
+            if _is_dev(proj) and out.ptr.value != proj.ptr.value:
+                a0, b0 = proj.ptr.value, out.ptr.value
+                if a0 < b0 + out.nbytes and b0 < a0 + proj.nbytes:
+                    raise ValueError("out must be proj itself or not overlap it")
+        self._ready(proj)
+        temps = []
+        try:
+            d_in = self._upload(proj, temps)
+            res = out
+            if res is None:
+                res = self.ctx.empty(shape, np.float32)
+                if not _is_dev(proj):
+                    temps.append(res)
+            try:
+                ms = self.handle.stripe_sorting(self.ctx.stream(), d_in.ptr, res.ptr, n, nx, nz, size, budget, timed)
+            except Exception:
+                if out is None:
+                    res.free()
+                raise
+            result = res if _is_dev(proj) else res.download()
+        finally:
+            self._free(temps)
+        return (result, ms) if timed else result
+
+
+def reference_frames(flats, darks, method="mean", ctx=None):
+    """(flat, dark) float32 reference frames: Preprocessor.reference_frames on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.reference_frames(flats, darks, method)
+    finally:
+        p.close()
+
+
+def normalize(frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6, method="mean", crop=None, ctx=None, out=None):
+    """The (n_proj, nx, nz) sinogram of raw frames: Preprocessor.normalize on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.normalize(frames, flats, darks, cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, method=method, crop=crop, out=out)
+    finally:
+        p.close()
+
+
+def remove_stripe_sorting(proj, size=21, ctx=None, out=None, max_scratch_bytes=None):
+    """Sorting-based stripe removal: Preprocessor.remove_stripe_sorting on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.remove_stripe_sorting(proj, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
+    finally:
+        p.close()
