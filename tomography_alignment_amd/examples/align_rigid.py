@@ -13,7 +13,13 @@ per iteration over xGMI) and aligns its own projections against the replicated r
 inside the optimiser; the recovered pose table is summed once per outer iteration.  The reconstruction is warm-started
 from the previous outer iteration's (examples/align_rigid.py:42) where it lies, in HBM.
 
+Coarse to fine (run_multires, --levels): the first outer iterations run on data binned by 2^(levels-1), ..., 2 (multires.py: the
+binning and prolongation kernels of libtomo_pyr.so), each level a unit-pitch geometry of its own; the poses (translations times 2, tilts
+as they are) and the prolonged reconstruction are handed up, and only the last iterations run at full size.  The bounds of the optimiser
+are in pixels of the level, so the same +-3 px reach +-12 full-size pixels at a level binned by 4.
+
     python -m tomography_alignment_amd.examples.align_rigid data.npz --outer 5 --sirt-iters 50
+    python -m tomography_alignment_amd.examples.align_rigid data.npz --levels 3 --outer 3 --sirt-iters 50
     python -m torch.distributed.run --nproc-per-node 8 -m tomography_alignment_amd.examples.align_rigid data.npz
 """
 import argparse
@@ -21,7 +27,7 @@ import time
 
 import numpy as np
 
-from .. import alignment
+from .. import alignment, multires
 from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
 
@@ -36,9 +42,14 @@ class OuterLoop(object):
     data: dict with `projections` (n_proj, nx, nz) and `phi`; optional `phantom` (ground truth -> RMSE per outer iteration) and
     `xyz`, `alpha`, `beta` (true poses -> pose errors in the history).  `projections` may be a DEVICE buffer that already holds this
     rank's rows (then `projections_shape` = (n_proj, nx, nz) says what it is a block of), `phantom` a device buffer too.
-    comm     None: one GPU.  A communicator: angle-sharded over its ranks (module docstring); every rank holds the same poses."""
+    comm     None: one GPU.  A communicator: angle-sharded over its ranks (module docstring); every rank holds the same poses.
+    base     None, or (xyz0 (n_proj, 3), alpha0, beta0): a fixed pose the estimates start from and every alignment pass searches an
+             INCREMENT around (from a zero start, inside the bounds); the estimate is base + increment (run_multires: the coarser level's).
+    d_rec    None, or a device buffer that is the warm start of the first SIRT (it is updated in place).
+    factor   the binning factor of the level `data` belongs to: `xyz` of the true poses is in full-size pixels, and pose_errors reports
+             in full-size pixels."""
 
-    def __init__(self, data, backend=None, comm=None, kernel_names=None):
+    def __init__(self, data, backend=None, comm=None, kernel_names=None, base=None, d_rec=None, factor=1):
         self.comm = comm
         self.size = 1 if comm is None else (comm.Get_size() if hasattr(comm, "Get_size") else comm.size)
         self.rank = 0 if comm is None else (comm.Get_rank() if hasattr(comm, "Get_rank") else comm.rank)
@@ -71,7 +82,17 @@ class OuterLoop(object):
         if ground_truth is not None:
             self.d_gt = ground_truth if be.is_buffer(ground_truth) else be.upload(np.asarray(ground_truth, np.float32).ravel())
         self.alpha_rec, self.beta_rec, self.xyz_rec = np.zeros(n_proj), np.zeros(n_proj), np.zeros((n_proj, 3))
-        self.d_rec, self.solver = None, None
+        self.base = None
+        if base is not None:
+            xyz0, alpha0, beta0 = (np.array(v, np.float64) for v in base)
+            if xyz0.shape != (n_proj, 3) or alpha0.shape != (n_proj,) or beta0.shape != (n_proj,):
+                raise ValueError("align_rigid: base must be (xyz0 (n_proj, 3), alpha0 (n_proj,), beta0 (n_proj,))")
+            self.base = (xyz0, alpha0, beta0)
+            self.xyz_rec, self.alpha_rec, self.beta_rec = xyz0.copy(), alpha0.copy(), beta0.copy()
+        self.factor = int(factor)
+        if d_rec is not None and d_rec.size != nx * ny * nz:
+            raise ValueError("align_rigid: the initial reconstruction must hold the %d voxels of the volume" % (nx * ny * nz))
+        self.d_rec, self.solver = d_rec, None
 
     def reconstruct(self, sirt_iters=50, positivity=True, init="zero"):
         """SIRT at the current pose estimates, warm-started from the previous reconstruction where it lies (examples/align_rigid.py:37-39,42).
@@ -107,6 +128,8 @@ class OuterLoop(object):
         """One alignment pass: every projection's L-BFGS-B on cost_xzab / gradient_xzab from a zero start against self.d_rec
         (examples/align_rigid.py:40-52); sets the pose estimates, returns alignment.align_projections' result dict."""
         kw = dict(letters="xzab", bounds=bounds)
+        if self.base is not None:
+            kw.update(xyz0=self.base[0], angles0=np.column_stack([self.phi, self.base[1], self.base[2]]))
         kw.update(align_kwargs)
         if self.comm is None:
             res = alignment.align_projections(self.be, self.d_rec, self.d_b, self.phi, indices=self.mine, **kw)
@@ -115,13 +138,18 @@ class OuterLoop(object):
         self.xyz_rec = np.zeros((self.n_proj, 3))
         self.xyz_rec[:, 0], self.xyz_rec[:, 2] = res["x"][:, 0], res["x"][:, 1]
         self.alpha_rec, self.beta_rec = res["x"][:, 2].copy(), res["x"][:, 3].copy()
+        if self.base is not None:
+            self.xyz_rec += self.base[0]
+            self.alpha_rec += self.base[1]
+            self.beta_rec += self.base[2]
         return res
 
     def pose_errors(self):
         d = self.data
         if "xyz" not in d:
             return {}
-        return {"shift_err_px": float(np.abs(self.xyz_rec[:, [0, 2]] - np.asarray(d["xyz"])[:, [0, 2]]).mean()),
+        shifts = self.xyz_rec[:, [0, 2]] if self.factor == 1 else self.factor * self.xyz_rec[:, [0, 2]]
+        return {"shift_err_px": float(np.abs(shifts - np.asarray(d["xyz"])[:, [0, 2]]).mean()),
                 "tilt_err_deg": float(np.rad2deg(np.abs(np.column_stack([self.alpha_rec, self.beta_rec]) - np.column_stack([d["alpha"], d["beta"]])).mean()))}
 
     def download(self):
@@ -137,32 +165,154 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
     loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names)
-    ctx = loop.ctx
     history = []
     for it in range(n_outer):
-        k0 = _kernel_ms(ctx, kernel_names)
-        t0 = time.perf_counter()
-        k_done, err = loop.reconstruct(sirt_iters, init=init)
-        if ctx is not None:
-            ctx.sync()
-        t1 = time.perf_counter()
-        k1 = _kernel_ms(ctx, kernel_names)
-        res = loop.align(bounds, **(align_kwargs or {}))
-        t2 = time.perf_counter()
-        k2 = _kernel_ms(ctx, kernel_names)
-        entry = {"outer": it, "rmse": float(err[-1]), "sirt_iterations": int(k_done), "residual": float(res["fun"].sum()), "launches": res["n_launch"],
-                 "evals": res["n_eval"], "driver": res.get("driver"), "sirt_wall_s": round(t1 - t0, 3), "align_wall_s": round(t2 - t1, 3),
-                 "ranks": loop.size}
-        if kernel_names and ctx is not None:
-            entry["sirt_kernel_ms"] = {k: round(k1[k] - k0[k], 1) for k in k1 if k1[k] - k0[k] > 0}
-            entry["align_kernel_ms"] = {k: round(k2[k] - k1[k], 1) for k in k2 if k2[k] - k1[k] > 0}
-        entry.update(loop.pose_errors())
-        history.append(entry)
-        if verbose and loop.rank == 0:
-            print(entry)
+        history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose))
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
+
+
+def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, extra=None):
+    """One outer iteration of `loop` -- SIRT, then the alignment pass -- and its history entry (`extra`: more keys for it)."""
+    ctx = loop.ctx
+    k0 = _kernel_ms(ctx, kernel_names)
+    t0 = time.perf_counter()
+    k_done, err = loop.reconstruct(sirt_iters, init=init)
+    if ctx is not None:
+        ctx.sync()
+    t1 = time.perf_counter()
+    k1 = _kernel_ms(ctx, kernel_names)
+    res = loop.align(bounds, **(align_kwargs or {}))
+    t2 = time.perf_counter()
+    k2 = _kernel_ms(ctx, kernel_names)
+    entry = {"outer": it, "rmse": float(err[-1]), "sirt_iterations": int(k_done), "residual": float(res["fun"].sum()), "launches": res["n_launch"],
+             "evals": res["n_eval"], "driver": res.get("driver"), "sirt_wall_s": round(t1 - t0, 3), "align_wall_s": round(t2 - t1, 3),
+             "ranks": loop.size}
+    if kernel_names and ctx is not None:
+        entry["sirt_kernel_ms"] = {k: round(k1[k] - k0[k], 1) for k in k1 if k1[k] - k0[k] > 0}
+        entry["align_kernel_ms"] = {k: round(k2[k] - k1[k], 1) for k in k2 if k2[k] - k1[k] > 0}
+    entry.update(loop.pose_errors())
+    if extra:
+        entry.update(extra)
+    if verbose and loop.rank == 0:
+        print(entry)
+    return entry
+
+
+def _per_level(value, levels, name):
+    """`value` as one entry per level, coarsest first: a number is repeated, a sequence must have `levels` entries."""
+    if np.ndim(value) == 0:
+        return [int(value)] * levels
+    value = [int(v) for v in value]
+    if len(value) != levels:
+        raise ValueError("run_multires: %s needs one entry per level (%d), got %d" % (name, levels, len(value)))
+    return value
+
+
+def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, align_kwargs=None, comm=None,
+                 kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None):
+    """`run` coarse to fine (module docstring): levels binned by 2^(levels-1), ..., 2, 1, coarsest first.
+    n_outer, sirt_iters   one number, or one per level, coarsest first.
+    bounds                of the increment every pass searches around the pose carried up from the coarser level (zero at the coarsest),
+                          in pixels of the level.
+    init                  the start of the coarsest level's first SIRT; every finer level starts from the prolonged coarser reconstruction.
+    ctx                   the _lib.Context all levels share (default: the communicator's, or a new one).
+    backend_factory, pyramid   test seams: geometry -> backend (default a HipBackend on ctx per level), and the object with multires.Pyramid's
+                          three methods (default a Pyramid on ctx).
+    Per level: the data are bin_projections of this rank's FULL-SIZE rows and bin_volume of the full-size ground truth (never of the previous
+    level's); the level's OuterLoop runs on the unit-pitch geometry of the binned sizes (multires.level_geometry); its base pose is the
+    coarser level's estimate with the translations times 2 and the tilts as they are.  The loop carries no centre-of-rotation offset, so
+    there is none to rescale.  A finished level's buffers are freed before the next level allocates its own.
+    Returns what `run` returns; every history entry also carries `level` (0: the coarsest) and `factor`, and its shift error is in
+    full-size pixels.  levels=1 IS `run`."""
+    levels = int(levels)
+    if levels < 1 or 2 ** (levels - 1) > multires.FACTORS[-1]:
+        raise ValueError("run_multires: levels must be 1 ... %d, got %d" % (len(multires.FACTORS) + 1, levels))
+    n_outer, sirt_iters = _per_level(n_outer, levels, "n_outer"), _per_level(sirt_iters, levels, "sirt_iters")
+    if levels == 1:
+        out = run(data, n_outer[0], sirt_iters[0], bounds=bounds, verbose=verbose, align_kwargs=align_kwargs, comm=comm,
+                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init)
+        for entry in out[4]:
+            entry.update(level=0, factor=1)
+        return out
+    if init not in ("zero", "fbp"):
+        raise ValueError("align_rigid: init must be 'zero' or 'fbp', not %r" % (init,))
+    phi = np.asarray(data["phi"], np.float64)
+    n_proj = phi.size
+    proj = data["projections"]
+    on_device = "projections_shape" in data
+    _, nx, nz = (int(v) for v in (data["projections_shape"] if on_device else np.shape(proj)))
+    ground_truth = data["phantom"] if "phantom" in data else None
+    ny = int(data["ny"]) if "ny" in data else (ground_truth.shape[1] if getattr(ground_truth, "ndim", 0) == 3 else nx)
+    f_max = 2 ** (levels - 1)
+    for e in (nx, ny, nz):
+        if e % f_max:
+            raise ValueError("run_multires: %d levels need sizes divisible by %d, got %d x %d x %d" % (levels, f_max, nx, ny, nz))
+    size = 1 if comm is None else (comm.Get_size() if hasattr(comm, "Get_size") else comm.size)
+    rank = 0 if comm is None else (comm.Get_rank() if hasattr(comm, "Get_rank") else comm.rank)
+    mine = np.array_split(np.arange(n_proj), size)[rank]
+    if backend_factory is None:
+        from .. import _lib
+        from ..backend import HipBackend
+        if ctx is None:
+            ctx = getattr(comm, "ctx", None)
+        if ctx is None:
+            ctx = _lib.Context()
+        backend_factory = lambda g: HipBackend(g, ctx=ctx)      # noqa: E731
+    own_pyramid = pyramid is None
+    if own_pyramid:
+        pyramid = multires.Pyramid(ctx)
+    try:
+        poses = {k: data[k] for k in ("xyz", "alpha", "beta") if "xyz" in data}
+        be = backend_factory(sirt_mpi.SIRT._shard_geometry(multires.level_geometry(n_proj, (nx, ny, nz)), mine))
+        # this rank's full-size rows and the ground truth go to HBM once: every level's data are made from them there
+        d_b = proj if on_device else be.upload(np.asarray(proj, np.float32).reshape(n_proj, -1)[mine])
+        d_gt = None
+        if ground_truth is not None:
+            d_gt = ground_truth if be.is_buffer(ground_truth) else be.upload(np.asarray(ground_truth, np.float32).ravel())
+        history, carried, d_rec, loop = [], None, None, None
+        for level in range(levels):
+            f = 2 ** (levels - 1 - level)
+            shape = (nx // f, ny // f, nz // f)
+            if f == 1:
+                be_l, d_b_l, d_gt_l = be, d_b, d_gt
+            else:
+                be_l = backend_factory(sirt_mpi.SIRT._shard_geometry(multires.level_geometry(n_proj, (nx, ny, nz), f), mine))
+                # (a rank that owns no angle keeps a zero-row table, as in `run`)
+                d_b_l = pyramid.bin_projections(d_b, f, shape=(mine.size, nx, nz)) if mine.size else be_l.empty(0)
+                d_gt_l = pyramid.bin_volume(d_gt, f, shape=(nx, ny, nz)) if d_gt is not None else None
+            ldata = dict(poses, projections=d_b_l, projections_shape=(n_proj,) + shape[::2], phi=phi, ny=shape[1])
+            if d_gt_l is not None:
+                ldata["phantom"] = d_gt_l
+            loop = OuterLoop(ldata, backend=be_l, comm=comm, kernel_names=kernel_names, base=carried, d_rec=d_rec, factor=f)
+            for _ in range(n_outer[level]):
+                history.append(_outer_iteration(loop, len(history), sirt_iters[level], bounds, init if level == 0 else "zero", align_kwargs,
+                                                kernel_names, verbose, extra={"level": level, "factor": f}))
+            if f == 1:
+                break
+            # hand up, and free what this level held before the finer one allocates: the solver's buffers, the binned data, then -- once it is
+            # prolonged -- the coarse reconstruction
+            carried = (2.0 * loop.xyz_rec, loop.alpha_rec.copy(), loop.beta_rec.copy())
+            coarse, loop.solver, loop.d_rec, loop.d_b, loop.d_gt = loop.d_rec, None, None, None, None
+            _free(d_b_l, d_gt_l)
+            d_b_l = d_gt_l = ldata = None
+            d_rec = None
+            if coarse is not None:
+                d_rec = pyramid.prolong_volume(coarse, shape=shape)
+                _free(coarse)
+    finally:
+        if own_pyramid:
+            pyramid.close()
+    rec = loop.download() if (download and loop.d_rec is not None) else None
+    out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
+    return out + (loop,) if return_loop else out
+
+
+def _free(*bufs):
+    for b in bufs:
+        if b is not None and hasattr(b, "free"):
+            b.free()
 
 
 def _kernel_ms(ctx, names):
@@ -177,13 +327,18 @@ def main():
     ap.add_argument("--outer", type=int, default=5)
     ap.add_argument("--sirt-iters", type=int, default=50)
     ap.add_argument("--init", choices=("zero", "fbp"), default="zero", help="start of the first SIRT: zero or the FBP")
+    ap.add_argument("--levels", type=int, default=1, help="resolution levels, coarse to fine (run_multires); --outer and --sirt-iters "
+                    "then count per level.  1: the plain loop")
     a = ap.parse_args()
     import os
     comm = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:       # launched one process per GPU: python -m torch.distributed.run --nproc-per-node N -m ...
         from ..comm import RcclComm
         comm = RcclComm.from_env()
-    run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init)
+    if a.levels == 1:
+        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init)
+    else:
+        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init)
     if comm is not None:
         comm.close()
 
