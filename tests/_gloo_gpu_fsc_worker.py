@@ -1,0 +1,44 @@
+"""Worker of tests/test_gpu_resolution.py: one rank of resolution.half_set_fsc with the REAL HIP backend (every rank opens its own context
+on GPU 0) and tests/_gloo_gpu_worker.py's host-staged gloo communicator standing in for RCCL.  The rank computes the curve once from the
+host array of all projections and once from a device buffer that holds only its own np.array_split block, and writes both, and the raw
+table of the second, to <out>.rank<r>.npz."""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+
+def main(out_path):
+    import torch.distributed as dist
+    dist.init_process_group("gloo", init_method="env://")
+    from _gloo_gpu_worker import HostStagedComm
+    from tomography_alignment_amd import _lib, resolution
+    from tomography_alignment_amd.examples import generate_data
+    from tomography_alignment_amd.utilities.geometry import Geometry
+
+    ctx = _lib.Context(0)
+    comm = HostStagedComm(ctx)
+    d = generate_data.make(64, 90, seed=3)
+    n = d["phi"].size
+    geo = Geometry(n, np.array([64, 64, 64]), np.ones(3), np.array([64, 64]), np.ones(2))
+    angles = np.array([d["phi"], d["alpha"], d["beta"]]).T
+    proj = np.asarray(d["projections"], np.float32)
+    out = {}
+    c = resolution.half_set_fsc(geo, proj, angles, d["xyz"], comm=comm)
+    out.update(host_fsc=c.fsc, host_count=c.count, host_PA=c.PA)
+    mine = np.array_split(np.arange(n), comm.size)[comm.rank]
+    d_p = ctx.to_device(proj.reshape(n, -1)[mine].ravel())
+    c = resolution.half_set_fsc(geo, d_p, angles, d["xyz"], comm=comm)
+    out.update(device_fsc=c.fsc, device_count=c.count, device_PA=c.PA, table=np.array([c.C, c.PA, c.PB, c.count]), rows=mine)
+    np.savez(out_path + ".rank%d.npz" % comm.rank, **out)
+    dist.barrier()
+    ctx.close()
+    dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

@@ -1,0 +1,173 @@
+"""
+ctypes binding of libtomo_fsc.so (include/tomo_fsc.h): the masked, mean-free FFT input of a device volume or stack, its in-place hipFFT
+R2C transform, and the deterministic float64 shell / ring sums of two spectra -- the device operations of resolution.py.
+
+As with _lib, there is NO CPU fallback: if the library or a device is missing, every entry point raises.
+"""
+import ctypes
+import os
+import threading
+
+import numpy as np
+
+from ._lib import TomoError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("TOMO_FSC_LIB") or os.path.join(_HERE, "libtomo_fsc.so")   # override: development builds only
+
+_c_vp = ctypes.c_void_p
+_c_int = ctypes.c_int
+_c_double = ctypes.c_double
+_c_size = ctypes.c_size_t
+
+ERR_UNSUPPORTED = 4       # TOMO_FSC_ERR_UNSUPPORTED
+MAX_N = 2048              # TOMO_FSC_MAX_N
+MAX_PLANES = 65535        # TOMO_FSC_MAX_PLANES
+MASK_NONE, MASK_ARRAY, MASK_SPHERE = 0, 1, 2
+
+# every symbol include/tomo_fsc.h declares: name -> (restype, argtypes)
+SIGNATURES = {
+    "tomo_fsc_abi_version": (_c_int, []),
+    "tomo_fsc_create": (_c_int, [_c_int, ctypes.POINTER(_c_vp)]),
+    "tomo_fsc_destroy": (_c_int, [_c_vp]),
+    "tomo_fsc_last_error": (ctypes.c_char_p, [_c_vp]),
+    "tomo_fsc_n_shells": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int)]),
+    "tomo_fsc_set_shape": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "tomo_fsc_device_bytes": (_c_int, [_c_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "tomo_fsc_plan_seconds": (_c_int, [_c_vp, ctypes.POINTER(_c_double)]),
+    "tomo_fsc_prepare": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_double, _c_double, _c_int]),
+    "tomo_fsc_fft": (_c_int, [_c_vp, _c_vp, _c_int]),
+    "tomo_fsc_reduce": (_c_int, [_c_vp, _c_vp]),
+    "tomo_fsc_fetch": (_c_int, [_c_vp, _c_vp, _c_vp]),
+    "tomo_fsc_take_rows": (_c_int, [_c_vp, _c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp]),
+}
+
+_lib = None
+_lock = threading.Lock()
+
+
+class FscUnsupported(TomoError):
+    """A shape the library does not handle: an axis shorter than 2 or longer than MAX_N, more than MAX_PLANES planes."""
+
+
+def load():
+    """Load libtomo_fsc.so and bind every symbol; raises TomoError (never falls back) on failure."""
+    global _lib
+    with _lock:
+        if _lib is None:
+            if not os.path.exists(LIB_PATH):
+                raise TomoError("libtomo_fsc.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
+                                "`make -C tomography_alignment_amd/csrc/fsc`; there is no CPU fallback" % LIB_PATH)
+            try:
+                lib = ctypes.CDLL(LIB_PATH)
+            except OSError as e:
+                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
+            for name, (res, args) in SIGNATURES.items():
+                fn = getattr(lib, name)          # AttributeError if include/tomo_fsc.h and the .so disagree
+                fn.restype = res
+                fn.argtypes = args
+            if lib.tomo_fsc_abi_version() != 1:
+                raise TomoError("libtomo_fsc.so ABI version mismatch")
+            _lib = lib
+    return _lib
+
+
+def _raise(lib, rc, h):
+    msg = (lib.tomo_fsc_last_error(h) or b"").decode(errors="replace")
+    raise (FscUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_fsc error %d: %s" % (rc, msg))
+
+
+def n_shells(ndim, nb, nx, ny, nz):
+    """min(n) / 2 + 1 of a shape the library handles; FscUnsupported otherwise.  Needs no device."""
+    lib = load()
+    n = _c_int(0)
+    rc = lib.tomo_fsc_n_shells(int(ndim), int(nb), int(nx), int(ny), int(nz), ctypes.byref(n))
+    if rc != 0:
+        _raise(lib, rc, None)
+    return n.value
+
+
+class FscHandle(object):
+    """One tomo_fsc handle: a device, the hipFFT plans and spectrum buffers of the shapes it has seen, and the last error.  A context
+    manager.  device: the tomo context's (ctx.device) -- every call is enqueued on the stream it is given, in practice that context's,
+    and only fetch() synchronises."""
+
+    def __init__(self, device=0):
+        self._h = None
+        self.lib = load()
+        h = _c_vp()
+        self._check(self.lib.tomo_fsc_create(int(device), ctypes.byref(h)), None)
+        self._h = h
+        self.device = int(device)
+        self.shape = None
+
+    def _check(self, rc, h="self"):
+        if rc != 0:
+            _raise(self.lib, rc, self._h if h == "self" else h)
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise TomoError("fsc handle closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self.lib.tomo_fsc_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+    def set_shape(self, ndim, nb, nx, ny, nz):
+        """The shape of the calls that follow; returns the number of shells.  Raises FscUnsupported before anything is launched."""
+        shape = (int(ndim), int(nb), int(nx), int(ny), int(nz))
+        self._check(self.lib.tomo_fsc_set_shape(self.handle, *shape))
+        self.shape = shape
+        self.n_shells = n_shells(*shape)
+        return self.n_shells
+
+    def device_bytes(self):
+        n = ctypes.c_int64(0)
+        self._check(self.lib.tomo_fsc_device_bytes(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def plan_seconds(self):
+        s = _c_double(0.0)
+        self._check(self.lib.tomo_fsc_plan_seconds(self.handle, ctypes.byref(s)))
+        return s.value
+
+    def prepare(self, stream, slot, d_vol, mask=MASK_NONE, d_mask=None, radius=0.0, edge=0.0, subtract_mean=True):
+        self._check(self.lib.tomo_fsc_prepare(self.handle, _ptr(stream), int(slot), _ptr(d_vol), int(mask), _ptr(d_mask), float(radius),
+                                              float(edge), 1 if subtract_mean else 0))
+
+    def fft(self, stream, slot):
+        self._check(self.lib.tomo_fsc_fft(self.handle, _ptr(stream), int(slot)))
+
+    def reduce(self, stream):
+        self._check(self.lib.tomo_fsc_reduce(self.handle, _ptr(stream)))
+
+    def fetch(self, stream):
+        """The table of the last reduce(): float64 (nb, 4, n_shells) in the order C, PA, PB, n.  Waits for the stream."""
+        out = np.empty((self.shape[1], 4, self.n_shells), np.float64)
+        self._check(self.lib.tomo_fsc_fetch(self.handle, _ptr(stream), out.ctypes.data_as(_c_vp)))
+        return out
+
+    def take_rows(self, stream, d_src, row_elems, first, step, count, d_dst):
+        self._check(self.lib.tomo_fsc_take_rows(self.handle, _ptr(stream), _ptr(d_src), int(row_elems), int(first), int(step), int(count),
+                                                _ptr(d_dst)))
+
+
+def _ptr(p):
+    if isinstance(p, ctypes.c_void_p):
+        return p
+    return _c_vp(int(p)) if p else None

@@ -1,0 +1,553 @@
+// libtomo_fsc.so: Fourier shell / ring correlation of device-resident volumes and stacks (tomography_alignment_amd/resolution.py) on gfx950.
+// The transforms are hipFFT R2C plans, in place in padded buffers; everything else is the kernels below.
+//
+// k_mask_sums<DIM>   first stage of the mask-weighted mean: a fixed grid of SUM_G blocks per plane writes block partials of sum(m v)
+//                    and sum(m) in float64; the second stage is a fixed tree over those SUM_G partials inside k_prepare.
+// k_prepare<DIM>     one thread per voxel: float32((v - mean) m) into the padded FFT buffer.
+// k_shell<DIM>       the radial histogram.  Along a row of the half-spectrum (kx, ky fixed, kz = 0 .. nz/2) the shell index does not
+//                    decrease.  A work-group is ONE wave: it owns a contiguous range of rows (of one plane for DIM 2), walks each in
+//                    chunks of 64 kz -- lane l loads A and B at kz = c + l as float2, lane-contiguous -- and reduces every run of equal
+//                    shells within the chunk by a segmented shuffle reduction in a fixed tree (strides 1, 2, .. 32; a lane adds the
+//                    value `stride` lanes up if that lane has the same shell).  The first lane of a run then adds the run's four totals
+//                    to the work-group's accumulators in LDS, 4 (S) doubles; runs of one chunk have distinct shells, so no two lanes
+//                    touch one accumulator, and the chunks of a wave follow each other in program order.  The order of every addition is
+//                    thus fixed by the shape alone.  The work-group stores its table; the grid is a function of the shape only.
+// k_shell_final      adds the work-groups' tables in index order.  No atomics anywhere.
+#include <hip/hip_runtime.h>
+#include <hipfft/hipfft.h>
+
+#include <algorithm>
+#include <chrono>
+#include <map>
+#include <string>
+#include <tuple>
+#include <type_traits>
+
+#include "../../../include/tomo_fsc.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+constexpr int TPB = 256;             // threads per block of the streaming kernels
+constexpr int SUM_G = 256;           // blocks per plane of the first-stage sums (== TPB: the second stage is one partial per thread)
+constexpr int WAVE = 64;             // k_shell: one wave per work-group
+constexpr int SHELL_WGS = 2048;      // k_shell: at most this many work-groups (partial tables); a constant, so the sums do not depend on the device
+constexpr double PI = 3.141592653589793238462643383279502884;
+
+struct Shape {
+    int ndim, nb, nx, ny, nz;        // ny == 1 for ndim 2
+    int nzh;                         // nz / 2 + 1 complex values per row
+    int nmax, S;                     // the longest axis; the number of shells, min(n) / 2 + 1
+    int exact;                       // every nmax / n_i is an integer: the shell index in integer arithmetic
+    int kz_nyq;                      // nz / 2 for even nz, else -1
+    long long rows;                  // rows of one plane: nx * ny
+    long long rows_per_wg;
+    int wgs;                         // work-groups per plane
+};
+
+// ---------------------------------------------------------------------------------------------------------------------- kernels
+
+// Block tree reduction of a sum in LDS, fixed order; every thread gets the total.
+__device__ inline double block_sum(double v, double *sh) {
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = TPB / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+struct Mask {
+    int mode;                        // tomo_fsc_mask
+    const float *arr;
+    double R, E;
+};
+
+// The mask at voxel (ix, iy, iz) of a plane (linear index i within the plane), float64.
+template <int DIM>
+__device__ inline double mask_at(const Mask &m, const Shape &g, long long i) {
+    if (m.mode == TOMO_FSC_MASK_NONE) return 1.0;
+    if (m.mode == TOMO_FSC_MASK_ARRAY) return (double)m.arr[i];
+    const int iz = (int)(i % g.nz);
+    const long long row = i / g.nz;
+    double dx, dy = 0.0;
+    if (DIM == 3) {
+        dx = (double)(row / g.ny) - 0.5 * (g.nx - 1);
+        dy = (double)(row % g.ny) - 0.5 * (g.ny - 1);
+    } else {
+        dx = (double)row - 0.5 * (g.nx - 1);
+    }
+    const double dz = (double)iz - 0.5 * (g.nz - 1);
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    if (d2 <= m.R * m.R) return 1.0;
+    const double Ro = m.R + m.E;
+    if (d2 >= Ro * Ro || m.E <= 0.0) return 0.0;
+    return 0.5 * (1.0 + cos(PI * (sqrt(d2) - m.R) / m.E));
+}
+
+// part[(b * SUM_G + blk) * 2 + {0, 1}] = this block's share of sum(m v), sum(m) over plane b.
+template <int DIM>
+__global__ __launch_bounds__(TPB) void k_mask_sums(const float *__restrict__ v, Shape g, Mask m, double *__restrict__ part) {
+    __shared__ double sh[TPB];
+    const long long N = g.rows * g.nz;
+    const long long b = blockIdx.y;
+    const long long chunk = (N + SUM_G - 1) / SUM_G;
+    const long long lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+    double smv = 0.0, sm = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += TPB) {
+        const double w = mask_at<DIM>(m, g, i);
+        smv += w * (double)v[b * N + i];
+        sm += w;
+    }
+    const double t0 = block_sum(smv, sh);
+    const double t1 = block_sum(sm, sh);
+    if (threadIdx.x == 0) {
+        part[(b * SUM_G + blockIdx.x) * 2] = t0;
+        part[(b * SUM_G + blockIdx.x) * 2 + 1] = t1;
+    }
+}
+
+// out (rows of 2 nzh floats) = float32((v - mean) m); mean from part (NULL: 0).
+template <int DIM>
+__global__ __launch_bounds__(TPB) void k_prepare(const float *__restrict__ v, Shape g, Mask m, const double *__restrict__ part,
+                                                 float *__restrict__ out) {
+    __shared__ double sh[TPB];
+    const long long N = g.rows * g.nz;
+    const long long b = blockIdx.y;
+    double mean = 0.0;
+    if (part) {
+        const double smv = block_sum(part[(b * SUM_G + threadIdx.x) * 2], sh);
+        const double sm = block_sum(part[(b * SUM_G + threadIdx.x) * 2 + 1], sh);
+        mean = sm != 0.0 ? smv / sm : 0.0;
+    }
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    const double w = mask_at<DIM>(m, g, i);
+    const long long row = i / g.nz;
+    const int iz = (int)(i % g.nz);
+    out[(b * g.rows + row) * (2 * (long long)g.nzh) + iz] = (float)(((double)v[b * N + i] - mean) * w);
+}
+
+// The shell of the coefficient at |kx|, |ky| (their integer frequencies' magnitudes) and kz.  Exact form: r2 is an integer,
+// s = isqrt(r2), one more if r2 > s^2 + s, i.e. r > s + 1/2.  General form: float64, nothing contracted, so that a host model which
+// does the same operations in the same order gets the same index.
+__device__ inline int shell_exact(long long r2) {
+    long long s = (long long)sqrtf((float)r2);
+    while (s * s > r2) --s;
+    while ((s + 1) * (s + 1) <= r2) ++s;
+    return (int)(s + (r2 > s * s + s ? 1 : 0));
+}
+
+__device__ inline double sq_scaled(int k, int nmax, int n) {
+#pragma clang fp contract(off)
+    const double f = (double)((long long)k * nmax) / (double)n;
+    return f * f;
+}
+
+__device__ inline int shell_general(double fx2, double fy2, double fz2) {
+#pragma clang fp contract(off)
+    const double r2 = (fx2 + fy2) + fz2;
+    const double r = __dsqrt_rn(r2);
+    return (int)floor(r + 0.5);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(WAVE) void k_shell(const float2 *__restrict__ A, const float2 *__restrict__ B, Shape g, double *__restrict__ part) {
+    extern __shared__ double acc[];                  // [4][S]: C, PA, PB, n
+    const int lane = threadIdx.x;
+    const int S = g.S;
+    for (int i = lane; i < 4 * S; i += WAVE) acc[i] = 0.0;
+    __syncthreads();
+    const long long plane = blockIdx.y;
+    const long long row0 = (long long)blockIdx.x * g.rows_per_wg;
+    const long long row1 = min(g.rows, row0 + g.rows_per_wg);
+    const long long base = plane * g.rows * g.nzh;
+    const int sx = g.nmax / g.nx, sy = g.nmax / g.ny, sz = g.nmax / g.nz;      // used by the exact form only (ny = 1 for DIM 2: ky = 0)
+    for (long long row = row0; row < row1; ++row) {
+        const int ix = DIM == 3 ? (int)(row / g.ny) : (int)row;
+        const int iy = DIM == 3 ? (int)(row % g.ny) : 0;
+        const int kx = min(ix, g.nx - ix), ky = DIM == 3 ? min(iy, g.ny - iy) : 0;
+        long long r2xy = 0;
+        double fx2 = 0.0, fy2 = 0.0;
+        if (g.exact) {
+            const long long a = (long long)kx * sx, b = (long long)ky * sy;
+            r2xy = a * a + b * b;
+        } else {
+            fx2 = sq_scaled(kx, g.nmax, g.nx);
+            fy2 = DIM == 3 ? sq_scaled(ky, g.nmax, g.ny) : 0.0;
+        }
+        const float2 *ra = A + base + row * g.nzh, *rb = B + base + row * g.nzh;
+        for (int c0 = 0; c0 < g.nzh; c0 += WAVE) {
+            const int kz = c0 + lane;
+            const bool live = kz < g.nzh;
+            int s = S;                                // the key of everything that is not accumulated: the tail of the row
+            double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+            if (live) {
+                if (g.exact) {
+                    const long long c = (long long)kz * sz;
+                    s = shell_exact(r2xy + c * c);
+                } else {
+                    s = shell_general(fx2, fy2, sq_scaled(kz, g.nmax, g.nz));
+                }
+                if (s < S) {
+                    const float2 a = ra[kz], b = rb[kz];
+                    const double w = (kz == 0 || kz == g.kz_nyq) ? 1.0 : 2.0;
+                    const double ar = a.x, ai = a.y, br = b.x, bi = b.y;
+                    v0 = w * (ar * br + ai * bi);
+                    v1 = w * (ar * ar + ai * ai);
+                    v2 = w * (br * br + bi * bi);
+                    v3 = w;
+                } else {
+                    s = S;
+                }
+            }
+            // segmented reduction: after the step of stride d a lane holds the sum over itself and the next 2 d - 1 lanes of its run
+#pragma unroll
+            for (int d = 1; d < WAVE; d <<= 1) {
+                const int so = __shfl_down(s, d, WAVE);
+                const double o0 = __shfl_down(v0, d, WAVE), o1 = __shfl_down(v1, d, WAVE);
+                const double o2 = __shfl_down(v2, d, WAVE), o3 = __shfl_down(v3, d, WAVE);
+                if (lane + d < WAVE && so == s) {
+                    v0 += o0;
+                    v1 += o1;
+                    v2 += o2;
+                    v3 += o3;
+                }
+            }
+            const int sp = __shfl_up(s, 1, WAVE);
+            if ((lane == 0 || sp != s) && s < S) {
+                acc[s] += v0;
+                acc[S + s] += v1;
+                acc[2 * S + s] += v2;
+                acc[3 * S + s] += v3;
+            }
+            __syncthreads();                          // one wave: orders this chunk's LDS updates before the next chunk's
+        }
+    }
+    double *out = part + (plane * gridDim.x + blockIdx.x) * (long long)(4 * S);
+    for (int i = lane; i < 4 * S; i += WAVE) out[i] = acc[i];
+}
+
+// table[b][i] = part[b][0][i] + part[b][1][i] + ... in index order; i < 4 S.
+__global__ __launch_bounds__(TPB) void k_shell_final(const double *__restrict__ part, int wgs, int n4, double *__restrict__ table) {
+    const long long b = blockIdx.y;
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n4) return;
+    double t = 0.0;
+    for (int w = 0; w < wgs; ++w) t += part[(b * wgs + w) * (long long)n4 + i];
+    table[b * n4 + i] = t;
+}
+
+template <int VW>
+__global__ __launch_bounds__(TPB) void k_take_rows(const float *__restrict__ src, size_t row_v, size_t first, size_t step, size_t total_v,
+                                                   float *__restrict__ dst) {
+    typedef typename std::conditional<VW == 4, float4, float>::type vec_t;
+    const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= total_v) return;
+    const size_t r = i / row_v, c = i % row_v;
+    reinterpret_cast<vec_t *>(dst)[i] = reinterpret_cast<const vec_t *>(src)[(first + r * step) * row_v + c];
+}
+
+struct Plan {
+    hipfftHandle fft = 0;
+    void *work = nullptr;
+    size_t work_bytes = 0;
+};
+
+struct Buf {
+    void *p = nullptr;
+    size_t n = 0;
+};
+
+}  // namespace
+
+struct tomo_fsc {
+    int device = 0;
+    std::string err;
+    bool shaped = false;
+    Shape g{};
+    std::map<std::tuple<int, int, int, int, int>, Plan> plans;
+    Plan *plan = nullptr;
+    Buf spec[2], sums, part, table;
+    double t_plan = 0.0;
+};
+
+namespace {
+
+int fail(tomo_fsc *h, int code, const std::string &msg) {
+    if (h) h->err = msg; else g_err = msg;
+    return code;
+}
+
+#define HIPCHK(h, call)                                                                                              \
+    do {                                                                                                             \
+        hipError_t e_ = (call);                                                                                      \
+        if (e_ != hipSuccess) return fail(h, TOMO_FSC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
+    } while (0)
+#define FFTCHK(h, call)                                                                                                             \
+    do {                                                                                                                            \
+        hipfftResult r_ = (call);                                                                                                   \
+        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_FSC_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
+    } while (0)
+#define CHK(expr)                           \
+    do {                                    \
+        int rc_ = (expr);                   \
+        if (rc_ != TOMO_FSC_OK) return rc_; \
+    } while (0)
+
+// A work buffer of at least `bytes`, grown (never shrunk) on demand.
+int grow(tomo_fsc *h, Buf &b, size_t bytes) {
+    if (b.n >= bytes) return TOMO_FSC_OK;
+    if (b.p) {
+        HIPCHK(h, hipFree(b.p));
+        b.p = nullptr;
+        b.n = 0;
+    }
+    HIPCHK(h, hipMalloc(&b.p, bytes));
+    b.n = bytes;
+    return TOMO_FSC_OK;
+}
+
+int make_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, int nz, Shape *out) {
+    if (ndim != 2 && ndim != 3) return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: ndim must be 2 or 3, got " + std::to_string(ndim));
+    if (ndim == 2) ny = 1;
+    if (ndim == 3 && nb != 1) return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: one volume at a time (nb = 1 for ndim 3)");
+    if (nb < 1 || nb > TOMO_FSC_MAX_PLANES)
+        return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: nb must be 1 ... " + std::to_string(TOMO_FSC_MAX_PLANES) + ", got " + std::to_string(nb));
+    const int ext[3] = {nx, nz, ny};
+    for (int i = 0; i < ndim; ++i)
+        if (ext[i] < 2 || ext[i] > TOMO_FSC_MAX_N)
+            return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: every axis must have 2 ... " + std::to_string(TOMO_FSC_MAX_N) + " values, got " +
+                                                         std::to_string(ext[i]));
+    const long long total = (long long)nb * nx * ny * nz;
+    if (total > 2147483647LL) return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: more than 2^31 - 1 values");
+    Shape g{};
+    g.ndim = ndim, g.nb = nb, g.nx = nx, g.ny = ny, g.nz = nz;
+    g.nzh = nz / 2 + 1;
+    g.nmax = std::max(nx, nz);
+    int nmin = std::min(nx, nz);
+    if (ndim == 3) g.nmax = std::max(g.nmax, ny), nmin = std::min(nmin, ny);
+    g.S = nmin / 2 + 1;
+    g.exact = g.nmax % nx == 0 && g.nmax % nz == 0 && (ndim == 2 || g.nmax % ny == 0);
+    g.kz_nyq = nz % 2 == 0 ? nz / 2 : -1;
+    g.rows = (long long)nx * ny;
+    const long long want = ndim == 3 ? SHELL_WGS : std::max(8, SHELL_WGS / nb);
+    g.rows_per_wg = (g.rows + want - 1) / want;
+    g.wgs = (int)((g.rows + g.rows_per_wg - 1) / g.rows_per_wg);
+    *out = g;
+    return TOMO_FSC_OK;
+}
+
+size_t spectrum_bytes(const Shape &g) { return sizeof(float2) * (size_t)g.nb * (size_t)g.rows * (size_t)g.nzh; }
+
+int get_plan(tomo_fsc *h, const Shape &g, Plan **out) {
+    auto key = std::make_tuple(g.ndim, g.nb, g.nx, g.ny, g.nz);
+    auto it = h->plans.find(key);
+    if (it != h->plans.end()) {
+        *out = &it->second;
+        return TOMO_FSC_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    Plan p;
+    FFTCHK(h, hipfftCreate(&p.fft));
+    hipfftResult r = hipfftSetAutoAllocation(p.fft, 0);
+    size_t ws = 0;
+    if (r == HIPFFT_SUCCESS) {
+        if (g.ndim == 3) {
+            r = hipfftMakePlan3d(p.fft, g.nx, g.ny, g.nz, HIPFFT_R2C, &ws);
+        } else {
+            int n[2] = {g.nx, g.nz};
+            r = hipfftMakePlanMany(p.fft, 2, n, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_R2C, g.nb, &ws);
+        }
+    }
+    if (r != HIPFFT_SUCCESS) {
+        hipfftDestroy(p.fft);
+        return fail(h, TOMO_FSC_ERR_FFT, "hipfft R2C plan: hipfft error " + std::to_string((int)r));
+    }
+    if (ws) {
+        hipError_t e = hipMalloc(&p.work, ws);
+        if (e != hipSuccess) {
+            hipfftDestroy(p.fft);
+            return fail(h, TOMO_FSC_ERR_HIP, std::string("hipMalloc of the hipFFT work area: ") + hipGetErrorString(e));
+        }
+        p.work_bytes = ws;
+        r = hipfftSetWorkArea(p.fft, p.work);
+        if (r != HIPFFT_SUCCESS) {
+            (void)hipFree(p.work);
+            hipfftDestroy(p.fft);
+            return fail(h, TOMO_FSC_ERR_FFT, "hipfftSetWorkArea: hipfft error " + std::to_string((int)r));
+        }
+    }
+    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out = &(h->plans[key] = p);
+    return TOMO_FSC_OK;
+}
+
+int ready(tomo_fsc *h, const char *who) {
+    if (!h) return fail(h, TOMO_FSC_ERR_ARG, std::string(who) + ": NULL handle");
+    if (!h->shaped) return fail(h, TOMO_FSC_ERR_ARG, std::string(who) + ": call tomo_fsc_set_shape first");
+    return TOMO_FSC_OK;
+}
+
+inline dim3 grid1(long long n, int b) { return dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)b); }
+
+}  // namespace
+
+extern "C" {
+
+TOMO_API int tomo_fsc_abi_version(void) { return 1; }
+
+TOMO_API int tomo_fsc_create(int device, tomo_fsc **out) {
+    if (!out) return fail(nullptr, TOMO_FSC_ERR_ARG, "NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_FSC_ERR_NODEV, "no HIP device");
+    if (device < 0 || device >= n) return fail(nullptr, TOMO_FSC_ERR_ARG, "device out of range");
+    tomo_fsc *h = new tomo_fsc();
+    h->device = device;
+    *out = h;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_destroy(tomo_fsc *h) {
+    if (!h) return TOMO_FSC_OK;
+    (void)hipSetDevice(h->device);
+    for (auto &kv : h->plans) {
+        hipfftDestroy(kv.second.fft);
+        if (kv.second.work) (void)hipFree(kv.second.work);
+    }
+    for (Buf *b : {&h->spec[0], &h->spec[1], &h->sums, &h->part, &h->table})
+        if (b->p) (void)hipFree(b->p);
+    delete h;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API const char *tomo_fsc_last_error(tomo_fsc *h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+TOMO_API int tomo_fsc_n_shells(int ndim, int nb, int nx, int ny, int nz, int *n_shells) {
+    if (!n_shells) return fail(nullptr, TOMO_FSC_ERR_ARG, "tomo_fsc_n_shells: NULL");
+    Shape g{};
+    CHK(make_shape(nullptr, ndim, nb, nx, ny, nz, &g));
+    *n_shells = g.S;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_set_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, int nz) {
+    if (!h) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_set_shape: NULL handle");
+    Shape g{};
+    CHK(make_shape(h, ndim, nb, nx, ny, nz, &g));
+    HIPCHK(h, hipSetDevice(h->device));
+    h->shaped = false;
+    CHK(get_plan(h, g, &h->plan));
+    CHK(grow(h, h->spec[0], spectrum_bytes(g)));
+    CHK(grow(h, h->spec[1], spectrum_bytes(g)));
+    CHK(grow(h, h->sums, sizeof(double) * 2 * SUM_G * (size_t)g.nb));
+    CHK(grow(h, h->part, sizeof(double) * 4 * (size_t)g.S * (size_t)g.wgs * (size_t)g.nb));
+    CHK(grow(h, h->table, sizeof(double) * 4 * (size_t)g.S * (size_t)g.nb));
+    h->g = g;
+    h->shaped = true;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_device_bytes(tomo_fsc *h, int64_t *bytes) {
+    if (!h || !bytes) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_device_bytes: NULL");
+    size_t t = h->spec[0].n + h->spec[1].n + h->sums.n + h->part.n + h->table.n;
+    for (auto &kv : h->plans) t += kv.second.work_bytes;
+    *bytes = (int64_t)t;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_plan_seconds(tomo_fsc *h, double *seconds) {
+    if (!h || !seconds) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_plan_seconds: NULL");
+    *seconds = h->t_plan;
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_prepare(tomo_fsc *h, void *stream, int slot, const float *d_vol, int mask, const float *d_mask, double radius,
+                              double edge, int subtract_mean) {
+    CHK(ready(h, "tomo_fsc_prepare"));
+    if (slot != 0 && slot != 1) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_prepare: slot must be 0 or 1");
+    if (!d_vol) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_prepare: NULL volume");
+    if (mask != TOMO_FSC_MASK_NONE && mask != TOMO_FSC_MASK_ARRAY && mask != TOMO_FSC_MASK_SPHERE)
+        return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_prepare: unknown mask mode");
+    if (mask == TOMO_FSC_MASK_ARRAY && !d_mask) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_prepare: NULL mask array");
+    if (mask == TOMO_FSC_MASK_SPHERE && !(radius >= 0.0 && edge >= 0.0 && radius < 1e9 && edge < 1e9))
+        return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_prepare: the sphere needs a finite radius >= 0 and edge >= 0");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Shape &g = h->g;
+    const Mask m{mask, d_mask, radius, edge};
+    const long long N = g.rows * g.nz;
+    double *part = subtract_mean ? (double *)h->sums.p : nullptr;
+    float *out = (float *)h->spec[slot].p;
+    if (g.ndim == 3) {
+        if (part) hipLaunchKernelGGL(k_mask_sums<3>, dim3(SUM_G, g.nb), dim3(TPB), 0, st, d_vol, g, m, part);
+        hipLaunchKernelGGL(k_prepare<3>, grid1(N, g.nb), dim3(TPB), 0, st, d_vol, g, m, (const double *)part, out);
+    } else {
+        if (part) hipLaunchKernelGGL(k_mask_sums<2>, dim3(SUM_G, g.nb), dim3(TPB), 0, st, d_vol, g, m, part);
+        hipLaunchKernelGGL(k_prepare<2>, grid1(N, g.nb), dim3(TPB), 0, st, d_vol, g, m, (const double *)part, out);
+    }
+    HIPCHK(h, hipGetLastError());
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_fft(tomo_fsc *h, void *stream, int slot) {
+    CHK(ready(h, "tomo_fsc_fft"));
+    if (slot != 0 && slot != 1) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_fft: slot must be 0 or 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    FFTCHK(h, hipfftSetStream(h->plan->fft, reinterpret_cast<hipStream_t>(stream)));
+    FFTCHK(h, hipfftExecR2C(h->plan->fft, (hipfftReal *)h->spec[slot].p, (hipfftComplex *)h->spec[slot].p));
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_reduce(tomo_fsc *h, void *stream) {
+    CHK(ready(h, "tomo_fsc_reduce"));
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Shape &g = h->g;
+    const size_t lds = sizeof(double) * 4 * (size_t)g.S;
+    const float2 *A = (const float2 *)h->spec[0].p, *B = (const float2 *)h->spec[1].p;
+    double *part = (double *)h->part.p, *table = (double *)h->table.p;
+    if (g.ndim == 3)
+        hipLaunchKernelGGL(k_shell<3>, dim3(g.wgs, g.nb), dim3(WAVE), lds, st, A, B, g, part);
+    else
+        hipLaunchKernelGGL(k_shell<2>, dim3(g.wgs, g.nb), dim3(WAVE), lds, st, A, B, g, part);
+    hipLaunchKernelGGL(k_shell_final, grid1(4 * g.S, g.nb), dim3(TPB), 0, st, (const double *)part, g.wgs, 4 * g.S, table);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_fetch(tomo_fsc *h, void *stream, double *out) {
+    CHK(ready(h, "tomo_fsc_fetch"));
+    if (!out) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_fetch: NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIPCHK(h, hipMemcpyAsync(out, h->table.p, sizeof(double) * 4 * (size_t)h->g.S * (size_t)h->g.nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return TOMO_FSC_OK;
+}
+
+TOMO_API int tomo_fsc_take_rows(tomo_fsc *h, void *stream, const float *d_src, size_t row_elems, size_t first, size_t step, size_t count,
+                                float *d_dst) {
+    if (!h) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_take_rows: NULL handle");
+    if (row_elems < 1 || step < 1) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_take_rows: row_elems and step must be >= 1");
+    if (count == 0) return TOMO_FSC_OK;
+    if (!d_src || !d_dst) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_take_rows: NULL pointer");
+    const bool v4 = row_elems % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 15u) == 0;
+    const size_t row_v = v4 ? row_elems / 4 : row_elems, total_v = row_v * count;
+    const size_t blocks = (total_v + TPB - 1) / TPB;
+    if (blocks >= (1ull << 31)) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_take_rows: too many work-groups");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (v4)
+        hipLaunchKernelGGL(k_take_rows<4>, dim3((unsigned)blocks), dim3(TPB), 0, st, d_src, row_v, first, step, total_v, d_dst);
+    else
+        hipLaunchKernelGGL(k_take_rows<1>, dim3((unsigned)blocks), dim3(TPB), 0, st, d_src, row_v, first, step, total_v, d_dst);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_FSC_OK;
+}
+
+}  // extern "C"

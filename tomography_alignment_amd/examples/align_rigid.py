@@ -13,6 +13,10 @@ per iteration over xGMI) and aligns its own projections against the replicated r
 inside the optimiser; the recovered pose table is summed once per outer iteration.  The reconstruction is warm-started
 from the previous outer iteration's (examples/align_rigid.py:42) where it lies, in HBM.
 
+Without ground truth (fsc=True, --fsc): after every alignment pass the even and the odd projections are reconstructed separately by FBP
+at the current poses and their Fourier shell correlation (resolution.half_set_fsc) gives the half-bit resolution, in full-size pixels --
+the monitor that measured data, which have no phantom, allow.
+
 Coarse to fine (run_multires, --levels): the first outer iterations run on data binned by 2^(levels-1), ..., 2 (multires.py: the
 binning and prolongation kernels of libtomo_pyr.so), each level a unit-pitch geometry of its own; the poses (translations times 2, tilts
 as they are) and the prolonged reconstruction are handed up, and only the last iterations run at full size.  The bounds of the optimiser
@@ -20,6 +24,7 @@ are in pixels of the level, so the same +-3 px reach +-12 full-size pixels at a 
 
     python -m tomography_alignment_amd.examples.align_rigid data.npz --outer 5 --sirt-iters 50
     python -m tomography_alignment_amd.examples.align_rigid data.npz --levels 3 --outer 3 --sirt-iters 50
+    python -m tomography_alignment_amd.examples.align_rigid measured.npz --fsc          # no phantom needed: a resolution per outer iteration
     python -m torch.distributed.run --nproc-per-node 8 -m tomography_alignment_amd.examples.align_rigid data.npz
 """
 import argparse
@@ -27,7 +32,7 @@ import time
 
 import numpy as np
 
-from .. import alignment, multires
+from .. import alignment, multires, resolution
 from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
 
@@ -152,29 +157,52 @@ class OuterLoop(object):
         return {"shift_err_px": float(np.abs(shifts - np.asarray(d["xyz"])[:, [0, 2]]).mean()),
                 "tilt_err_deg": float(np.rad2deg(np.abs(np.column_stack([self.alpha_rec, self.beta_rec]) - np.column_stack([d["alpha"], d["beta"]])).mean()))}
 
+    def half_set_fsc(self, res=None):
+        """The FSC of the FBPs of the even and of the odd projections at the current pose estimates (resolution.half_set_fsc): the halves by
+        the parity of the GLOBAL index, each rank back-projecting the rows it holds."""
+        angles = np.array([self.phi, self.alpha_rec, self.beta_rec]).T
+        return resolution.half_set_fsc(self.geom, self.d_b, angles, self.xyz_rec, method="fbp", comm=self.comm, rows=self.mine,
+                                       options={"_backend": self.be}, resolution=res)
+
     def download(self):
         return self.be.download(self.d_rec).reshape(self.vox_shape)
 
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
-        kernel_names=None, download=True, return_loop=False, init="zero"):
+        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
+    fsc            True: every history entry gains `fsc_resolution` (pixels) and `fsc_curve` (_fsc_entry); needs no phantom.
     kernel_names   with a HIP context: the history carries the HIP-event kernel time of each half of each outer iteration for these names.
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
     loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names)
     history = []
-    for it in range(n_outer):
-        history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose))
+    res = resolution.Resolution(loop.ctx) if fsc else None
+    try:
+        for it in range(n_outer):
+            history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, fsc_with=res))
+    finally:
+        if res is not None:
+            res.close()
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
 
 
-def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, extra=None):
-    """One outer iteration of `loop` -- SIRT, then the alignment pass -- and its history entry (`extra`: more keys for it)."""
+def _fsc_entry(loop, res):
+    """`fsc_resolution`: the half-bit resolution of the half-set FBPs at the current poses, in pixels of the level times the level's factor;
+    where the curve stays above the threshold up to the last shell, that shell's length (the sampling limit, 2 pixels of the level).
+    `fsc_curve`: the resolution.FSCCurve itself (its crossing() tells the two cases apart)."""
+    curve = loop.half_set_fsc(res)
+    r = curve.resolution("half-bit")
+    return {"fsc_resolution": float(loop.factor * (curve.nyquist if r is None else r)), "fsc_curve": curve}
+
+
+def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, extra=None, fsc_with=None):
+    """One outer iteration of `loop` -- SIRT, then the alignment pass -- and its history entry (`extra`: more keys for it; `fsc_with`: a
+    resolution.Resolution -> the entry of _fsc_entry)."""
     ctx = loop.ctx
     k0 = _kernel_ms(ctx, kernel_names)
     t0 = time.perf_counter()
@@ -195,6 +223,8 @@ def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_na
     entry.update(loop.pose_errors())
     if extra:
         entry.update(extra)
+    if fsc_with is not None:
+        entry.update(_fsc_entry(loop, fsc_with))
     if verbose and loop.rank == 0:
         print(entry)
     return entry
@@ -211,12 +241,13 @@ def _per_level(value, levels, name):
 
 
 def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, align_kwargs=None, comm=None,
-                 kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None):
+                 kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None, fsc=False):
     """`run` coarse to fine (module docstring): levels binned by 2^(levels-1), ..., 2, 1, coarsest first.
     n_outer, sirt_iters   one number, or one per level, coarsest first.
     bounds                of the increment every pass searches around the pose carried up from the coarser level (zero at the coarsest),
                           in pixels of the level.
     init                  the start of the coarsest level's first SIRT; every finer level starts from the prolonged coarser reconstruction.
+    fsc                   as in `run`; `fsc_resolution` is in full-size pixels at every level.
     ctx                   the _lib.Context all levels share (default: the communicator's, or a new one).
     backend_factory, pyramid   test seams: geometry -> backend (default a HipBackend on ctx per level), and the object with multires.Pyramid's
                           three methods (default a Pyramid on ctx).
@@ -232,7 +263,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
     n_outer, sirt_iters = _per_level(n_outer, levels, "n_outer"), _per_level(sirt_iters, levels, "sirt_iters")
     if levels == 1:
         out = run(data, n_outer[0], sirt_iters[0], bounds=bounds, verbose=verbose, align_kwargs=align_kwargs, comm=comm,
-                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init)
+                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init, fsc=fsc)
         for entry in out[4]:
             entry.update(level=0, factor=1)
         return out
@@ -263,6 +294,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
     own_pyramid = pyramid is None
     if own_pyramid:
         pyramid = multires.Pyramid(ctx)
+    res = None
     try:
         poses = {k: data[k] for k in ("xyz", "alpha", "beta") if "xyz" in data}
         be = backend_factory(sirt_mpi.SIRT._shard_geometry(multires.level_geometry(n_proj, (nx, ny, nz)), mine))
@@ -286,9 +318,11 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
             if d_gt_l is not None:
                 ldata["phantom"] = d_gt_l
             loop = OuterLoop(ldata, backend=be_l, comm=comm, kernel_names=kernel_names, base=carried, d_rec=d_rec, factor=f)
+            if fsc and res is None:
+                res = resolution.Resolution(loop.ctx)
             for _ in range(n_outer[level]):
                 history.append(_outer_iteration(loop, len(history), sirt_iters[level], bounds, init if level == 0 else "zero", align_kwargs,
-                                                kernel_names, verbose, extra={"level": level, "factor": f}))
+                                                kernel_names, verbose, extra={"level": level, "factor": f}, fsc_with=res))
             if f == 1:
                 break
             # hand up, and free what this level held before the finer one allocates: the solver's buffers, the binned data, then -- once it is
@@ -302,6 +336,8 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
                 d_rec = pyramid.prolong_volume(coarse, shape=shape)
                 _free(coarse)
     finally:
+        if res is not None:
+            res.close()
         if own_pyramid:
             pyramid.close()
     rec = loop.download() if (download and loop.d_rec is not None) else None
@@ -329,6 +365,8 @@ def main():
     ap.add_argument("--init", choices=("zero", "fbp"), default="zero", help="start of the first SIRT: zero or the FBP")
     ap.add_argument("--levels", type=int, default=1, help="resolution levels, coarse to fine (run_multires); --outer and --sirt-iters "
                     "then count per level.  1: the plain loop")
+    ap.add_argument("--fsc", action="store_true", help="report the half-bit resolution of the half-set Fourier shell correlation per outer "
+                    "iteration (needs no phantom)")
     a = ap.parse_args()
     import os
     comm = None
@@ -336,9 +374,9 @@ def main():
         from ..comm import RcclComm
         comm = RcclComm.from_env()
     if a.levels == 1:
-        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init)
+        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc)
     else:
-        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init)
+        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc)
     if comm is not None:
         comm.close()
 

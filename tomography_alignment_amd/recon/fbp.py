@@ -120,7 +120,8 @@ class FBP(object):
     options: filter ('ramp' | 'shepp-logan' | 'cosine' | 'hamming' | 'hann'; default 'ramp'), angle_weights (n_proj weights that
     replace angle_weights(phi)), ground_truth (-> self.rms_error = ||gt - rec|| / ||gt||), _backend (a HipBackend) and
     overwrite_projections (filter a device-resident sinogram in place instead of into a buffer of its own: one sinogram less of HBM,
-    the caller's projections are then the filtered ones).  Projections and the ground truth may be DeviceArrays."""
+    the caller's projections are then the filtered ones) and download (default True; False: run() leaves the volume in self.d_rec and
+    returns None instead of copying it to the host).  Projections and the ground truth may be DeviceArrays."""
 
     def __init__(self, geometry, projections, angles, xyz_shifts, options={}):
         self.geometry = geometry
@@ -136,6 +137,7 @@ class FBP(object):
             raise ValueError("FBP: angle_weights must hold one weight per projection (%d)" % self.n_proj)
         self.ground_truth = options.get('ground_truth')
         self.overwrite_projections = bool(options.get('overwrite_projections', False))
+        self.download = bool(options.get('download', True))
         self._backend = options.get('_backend')
         self.rms_error = None
         self.d_rec = None
@@ -201,5 +203,7 @@ class FBP(object):
             if gt is not None:
                 err = be.acc_fetch(0)[0]
                 self.rms_error = float(np.sqrt(err) / np.sqrt(be.dot(gt, gt)))
+        if not self.download:
+            return None
         rec = be.download(self.d_rec)
         return rec.reshape(tuple(int(v) for v in self.geometry.vox_shape))
