@@ -1,0 +1,273 @@
+"""preprocess.retrieve_phase / minus_log on the GPU (libtomo_phase.so) against the float64 model of tests/phase_model.py: parity within
+16 d32 (d32: what float32 transforms cost the model itself) plus 2e-6 relative for logf, bit-for-bit equality across scratch budgets, in
+place, host and device paths, repeated calls and fresh handles, strength 0 against minus_log, order independence, no leaked buffers, and
+generate_data --raw --propagate -> examples/preprocess -> FBP.  Every test prints the error it measured."""
+import numpy as np
+import pytest
+
+import phase_model as pm
+
+from tomography_alignment_amd import _lib, _phase_lib, preprocess
+from tomography_alignment_amd.examples import generate_data
+from tomography_alignment_amd.examples import preprocess as ex_pre
+from tomography_alignment_amd.recon import fbp
+from tomography_alignment_amd.utilities.geometry import Geometry
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(5, 64, 48), (3, 33, 31), (2, 96, 128), (4, 128, 96)]
+STRENGTHS = [0.0, 1.0, 25.0, 400.0, 4000.0]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = _lib.Context()
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def pre(ctx):
+    p = preprocess.Preprocessor(ctx)
+    yield p
+    p.close()
+
+
+def _frames(shape, seed=0):
+    """Transmission-like float32 frames in 0.3 ... 1.2: a smooth body, an edge and white noise."""
+    rng = np.random.default_rng(seed)
+    n, nx, nz = shape
+    x = np.linspace(-1, 1, nx)[:, None]
+    z = np.linspace(-1, 1, nz)[None, :]
+    T = np.empty(shape)
+    for i in range(n):
+        body = 0.35 * np.sqrt(np.clip(1 - (x / rng.uniform(0.4, 0.9)) ** 2 - (z / rng.uniform(0.4, 0.9)) ** 2, 0, None))
+        T[i] = 1.0 - body - 0.2 * (x + 0.3 * z > rng.uniform(-0.5, 0.5)) + 0.1 * rng.uniform(-1, 1, (nx, nz))
+    return np.clip(T, 0.3, 1.2).astype(np.float32)
+
+
+def _bound(ref, d32, minus_log):
+    b = 16.0 * d32 * np.max(np.abs(ref)) * np.ones_like(ref)
+    if minus_log:
+        b = b + 2e-6 * np.maximum(1.0, np.abs(ref))
+    return b
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.parametrize("a", STRENGTHS)
+@pytest.mark.parametrize("shape", SHAPES)
+def test_parity_with_the_float64_model(pre, shape, a):
+    T = _frames(shape, seed=int(a) + shape[1])
+    worst = 0.0
+    for pad in (None, 0):
+        for minus_log in (True, False):
+            d32, ref = pm.d32(T, a, pad, minus_log)
+            got = pre.retrieve_phase(T, a, pad=pad, minus_log=minus_log)
+            assert got.dtype == np.float32 and got.shape == shape and np.all(np.isfinite(got))
+            err = np.abs(got.astype(np.float64) - ref)
+            frac = float(np.max(err / _bound(ref, d32, minus_log)))
+            worst = max(worst, frac)
+            print("shape %s a %g pad %s log %d: padded %s, d32 %.2e, max err %.2e (%.2f d32), fraction of the bound %.3f"
+                  % (shape, a, pad, minus_log, pm.padded_shape(shape, a, pad), d32, err.max() / np.max(np.abs(ref)),
+                     err.max() / np.max(np.abs(ref)) / d32, frac))
+            assert frac <= 1.0
+    print("shape %s a %g: largest fraction of the bound %.3f" % (shape, a, worst))
+
+
+def test_physical_arguments_equal_the_strength(pre):
+    T = _frames((2, 33, 31), seed=9)
+    a = preprocess.paganin_strength(1e-6, 0.01, energy=25.0, delta_beta=100.0)
+    by_strength = pre.retrieve_phase(T, a)
+    by_physics = pre.retrieve_phase(T, pixel_size=1e-6, dist=0.01, energy=25.0, delta_beta=100.0)
+    print("a = %.3f" % a)
+    assert np.array_equal(_bits(by_strength), _bits(by_physics))
+
+
+def test_scratch_budgets_give_the_same_bits(ctx, pre):
+    shape = (5, 64, 48)
+    T = _frames(shape, seed=1)
+    for a, pad in ((400.0, None), (25.0, 0)):
+        px, pz = pm.padded_shape(shape, a, pad)
+        fb = 4 * px * (pz + 2)
+        ref = pre.retrieve_phase(T, a, pad=pad, max_scratch_bytes=0)
+        assert _phase_lib.batch(5, px, pz, 0) == 5 and _phase_lib.batch(5, px, pz, 2 * fb) == 1 and _phase_lib.batch(5, px, pz, 1) == 1
+        assert _phase_lib.batch(5, px, pz, 4 * fb) == 2 and _phase_lib.batch(5, px, pz, 6 * fb + 5) == 3
+        for budget in (1, 2 * fb, 4 * fb, 6 * fb + 5, 8 * fb, None):
+            got = pre.retrieve_phase(T, a, pad=pad, max_scratch_bytes=budget)
+            diff = float(np.max(np.abs(got - ref)))
+            print("a %g budget %s: max difference from the unbatched run %.1e" % (a, budget, diff))
+            assert np.array_equal(_bits(got), _bits(ref)), budget
+
+
+def test_in_place_host_device_repeats_and_a_fresh_handle_give_the_same_bits(ctx, pre):
+    shape = (4, 128, 96)
+    T = _frames(shape, seed=2)
+    for minus_log in (True, False):
+        host = pre.retrieve_phase(T, 400.0, minus_log=minus_log)
+        d = ctx.to_device(T)
+        out_of_place = pre.retrieve_phase(d, 400.0, minus_log=minus_log)
+        assert isinstance(out_of_place, _lib.DeviceArray) and np.array_equal(d.download(), T)
+        given = ctx.zeros(shape)
+        assert pre.retrieve_phase(d, 400.0, minus_log=minus_log, out=given) is given
+        pre.retrieve_phase(_frames((3, 33, 31)), 25.0)                       # another shape and plan between the calls
+        assert pre.retrieve_phase(d, 400.0, minus_log=minus_log, out=d) is d
+        with preprocess_handle(ctx) as fresh:
+            other = fresh.retrieve_phase(T, 400.0, minus_log=minus_log)
+        module_level = preprocess.retrieve_phase(T, 400.0, ctx=ctx, minus_log=minus_log)
+        results = dict(out_of_place=out_of_place.download(), given=given.download(), in_place=d.download(), fresh=other,
+                       module_level=module_level, repeat=pre.retrieve_phase(T, 400.0, minus_log=minus_log))
+        for name, r in results.items():
+            print("log %d %s: max difference from the host path %.1e" % (minus_log, name, float(np.max(np.abs(r - host)))))
+            assert np.array_equal(_bits(r), _bits(host)), name
+        for b in (d, out_of_place, given):
+            b.free()
+
+
+class preprocess_handle(object):
+    def __init__(self, ctx):
+        self.p = preprocess.Preprocessor(ctx)
+
+    def __enter__(self):
+        return self.p
+
+    def __exit__(self, *exc):
+        self.p.close()
+
+
+def test_strength_zero_is_minus_log(ctx, pre):
+    T = _frames((3, 33, 31), seed=3)
+    T.reshape(-1)[::7] = 0.0            # clamped
+    T.reshape(-1)[3::11] = -0.5
+    T.reshape(-1)[5::13] = 1.0          # -log(1) = -0
+    ml = pre.minus_log(T)
+    ref = -np.log(np.fmax(T.astype(np.float64), 1e-6))
+    err = float(np.max(np.abs(ml - ref) / np.maximum(1.0, np.abs(ref))))
+    print("minus_log against float64: %.2e relative" % err)
+    assert err <= 2e-6 and np.all(np.isfinite(ml))
+    for pad in (None, 0, 9):
+        assert np.array_equal(_bits(pre.retrieve_phase(T, 0.0, pad=pad)), _bits(ml))
+        assert np.array_equal(_bits(pre.retrieve_phase(T, 0.0, pad=pad, minus_log=False)), _bits(T))
+    assert np.array_equal(_bits(preprocess.minus_log(T, ctx=ctx)), _bits(ml))
+    half = -np.log(np.fmax(T.astype(np.float64), 0.5))
+    assert np.max(np.abs(pre.minus_log(T, min_ratio=0.5) - half) / np.maximum(1.0, np.abs(half))) <= 2e-6
+    d = ctx.to_device(T[:, :, :30].copy())                                  # 2970 values: the scalar tail after the float4 body
+    assert pre.minus_log(d, out=d) is d
+    assert np.array_equal(_bits(d.download()), _bits(ml[:, :, :30]))
+    d.free()
+
+
+def test_a_constant_frame_gives_minus_log_c(pre):
+    for c in (0.25, 1.0, 1.7):
+        T = np.full((2, 33, 31), c, np.float32)
+        for a in (25.0, 4000.0):
+            d32, ref = pm.d32(T, a)
+            got = pre.retrieve_phase(T, a)
+            err = np.abs(got - (-np.log(np.float64(np.float32(c)))))
+            frac = float(np.max(err / _bound(ref, d32, True)))
+            print("c %g a %g: max error %.2e, fraction of the bound %.3f" % (c, a, err.max(), frac))
+            assert frac <= 1.0
+
+
+def test_frames_do_not_influence_each_other(pre):
+    shape = (5, 64, 48)
+    T = _frames(shape, seed=4)
+    perm = np.array([3, 0, 4, 1, 2])
+    fb = 4 * 80 * (64 + 2)
+    ref = pre.retrieve_phase(T, 25.0)
+    for budget in (None, 4 * fb):
+        got = pre.retrieve_phase(T[perm], 25.0, max_scratch_bytes=budget)
+        print("permuted stack, budget %s: max difference %.1e" % (budget, float(np.max(np.abs(got - ref[perm])))))
+        assert np.array_equal(_bits(got), _bits(ref[perm]))
+    alone = pre.retrieve_phase(T[2:3], 25.0)
+    assert np.array_equal(_bits(alone), _bits(ref[2:3]))
+
+
+def test_unsupported_sizes_are_refused_and_leave_the_buffers(ctx, pre):
+    T = _frames((1, 8, 6))
+    d = ctx.to_device(T)
+    o = ctx.zeros(T.shape)
+    with pytest.raises(preprocess.PrepUnsupported):
+        pre.retrieve_phase(d, 25.0, pad=4100, out=o)
+    assert np.array_equal(d.download(), T) and not np.any(o.download())
+    with pytest.raises(preprocess.PrepUnsupported):
+        _phase_lib.padded_length(8000, 100)
+    assert _phase_lib.padded_length(1024, 128) == 1280
+
+
+def test_device_residency_and_no_leaks(ctx, pre):
+    T = _frames((4, 128, 96), seed=5)
+    d = ctx.to_device(T)
+    pre.retrieve_phase(d, 400.0, out=d)                                     # warm: the plan and the work area belong to the handle
+    held = pre._phase.device_bytes()
+    before = len(ctx._arrays)
+    r = pre.retrieve_phase(d, 400.0)
+    assert isinstance(r, _lib.DeviceArray) and r.shape == T.shape and len(ctx._arrays) == before + 1
+    r.free()
+    del r
+    pre.retrieve_phase(d, 400.0, out=d)
+    pre.retrieve_phase(d, 400.0, out=d, max_scratch_bytes=1)
+    pre.minus_log(d, out=d)
+    assert len(ctx._arrays) == before
+    assert isinstance(pre.retrieve_phase(T, 400.0), np.ndarray) and isinstance(pre.minus_log(T), np.ndarray)
+    assert isinstance(preprocess.retrieve_phase(T, 400.0, ctx=ctx), np.ndarray)
+    assert len(ctx._arrays) == before
+    print("device bytes the handle keeps between calls: %d (before) %d (after)" % (held, pre._phase.device_bytes()))
+    assert pre._phase.device_bytes() == held
+    # the spectrum buffer is the library's own allocation: the device's free memory says whether it is gone after every call
+    free0 = pre._phase.mem_info()[0]
+    for _ in range(8):
+        pre.retrieve_phase(d, 400.0, out=d)
+        pre.retrieve_phase(d, 400.0, out=d, max_scratch_bytes=1)
+    free1 = pre._phase.mem_info()[0]
+    print("free device memory before %d and after %d sixteen more calls (one spectrum batch: %d bytes)" % (free0, free1, 4 * 4 * 180 * 152))
+    assert free1 >= free0
+    _, ms = pre.retrieve_phase(d, 400.0, out=d, timed=True)
+    print("pass ms (pad, r2c, filter, c2r, crop): %s" % (ms,))
+    assert len(ms) == 5 and all(t > 0 for t in ms)
+    d.free()
+    plain = preprocess.Preprocessor(ctx)
+    plain.remove_stripe_sorting(_frames((8, 16, 6)), size=3)
+    assert plain._phase is None                                             # never retrieved: no phase handle, no hipFFT
+    plain.close()
+
+
+def _fbp_rmse(data, proj):
+    n, nx, nz = proj.shape
+    geom = Geometry(n, np.array([nx, nx, nz]), np.ones(3), np.array([nx, nz]), np.ones(2))
+    angles = np.zeros((n, 3))
+    angles[:, 0] = data["phi"]
+    rec = fbp.FBP(geom, proj, angles, np.zeros((n, 3))).run()
+    gt = data["phantom"]
+    c = (np.arange(nx) - (nx - 1) / 2.0)
+    inside = (c[:, None] ** 2 + c[None, :] ** 2 < (0.45 * nx) ** 2)[:, :, None] * np.ones((1, 1, nz), bool)
+    return float(np.sqrt(np.mean((rec - gt)[inside] ** 2)))
+
+
+def _rms(a, b):
+    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - b) ** 2)))
+
+
+def test_end_to_end_fringed_raw_data_to_fbp(ctx):
+    data = generate_data.make(64, 90, seed=0, ang_deg=0.0, shift_px=0.0, raw=True, propagate=25)
+    truth = np.asarray(data["projections"], np.float64)                     # the unpropagated data set's projections
+    mu = float(data["mu"])
+    for stripe in (0, 21):
+        plain = ex_pre.run(data, stripe_size=stripe, ctx=ctx)
+        retrieved = ex_pre.run(data, stripe_size=stripe, ctx=ctx, phase=dict(strength=25.0))
+        assert "counts" not in retrieved and retrieved["projections"].shape == (90, 64, 64)
+        e_plain, e_ret = _rms(plain["projections"], truth), _rms(retrieved["projections"], truth)
+        f_plain, f_ret = _fbp_rmse(data, plain["projections"]), _fbp_rmse(data, retrieved["projections"])
+        print("stripe window %d: projection rms error %.4f -> %.4f (ratio %.2f); FBP rmse in the cylinder %.4f -> %.4f"
+              % (stripe, e_plain, e_ret, e_plain / e_ret, f_plain, f_ret))
+        if stripe == 0:
+            # the model on the same data: the same flat-field ratio, retrieved and not, in float64
+            T = preprocess.normalize(data["counts"], data["flats"], data["darks"], minus_log=False, ctx=ctx)
+            m_plain, m_ret = _rms(pm.finish(T) / mu, truth), _rms(pm.retrieve(T, 25.0) / mu, truth)
+            print("the model on the same data: %.4f -> %.4f (ratio %.2f)" % (m_plain, m_ret, m_plain / m_ret))
+            assert m_plain / m_ret > 1.0
+            assert e_plain / e_ret >= 0.5 * m_plain / m_ret
+        assert e_ret < e_plain
+        assert f_ret < f_plain

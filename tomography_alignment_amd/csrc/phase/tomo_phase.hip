@@ -1,0 +1,492 @@
+// libtomo_phase.so: Paganin single-distance phase retrieval of a device-resident stack of transmission frames (include/tomo_phase.h,
+// tomography_alignment_amd/preprocess.py) on gfx950.  The transforms are hipFFT's batched 2-D R2C / C2R, in place in one padded buffer;
+// everything else is the three streaming kernels below.  A frame of the buffer is Px rows of RS = 2 (Pz/2 + 1) floats, which the R2C
+// turns into Px rows of Pz/2 + 1 complex values.  Every kernel is a flat grid over one batch: a thread finds its frame from blockIdx.y
+// and its row from one integer division, so short rows (a 48-wide frame) fill a work-group as well as long ones.
+//
+// k_pad      one thread per float2 of the padded buffer: the two source values are T's at the clamped coordinates (edge replication),
+//            read lane-contiguous along z, and the pair is stored with one 8-byte store; the two floats past Pz that the in-place layout
+//            adds to every row are written as zeros.  There is no real-valued padded copy beside the FFT buffer.
+// k_filter   the half-spectrum times H / (Px Pz).  H is never stored: tx[kx] = Px Pz a (kx / Px)^2 and tz[kz] = Px Pz (1 + a (kz / Pz)^2)
+//            come from the host in float64, and the multiplier is 1.0f / float(tx[kx] + tz[kz]), an IEEE float32 division.  A thread
+//            owns two neighbouring coefficients as one float4.  Rows are Pz/2 + 1 complex values long, an odd count for most lengths, so
+//            every other row starts 8 bytes off a 16-byte boundary: the row's pairs are shifted by one there, and the first and last
+//            coefficient of such a row go as single float2.
+// k_crop     crop + clamp + -log: a thread reads four values of a row of the window (two float2 where the window's z offset is even, so
+//            that they are aligned) and stores one float4 of the output; a scalar form serves rows whose length is not a multiple of 4.
+//            The output may be the buffer the pad kernel read: a batch's frames are all padded before any of them is written.
+// k_log      -log(fmax(v, min_ratio)) of a flat array, float4 with a scalar tail: minus_log alone, and strength 0.
+#include <hip/hip_runtime.h>
+#include <hipfft/hipfft.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <map>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "../../../include/tomo_phase.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+constexpr int TPB = 256;
+constexpr int MAX_BATCH = 65535;                 // frames of one batch: the y extent of a grid
+constexpr long long MAX_BATCH_FLOATS = 1LL << 31;  // floats of one batch's buffer
+
+struct Shape {
+    int nx, nz;          // a frame
+    int px, pz;          // the padded frame
+    int ox, oz;          // where the data sits in it
+    int pzh;             // pz / 2 + 1 complex values per row; a row is 2 pzh floats
+};
+
+// ---------------------------------------------------------------------------------------------------------------------- kernels
+
+__global__ __launch_bounds__(TPB) void k_pad(const float *__restrict__ T, Shape g, float *__restrict__ buf) {
+    const long long per_frame = (long long)g.px * g.pzh;          // float2 of one padded frame
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= per_frame) return;
+    const long long f = blockIdx.y;
+    const int row = (int)(idx / g.pzh), j = (int)(idx - (long long)row * g.pzh);
+    const int ix = min(max(row - g.ox, 0), g.nx - 1);
+    const int p0 = 2 * j;
+    float2 v = make_float2(0.f, 0.f);
+    if (p0 < g.pz) {                                               // pz is even: p0 + 1 < pz as well
+        const float *src = T + (f * g.nx + ix) * (long long)g.nz;
+        v.x = src[min(max(p0 - g.oz, 0), g.nz - 1)];
+        v.y = src[min(max(p0 + 1 - g.oz, 0), g.nz - 1)];
+    }
+    reinterpret_cast<float2 *>(buf)[f * per_frame + idx] = v;
+}
+
+__device__ inline float gain(double tx, double tz) { return 1.0f / (float)(tx + tz); }
+
+__global__ __launch_bounds__(TPB) void k_filter(float2 *__restrict__ spec, Shape g, const double *__restrict__ tx, const double *__restrict__ tz,
+                                                int per_row) {
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= (long long)g.px * per_row) return;
+    const long long f = blockIdx.y;
+    const int kx = (int)(idx / per_row), t = (int)(idx - (long long)kx * per_row);
+    const long long row0 = (f * g.px + kx) * (long long)g.pzh;    // the row's first coefficient
+    const int c0 = 2 * t - (int)(row0 & 1);                       // row0 + c0 is even: 16-byte aligned
+    const double ax = tx[kx];
+    if (c0 >= 0 && c0 + 1 < g.pzh) {
+        float4 *p = reinterpret_cast<float4 *>(spec + row0 + c0);
+        float4 v = *p;
+        const float h0 = gain(ax, tz[c0]), h1 = gain(ax, tz[c0 + 1]);
+        v.x *= h0, v.y *= h0, v.z *= h1, v.w *= h1;
+        *p = v;
+        return;
+    }
+    for (int c = max(c0, 0); c < min(c0 + 2, g.pzh); ++c) {
+        float2 v = spec[row0 + c];
+        const float h = gain(ax, tz[c]);
+        v.x *= h, v.y *= h;
+        spec[row0 + c] = v;
+    }
+}
+
+__device__ inline float finish(float r, int minus_log, float min_ratio) { return minus_log ? -logf(fmaxf(r, min_ratio)) : r; }
+
+// VW 4: nz % 4 == 0 and out 16-byte aligned.  EVEN: oz is even (the float2 loads are aligned).
+template <int VW, bool EVEN>
+__global__ __launch_bounds__(TPB) void k_crop(const float *__restrict__ buf, Shape g, int minus_log, float min_ratio, float *__restrict__ out) {
+    const int nzv = g.nz / VW;
+    const long long per_frame = (long long)g.nx * nzv;
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= per_frame) return;
+    const long long f = blockIdx.y;
+    const int ix = (int)(idx / nzv), iz = (int)(idx - (long long)ix * nzv) * VW;
+    const float *src = buf + ((f * g.px + g.ox + ix) * (long long)(2 * g.pzh) + g.oz + iz);
+    if (VW == 4) {
+        float4 v;
+        if (EVEN) {
+            const float2 a = reinterpret_cast<const float2 *>(src)[0], b = reinterpret_cast<const float2 *>(src)[1];
+            v = make_float4(a.x, a.y, b.x, b.y);
+        } else {
+            v = make_float4(src[0], src[1], src[2], src[3]);
+        }
+        v.x = finish(v.x, minus_log, min_ratio);
+        v.y = finish(v.y, minus_log, min_ratio);
+        v.z = finish(v.z, minus_log, min_ratio);
+        v.w = finish(v.w, minus_log, min_ratio);
+        reinterpret_cast<float4 *>(out)[f * per_frame + idx] = v;
+    } else {
+        out[f * per_frame + idx] = finish(src[0], minus_log, min_ratio);
+    }
+}
+
+__global__ __launch_bounds__(TPB) void k_log(const float *in, float *out, size_t n4, size_t count, float min_ratio) {
+    const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (i < n4) {
+        float4 v = reinterpret_cast<const float4 *>(in)[i];
+        v.x = finish(v.x, 1, min_ratio);
+        v.y = finish(v.y, 1, min_ratio);
+        v.z = finish(v.z, 1, min_ratio);
+        v.w = finish(v.w, 1, min_ratio);
+        reinterpret_cast<float4 *>(out)[i] = v;
+    } else {
+        const size_t j = 4 * n4 + (i - n4);
+        if (j < count) out[j] = finish(in[j], 1, min_ratio);
+    }
+}
+
+struct Plan {
+    hipfftHandle r2c = 0, c2r = 0;
+    size_t work_bytes = 0;       // the larger of the two
+};
+
+}  // namespace
+
+struct tomo_phase {
+    int device = 0;
+    std::string err;
+    std::map<std::tuple<int, int, int>, Plan> plans;
+    std::map<std::tuple<int, int, int>, int> lowered;   // (px, pz, first batch) -> the batch a too large work area lowered it to
+    void *work = nullptr;
+    size_t work_cap = 0;
+    double *tables = nullptr;    // tx[px], tz[pzh]
+    size_t tables_cap = 0;
+    std::vector<double> host_tables;
+    hipEvent_t ev[TOMO_PHASE_MS_N + 1] = {};
+    double t_plan = 0.0;
+};
+
+namespace {
+
+int fail(tomo_phase *h, int code, const std::string &msg) {
+    if (h) h->err = msg; else g_err = msg;
+    return code;
+}
+
+#define HIPCHK(h, call)                                                                                               \
+    do {                                                                                                              \
+        hipError_t e_ = (call);                                                                                       \
+        if (e_ != hipSuccess) return fail(h, TOMO_PHASE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+#define FFTCHK(h, call)                                                                                                               \
+    do {                                                                                                                              \
+        hipfftResult r_ = (call);                                                                                                     \
+        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_PHASE_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
+    } while (0)
+#define CHK(expr)                             \
+    do {                                      \
+        int rc_ = (expr);                     \
+        if (rc_ != TOMO_PHASE_OK) return rc_; \
+    } while (0)
+
+// The smallest even 2^i 3^j 5^k >= want (want >= 1); 0 if there is none up to TOMO_PHASE_MAX_P.
+int fast_even(long long want) {
+    int best = 0;
+    for (long long p5 = 1; p5 <= TOMO_PHASE_MAX_P; p5 *= 5)
+        for (long long p3 = p5; p3 <= TOMO_PHASE_MAX_P; p3 *= 3)
+            for (long long p = 2 * p3; p <= TOMO_PHASE_MAX_P; p *= 2)
+                if (p >= want && (best == 0 || p < best)) best = (int)p;
+    return best;
+}
+
+int padded(tomo_phase *h, int n, int m, int *out) {
+    if (n < 1 || m < 0) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase: an axis needs n >= 1 values and a pad >= 0");
+    const int p = fast_even((long long)n + 2LL * m);
+    if (!p)
+        return fail(h, TOMO_PHASE_ERR_UNSUPPORTED, "tomo_phase: the padded axis (" + std::to_string(n) + " + 2 x " + std::to_string(m) +
+                                                       ") would be longer than " + std::to_string(TOMO_PHASE_MAX_P) + "; nothing was written");
+    *out = p;
+    return TOMO_PHASE_OK;
+}
+
+size_t frame_bytes(int px, int pz) { return sizeof(float) * (size_t)px * (size_t)(2 * (pz / 2 + 1)); }
+
+// The frames of a batch when the work area is work_per_frame bytes a frame.
+int batch_for(int n, int px, int pz, size_t budget, size_t work_per_frame) {
+    const size_t fb = frame_bytes(px, pz);
+    long long b = n;
+    if (budget) b = std::min<long long>(b, (long long)(budget / (fb + work_per_frame)));
+    b = std::min<long long>(b, MAX_BATCH);
+    b = std::min<long long>(b, MAX_BATCH_FLOATS / (long long)(fb / sizeof(float)));
+    return (int)std::max<long long>(b, 1);
+}
+
+int get_plan(tomo_phase *h, int px, int pz, int b, Plan **out) {
+    auto key = std::make_tuple(px, pz, b);
+    auto it = h->plans.find(key);
+    if (it != h->plans.end()) {
+        *out = &it->second;
+        return TOMO_PHASE_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    Plan p;
+    int n[2] = {px, pz};
+    hipfftHandle *hs[2] = {&p.r2c, &p.c2r};
+    const hipfftType types[2] = {HIPFFT_R2C, HIPFFT_C2R};
+    for (int i = 0; i < 2; ++i) {
+        size_t ws = 0;
+        hipfftResult r = hipfftCreate(hs[i]);
+        if (r == HIPFFT_SUCCESS) r = hipfftSetAutoAllocation(*hs[i], 0);
+        if (r == HIPFFT_SUCCESS) r = hipfftMakePlanMany(*hs[i], 2, n, nullptr, 1, 0, nullptr, 1, 0, types[i], b, &ws);
+        if (r != HIPFFT_SUCCESS) {
+            if (p.r2c) hipfftDestroy(p.r2c);
+            if (p.c2r) hipfftDestroy(p.c2r);
+            return fail(h, TOMO_PHASE_ERR_FFT, "hipfft plan (" + std::to_string(px) + " x " + std::to_string(pz) + ", batch " + std::to_string(b) +
+                                                   "): hipfft error " + std::to_string((int)r));
+        }
+        p.work_bytes = std::max(p.work_bytes, ws);
+    }
+    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out = &(h->plans[key] = p);
+    return TOMO_PHASE_OK;
+}
+
+void drop_plan(tomo_phase *h, int px, int pz, int b) {
+    auto it = h->plans.find(std::make_tuple(px, pz, b));
+    if (it == h->plans.end()) return;
+    hipfftDestroy(it->second.r2c);
+    hipfftDestroy(it->second.c2r);
+    h->plans.erase(it);
+}
+
+// The shared work area, grown (never shrunk) on demand.  Only called while nothing of this handle is in flight.
+int grow_work(tomo_phase *h, size_t bytes) {
+    if (h->work_cap >= bytes) return TOMO_PHASE_OK;
+    if (h->work) {
+        HIPCHK(h, hipFree(h->work));
+        h->work = nullptr;
+        h->work_cap = 0;
+    }
+    HIPCHK(h, hipMalloc(&h->work, bytes));
+    h->work_cap = bytes;
+    return TOMO_PHASE_OK;
+}
+
+inline dim3 grid(long long per_frame, int b) { return dim3((unsigned)((per_frame + TPB - 1) / TPB), (unsigned)b); }
+
+int launch_log(tomo_phase *h, hipStream_t st, const float *d_in, float *d_out, size_t count, float min_ratio) {
+    const bool v4 = ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) == 0;
+    const size_t n4 = v4 ? count / 4 : 0, threads = n4 + (count - 4 * n4);
+    const size_t blocks = (threads + TPB - 1) / TPB;
+    if (blocks >= (1ull << 31)) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_minus_log: too many values");
+    hipLaunchKernelGGL(k_log, dim3((unsigned)blocks), dim3(TPB), 0, st, d_in, d_out, n4, count, min_ratio);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PHASE_OK;
+}
+
+// One batch of b frames, enqueued on st.  ms: NULL or the five pass times to add to (synchronises).
+int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, Plan *plan, int b, const float *d_in, float *d_out, float *buf, int minus_log,
+              float min_ratio, float *ms) {
+    const double *tx = h->tables, *tz = h->tables + g.px;
+    const int per_row = (g.pzh + 1) / 2 + 1;
+    int e = 0;
+    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    hipLaunchKernelGGL(k_pad, grid((long long)g.px * g.pzh, b), dim3(TPB), 0, st, d_in, g, buf);
+    HIPCHK(h, hipGetLastError());
+    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    FFTCHK(h, hipfftSetStream(plan->r2c, st));
+    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->r2c, h->work));
+    FFTCHK(h, hipfftExecR2C(plan->r2c, (hipfftReal *)buf, (hipfftComplex *)buf));
+    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    hipLaunchKernelGGL(k_filter, grid((long long)g.px * per_row, b), dim3(TPB), 0, st, (float2 *)buf, g, tx, tz, per_row);
+    HIPCHK(h, hipGetLastError());
+    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    FFTCHK(h, hipfftSetStream(plan->c2r, st));
+    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->c2r, h->work));
+    FFTCHK(h, hipfftExecC2R(plan->c2r, (hipfftComplex *)buf, (hipfftReal *)buf));
+    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    const bool v4 = g.nz % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+    const dim3 gr = grid((long long)g.nx * (v4 ? g.nz / 4 : g.nz), b);
+    if (v4 && g.oz % 2 == 0)
+        hipLaunchKernelGGL((k_crop<4, true>), gr, dim3(TPB), 0, st, (const float *)buf, g, minus_log, min_ratio, d_out);
+    else if (v4)
+        hipLaunchKernelGGL((k_crop<4, false>), gr, dim3(TPB), 0, st, (const float *)buf, g, minus_log, min_ratio, d_out);
+    else
+        hipLaunchKernelGGL((k_crop<1, false>), gr, dim3(TPB), 0, st, (const float *)buf, g, minus_log, min_ratio, d_out);
+    HIPCHK(h, hipGetLastError());
+    if (ms) {
+        HIPCHK(h, hipEventRecord(h->ev[e], st));
+        HIPCHK(h, hipEventSynchronize(h->ev[e]));
+        for (int p = 0; p < TOMO_PHASE_MS_N; ++p) {
+            float t = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&t, h->ev[p], h->ev[p + 1]));
+            ms[p] += t;
+        }
+    }
+    return TOMO_PHASE_OK;
+}
+
+int retrieve(tomo_phase *h, hipStream_t st, const Shape &g, int n, double a, const float *d_in, float *d_out, int minus_log, float min_ratio,
+             size_t budget, float *ms, float **spec) {
+    // tables, scaled by Px Pz so that the kernel's quotient carries the transforms' normalisation
+    const double N = (double)g.px * (double)g.pz;
+    h->host_tables.resize((size_t)g.px + g.pzh);
+    for (int k = 0; k < g.px; ++k) {
+        const double f = (double)(k <= g.px / 2 ? k : k - g.px) / (double)g.px;
+        h->host_tables[k] = N * (a * (f * f));
+    }
+    for (int k = 0; k < g.pzh; ++k) {
+        const double f = (double)k / (double)g.pz;
+        h->host_tables[g.px + k] = N * (1.0 + a * (f * f));
+    }
+    const size_t tb = sizeof(double) * h->host_tables.size();
+    if (h->tables_cap < tb) {
+        if (h->tables) HIPCHK(h, hipFree(h->tables));
+        h->tables = nullptr;
+        h->tables_cap = 0;
+        HIPCHK(h, hipMalloc((void **)&h->tables, tb));
+        h->tables_cap = tb;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->tables, h->host_tables.data(), tb, hipMemcpyHostToDevice, st));
+
+    // the batch: first with the work area taken to be one spectrum a frame, then with what the plan asks for
+    const size_t fb = frame_bytes(g.px, g.pz);
+    int b = batch_for(n, g.px, g.pz, budget, fb);
+    Plan *plan = nullptr;
+    const auto first = std::make_tuple(g.px, g.pz, b);
+    const auto low = h->lowered.find(first);
+    if (budget && low != h->lowered.end() && (size_t)low->second * fb < budget) b = low->second;     // decided by an earlier call
+    CHK(get_plan(h, g.px, g.pz, b, &plan));
+    if (budget && b > 1 && (size_t)b * fb + plan->work_bytes > budget) {
+        const size_t per = (plan->work_bytes + b - 1) / b;
+        const int b2 = std::min(b - 1, batch_for(n, g.px, g.pz, budget, per));
+        drop_plan(h, g.px, g.pz, b);
+        h->lowered[first] = b2;                       // so that the next call does not make the large plan again
+        b = b2;
+        CHK(get_plan(h, g.px, g.pz, b, &plan));
+    }
+    Plan *tail = nullptr;
+    if (n % b) CHK(get_plan(h, g.px, g.pz, n % b, &tail));
+    CHK(grow_work(h, std::max(plan->work_bytes, tail ? tail->work_bytes : (size_t)0)));
+    HIPCHK(h, hipMalloc((void **)spec, (size_t)b * fb));
+    const size_t in_frame = (size_t)g.nx * g.nz;
+    for (int f0 = 0; f0 < n; f0 += b) {
+        const int bb = std::min(b, n - f0);
+        CHK(run_batch(h, st, g, bb == b ? plan : tail, bb, d_in + f0 * in_frame, d_out + f0 * in_frame, *spec, minus_log, min_ratio, ms));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    return TOMO_PHASE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TOMO_API int tomo_phase_abi_version(void) { return 1; }
+
+TOMO_API int tomo_phase_create(int device, tomo_phase **out) {
+    if (!out) return fail(nullptr, TOMO_PHASE_ERR_ARG, "NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_PHASE_ERR_NODEV, "no HIP device");
+    if (device < 0 || device >= n) return fail(nullptr, TOMO_PHASE_ERR_ARG, "device out of range");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipSetDevice failed");
+    tomo_phase *h = new tomo_phase();
+    h->device = device;
+    for (hipEvent_t &e : h->ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            for (hipEvent_t &d : h->ev)
+                if (d) (void)hipEventDestroy(d);
+            delete h;
+            return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipEventCreate failed");
+        }
+    *out = h;
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API int tomo_phase_destroy(tomo_phase *h) {
+    if (!h) return TOMO_PHASE_OK;
+    (void)hipSetDevice(h->device);
+    for (auto &kv : h->plans) {
+        hipfftDestroy(kv.second.r2c);
+        hipfftDestroy(kv.second.c2r);
+    }
+    if (h->work) (void)hipFree(h->work);
+    if (h->tables) (void)hipFree(h->tables);
+    for (hipEvent_t &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete h;
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API const char *tomo_phase_last_error(tomo_phase *h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+TOMO_API int tomo_phase_padded_length(int n, int m, int *out) {
+    if (!out) return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_padded_length: NULL");
+    return padded(nullptr, n, m, out);
+}
+
+TOMO_API int tomo_phase_batch(int n, int px, int pz, size_t max_scratch_bytes, int *batch) {
+    if (!batch) return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_batch: NULL");
+    if (n < 1 || px < 2 || pz < 2 || px > TOMO_PHASE_MAX_P || pz > TOMO_PHASE_MAX_P || pz % 2)
+        return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_batch: bad shape");
+    *batch = batch_for(n, px, pz, max_scratch_bytes, frame_bytes(px, pz));
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API int tomo_phase_device_bytes(tomo_phase *h, int64_t *bytes) {
+    if (!h || !bytes) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_device_bytes: NULL");
+    *bytes = (int64_t)(h->work_cap + h->tables_cap);
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API int tomo_phase_mem_info(tomo_phase *h, size_t *free_bytes, size_t *total_bytes) {
+    if (!h || !free_bytes || !total_bytes) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_mem_info: NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemGetInfo(free_bytes, total_bytes));
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API int tomo_phase_plan_seconds(tomo_phase *h, double *seconds) {
+    if (!h || !seconds) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_plan_seconds: NULL");
+    *seconds = h->t_plan;
+    return TOMO_PHASE_OK;
+}
+
+TOMO_API int tomo_phase_minus_log(tomo_phase *h, void *stream, const float *d_in, float *d_out, size_t count, float min_ratio) {
+    if (!h) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_minus_log: NULL handle");
+    if (!(min_ratio > 0.f) || !std::isfinite(min_ratio)) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_minus_log: min_ratio must be finite and > 0");
+    if (count == 0) return TOMO_PHASE_OK;
+    if (!d_in || !d_out) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_minus_log: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_log(h, reinterpret_cast<hipStream_t>(stream), d_in, d_out, count, min_ratio);
+}
+
+TOMO_API int tomo_phase_retrieve(tomo_phase *h, void *stream, const float *d_in, float *d_out, int n, int nx, int nz, double strength,
+                                 int pad_x, int pad_z, int minus_log, float min_ratio, size_t max_scratch_bytes, float *pass_ms) {
+    if (!h) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: NULL handle");
+    if (n < 1 || nx < 1 || nz < 1) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: bad shape");
+    if (!(strength >= 0.0 && strength <= TOMO_PHASE_MAX_STRENGTH))
+        return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: the strength must be in 0 ... 1e12");
+    if (!(min_ratio > 0.f) || !std::isfinite(min_ratio)) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: min_ratio must be finite and > 0");
+    if (!d_in || !d_out) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: NULL pointer");
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)
+        return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: misaligned pointer");
+    if (pad_x < 0 || pad_z < 0) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_retrieve: pad must be >= 0");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (pass_ms)
+        for (int p = 0; p < TOMO_PHASE_MS_N; ++p) pass_ms[p] = 0.f;
+    const size_t count = (size_t)n * nx * nz;
+    if (strength == 0.0) {                        // the identity: nothing is padded or transformed, so no limit on the axes applies
+        HIPCHK(h, hipSetDevice(h->device));
+        if (minus_log) return launch_log(h, st, d_in, d_out, count, min_ratio);
+        if (d_out != d_in) HIPCHK(h, hipMemcpyAsync(d_out, d_in, sizeof(float) * count, hipMemcpyDeviceToDevice, st));
+        return TOMO_PHASE_OK;
+    }
+    Shape g{};
+    g.nx = nx, g.nz = nz;
+    CHK(padded(h, nx, pad_x, &g.px));
+    CHK(padded(h, nz, pad_z, &g.pz));
+    g.ox = (g.px - nx) / 2, g.oz = (g.pz - nz) / 2, g.pzh = g.pz / 2 + 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    float *spec = nullptr;
+    const int rc = retrieve(h, st, g, n, strength, d_in, d_out, minus_log ? 1 : 0, min_ratio, max_scratch_bytes, pass_ms, &spec);
+    if (spec) {
+        if (rc) (void)hipStreamSynchronize(st);   // nothing may still be using the buffer
+        const hipError_t e = hipFree(spec);
+        if (!rc && e != hipSuccess) return fail(h, TOMO_PHASE_ERR_HIP, std::string("hipFree of the spectrum: ") + hipGetErrorString(e));
+    }
+    return rc;
+}
+
+}  // extern "C"

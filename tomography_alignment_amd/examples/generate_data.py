@@ -10,20 +10,42 @@ With raw=True (--raw) the file also holds what a detector gives for the same pro
 (uint16 [n_proj][z][x]), `flats` and `darks` (uint16 stacks of frames) and `mu`, the attenuation per unit of `projections` (the line
 integral the counts encode is mu * projections).  counts = Poisson(I0 * gain * exp(-mu p)) + dark, with a per-pixel gain shared by flats
 and projections, and a few detector columns whose gain in the projections differs from the flats' by a few percent: the stripes.
+With propagate=A (--propagate A) the noiseless transmission exp(-mu p) is first carried over a propagation distance: the forward model
+of preprocess.retrieve_phase with strength A (pixels^2), which puts a bright/dark fringe pair on every edge.
 
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --out data.npz
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --out raw.npz
+    python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --propagate 25 --out fringed.npz
 """
 import argparse
 
 import numpy as np
 
+from .. import preprocess
 from ..utilities import generate_phantom, geometry, projection_operators
 
 
-def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03):
+def tie_propagate(T, strength):
+    """The intensity a propagation distance downstream of the transmission T [..., nx, nz], float64: the transport-of-intensity
+    equation linearised for a homogeneous object, i.e. preprocess.retrieve_phase's padding (edge replication to the same lengths) with
+    the spectrum DIVIDED by H = 1 / (1 + strength ((kx/Px)^2 + (kz/Pz)^2)).  tests/phase_model.propagate is the same model, which the
+    package cannot import; tests/test_phase.py holds the two together."""
+    T = np.asarray(T, np.float64)
+    nx, nz = T.shape[-2:]
+    (_, px), (_, pz) = preprocess.phase_padding(nx, strength), preprocess.phase_padding(nz, strength)
+    ox, oz = (px - nx) // 2, (pz - nz) // 2
+    P = np.pad(T, [(0, 0)] * (T.ndim - 2) + [(ox, px - nx - ox), (oz, pz - nz - oz)], mode="edge")
+    k2 = np.fft.fftfreq(px)[:, None] ** 2 + np.fft.rfftfreq(pz)[None, :] ** 2
+    r = np.fft.irfft2(np.fft.rfft2(P) * (1.0 + strength * k2), s=(px, pz))
+    return r[..., ox:ox + nx, oz:oz + nz]
+
+
+def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03, propagate=None):
     """Detector frames of the projections proj [n_proj][nx][nz]: dict(counts, flats, darks, mu) (module docstring).  mu defaults to
-    4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor."""
+    4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor.  propagate: the strength of the propagation
+    applied to the noiseless transmission (None or 0: none, and the frames are those of earlier versions for the same seed)."""
+    if propagate is not None and not (np.isfinite(propagate) and propagate >= 0):
+        raise ValueError("propagate must be a finite strength >= 0 or None, got %r" % (propagate,))
     rng = np.random.default_rng(seed)
     n_proj, nx, nz = proj.shape
     mu = 4.0 / nx if mu is None else float(mu)
@@ -37,14 +59,17 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
     def frames(mean):
         return np.clip(rng.poisson(mean) + np.rint(dark_mean), 0, 65535).astype(np.uint16)
 
-    att = np.exp(-mu * np.asarray(proj, np.float64)).transpose(0, 2, 1)   # [n][z][x]
+    att = np.exp(-mu * np.asarray(proj, np.float64))
+    if propagate:
+        att = np.clip(tie_propagate(att, float(propagate)), 0.0, None)
+    att = att.transpose(0, 2, 1)                                          # [n][z][x]
     counts = frames(i0 * gain * drift * att)
     flats = frames(np.broadcast_to(i0 * gain, (n_flat, nz, nx)))
     darks = np.clip(rng.poisson(np.broadcast_to(np.maximum(dark_mean, 0), (n_dark, nz, nx))), 0, 65535).astype(np.uint16)
     return dict(counts=counts, flats=flats, darks=darks, mu=np.float64(mu))
 
 
-def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False):
+def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None):
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
     shepp = generate_phantom.shepp3d(nx)
@@ -62,7 +87,7 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False):
     proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
     d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
     if raw:
-        d.update(make_raw(proj, seed=None if seed is None else seed + 1))   # a generator of its own: the other keys do not change
+        d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate))   # a generator of its own: the other keys do not change
     return d
 
 
@@ -73,8 +98,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="data.npz")
     ap.add_argument("--raw", action="store_true", help="also write detector counts, flats and darks (examples/preprocess.py)")
+    ap.add_argument("--propagate", type=float, default=None, metavar="A",
+                    help="with --raw: propagate the transmission with strength A pixels^2 before the counts are drawn (phase-contrast fringes)")
     a = ap.parse_args()
-    d = make(a.size, a.angles, a.seed, raw=a.raw)
+    if a.propagate is not None and not a.raw:
+        ap.error("--propagate needs --raw")
+    d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

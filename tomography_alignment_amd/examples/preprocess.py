@@ -6,12 +6,19 @@ on the GPU (tomography_alignment_amd.preprocess).  The input is a file with `cou
 projection) divides the line integrals back into the phantom's units.  Every other key (phi, alpha, beta, xyz, phantom, ...) is carried
 through; counts, flats and darks are dropped.
 
+For data recorded with a propagation distance, `phase` (--phase-strength A, or --pixel-size, --dist, --energy and --delta-beta) puts
+Paganin's single-distance phase retrieval between the flat-field division and the -log: normalize(minus_log=False) -> retrieve_phase
+-> stripe removal.  Without it the calls and the result are what they were before the option existed.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
     python -m tomography_alignment_amd.examples.generate_data --raw --out raw.npz
     python -m tomography_alignment_amd.examples.preprocess raw.npz --out data.npz
     python -m tomography_alignment_amd.examples.align_rigid data.npz --init fbp
+
+    python -m tomography_alignment_amd.examples.generate_data --raw --propagate 25 --out fringed.npz
+    python -m tomography_alignment_amd.examples.preprocess fringed.npz --phase-strength 25 --out data.npz
 """
 import argparse
 
@@ -20,11 +27,17 @@ import numpy as np
 from .. import _lib, preprocess
 
 RAW_KEYS = ("counts", "flats", "darks", "mu")
+PHASE_KEYS = ("strength", "pixel_size", "dist", "energy", "wavelength", "delta_beta", "pad", "min_ratio", "max_scratch_bytes")
 
 
-def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False):
+def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
-    removal, or 0 / None to skip it."""
+    removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
+    energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log."""
+    if phase is not None:
+        unknown = sorted(set(phase) - set(PHASE_KEYS))
+        if unknown:
+            raise ValueError("preprocess: phase has unknown keys %s (known: %s)" % (unknown, ", ".join(PHASE_KEYS)))
     for k in ("counts", "flats", "darks"):
         if k not in data:
             raise ValueError("preprocess: the data has no %r (write it with generate_data --raw)" % k)
@@ -35,8 +48,13 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     d_frames = sino = None
     try:
         d_frames = ctx.to_device(counts, counts.dtype if counts.dtype in (np.uint16, np.float32) else np.float32)     # uploaded once
-        sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop)
+        if phase is None:
+            sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop)
+        else:
+            sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop, minus_log=False)
         d_frames.free()
+        if phase is not None:
+            p.retrieve_phase(sino, out=sino, **phase)                                                     # in place; applies the -log
         if stripe_size:
             p.remove_stripe_sorting(sino, size=stripe_size, out=sino)                                    # in place, on the device
         proj = sino.download()
@@ -52,7 +70,8 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     out = {k: v for k, v in data.items() if k not in RAW_KEYS}
     out["projections"] = proj
     if verbose:
-        print("preprocess: %s counts -> projections %s (stripe window %s)" % (counts.shape, proj.shape, stripe_size or "off"))
+        print("preprocess: %s counts -> projections %s (stripe window %s, phase retrieval %s)"
+              % (counts.shape, proj.shape, stripe_size or "off", phase if phase is not None else "off"))
     return out
 
 
@@ -64,7 +83,25 @@ def parse_args(argv=None):
     ap.add_argument("--method", choices=("mean", "median"), default="mean", help="how flats and darks are reduced")
     ap.add_argument("--cutoff", type=float, default=None, help="upper bound of the flat-field ratio before the log")
     ap.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Z0", "Z1", "X0", "X1"), help="detector window")
+    ap.add_argument("--phase-strength", type=float, default=None, metavar="A",
+                    help="Paganin phase retrieval with strength A = pi lambda z (delta/beta) / pixel_size^2 in pixels^2")
+    ap.add_argument("--pixel-size", type=float, default=None, help="metres; with --dist and --energy, instead of --phase-strength")
+    ap.add_argument("--dist", type=float, default=None, help="propagation distance, metres")
+    ap.add_argument("--energy", type=float, default=None, help="keV")
+    ap.add_argument("--delta-beta", type=float, default=None, help="delta / beta of the material (default 1000)")
     a = ap.parse_args(argv)
+    physical = {k: getattr(a, k) for k in ("pixel_size", "dist", "energy", "delta_beta") if getattr(a, k) is not None}
+    a.phase = None
+    if a.phase_strength is not None:
+        if physical:
+            ap.error("give --phase-strength or --pixel-size / --dist / --energy / --delta-beta, not both")
+        if not a.phase_strength >= 0:
+            ap.error("--phase-strength must be >= 0")
+        a.phase = dict(strength=a.phase_strength)
+    elif physical:
+        if not all(k in physical for k in ("pixel_size", "dist", "energy")):
+            ap.error("the phase retrieval needs --pixel-size, --dist and --energy (or --phase-strength)")
+        a.phase = physical
     if a.stripe_size and (a.stripe_size < 3 or a.stripe_size % 2 == 0):
         ap.error("--stripe-size must be 0 or an odd number >= 3")
     if a.crop is not None:
@@ -74,7 +111,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True)
+    d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 

@@ -36,14 +36,28 @@ Limits: n_proj <= 8192 (one 64-bit key per angle in LDS; more raises PrepUnsuppo
 permutation) fits max_scratch_bytes (default 2 GiB); the result does not depend on the chunking.  The removal needs every angle of a
 column, so it runs on the full stack on one GPU; ranks that each hold a block of angles can still call normalize on their own frames.
 
+Phase retrieval (retrieve_phase; libtomo_phase.so, include/tomo_phase.h): Paganin's single-distance filter, the step between the
+flat-field division and the -log for data recorded with a propagation distance:
+    normalize(minus_log=False) --retrieve_phase--> line integrals --remove_stripe_sorting--> ...
+One parameter, the strength a = pi lambda z (delta/beta) / pixel_size^2 in pixels^2 (paganin_strength).  Per projection: pad by edge
+replication to (Px, Pz), P the smallest even 2^i 3^j 5^k >= n_axis + 2 m with the data at offset (P - n_axis) // 2, m = pad if given,
+else min(n_axis, ceil(8 sqrt(a) / (2 pi))); multiply the 2-D spectrum by H = 1 / (1 + a ((kx/Px)^2 + (kz/Pz)^2)); transform back, crop,
+and out = -log(fmax(r, min_ratio)) if minus_log (the default), else r.  a = 0 is the identity, applied as such: retrieve_phase(p, 0) is
+bit for bit minus_log(p).  Limits: a padded axis of at most 8192 values where a > 0 (PrepUnsupported before any launch otherwise), 0 <= a <= 1e12,
+float32 transforms.  Frames are filtered in batches whose spectra and hipFFT work area fit max_scratch_bytes (default 2 GiB; 0: no limit;
+never fewer than one frame); every frame is transformed on its own, so the result does not depend on the batch.  The work is per
+projection: a rank that holds a block of angles filters its own block.
+
 The kernels live in their own library, like libtomo_fbp.so and libtomo_xcorr.so, so that the projector's sources and the kernel-source
 hash that keys the committed PMC counters do not change.  Host arrays and _lib.DeviceArrays are both accepted; a device input gives a
 device output, with no host round trip, and every temporary buffer is freed before a call returns.  Arguments are checked (ValueError)
 before anything is uploaded or launched.
 """
+import math
+
 import numpy as np
 
-from . import _lib, _prep_lib
+from . import _lib, _phase_lib, _prep_lib
 from ._prep_lib import PrepUnsupported  # noqa: F401  (re-exported)
 
 DEFAULT_SCRATCH_BYTES = 2 << 30
@@ -87,6 +101,73 @@ def _crop(crop, rows, cols):
     return tuple(out)
 
 
+WAVELENGTH_KEV_M = 1.2398419843320026e-9      # h c in keV m: lambda = WAVELENGTH_KEV_M / E_keV
+
+
+def paganin_strength(pixel_size, dist, energy=None, wavelength=None, delta_beta=1000.0):
+    """The dimensionless strength a = pi lambda z (delta/beta) / pixel_size^2 (pixels^2) of retrieve_phase.  pixel_size and dist (the
+    propagation distance z) in metres; give exactly one of energy (keV) and wavelength (metres)."""
+    if (energy is None) == (wavelength is None):
+        raise ValueError("give exactly one of energy (keV) and wavelength (m)")
+    vals = dict(pixel_size=pixel_size, dist=dist, delta_beta=delta_beta)
+    vals["wavelength" if energy is None else "energy"] = wavelength if energy is None else energy
+    for k, v in vals.items():
+        v = vals[k] = float(v)
+        positive = k not in ("dist", "delta_beta")
+        if not math.isfinite(v) or v < 0 or (positive and v == 0):
+            raise ValueError("%s must be finite and %s, got %r" % (k, "> 0" if positive else ">= 0", v))
+    lam = WAVELENGTH_KEV_M / vals["energy"] if wavelength is None else vals["wavelength"]
+    return math.pi * lam * vals["dist"] * vals["delta_beta"] / vals["pixel_size"] ** 2
+
+
+def _fast_even(want):
+    """The smallest even 2^i 3^j 5^k >= want."""
+    p = max(2, int(want) + (int(want) & 1))
+    while True:
+        q = p
+        for f in (2, 3, 5):
+            while q % f == 0:
+                q //= f
+        if q == 1:
+            return p
+        p += 2
+
+
+def phase_padding(n_axis, strength, pad=None):
+    """(m, P): the padding on each side and the padded length of an axis of n_axis values (module docstring)."""
+    m = int(pad) if pad is not None else min(int(n_axis), int(math.ceil(8.0 * math.sqrt(strength) / (2.0 * math.pi))))
+    return m, _fast_even(int(n_axis) + 2 * m)
+
+
+def _check_out(proj, out, size):
+    if out is None:
+        return
+    if not (_is_dev(out) and out.dtype == np.float32 and out.size == size):
+        raise ValueError("out must be a float32 DeviceArray of %d values" % size)
+    if not _is_dev(proj):
+        raise ValueError("out needs a DeviceArray input (a host input gives a host result)")
+    if out.ptr.value != proj.ptr.value:
+        a0, b0 = proj.ptr.value, out.ptr.value
+        if a0 < b0 + out.nbytes and b0 < a0 + proj.nbytes:
+            raise ValueError("out must be proj itself or not overlap it")
+
+
+def _check_min_ratio(min_ratio):
+    try:
+        ok = bool(np.isfinite(min_ratio) and min_ratio > 0 and np.float32(min_ratio) > 0)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("min_ratio must be finite and > 0 (in float32), got %r" % (min_ratio,))
+
+
+def _float32_stack(proj):
+    shape, dtype = _shape_dtype(proj, "proj", (3,))
+    if dtype != np.float32:
+        raise ValueError("proj must be float32, got %s" % dtype)
+    return shape
+
+
 class Preprocessor(object):
     """One libtomo_prep handle and its scratch, reused across calls.  ctx: the _lib.Context whose device and stream the work uses (work
     is enqueued on ctx.stream(), in order with the projector work that follows); default the context of the first DeviceArray passed in,
@@ -96,6 +177,7 @@ class Preprocessor(object):
         self.ctx = ctx
         self.handle = None
         self._own_ctx = None
+        self._phase = None
 
     def _ready(self, like):
         if self.ctx is None:
@@ -107,6 +189,9 @@ class Preprocessor(object):
             self.handle = _prep_lib.PrepHandle(self.ctx.device)
 
     def close(self):
+        if self._phase is not None:
+            self._phase.close()
+            self._phase = None
         if self.handle is not None:
             self.handle.close()
             self.handle = None
@@ -248,6 +333,95 @@ class Preprocessor(object):
         return (result, ms) if timed else result
 
 
+    def _ready_phase(self, like):
+        if self.ctx is None:
+            if _is_dev(like):
+                self.ctx = like.ctx
+            else:
+                self.ctx = self._own_ctx = _lib.Context()
+        if self._phase is None:
+            self._phase = _phase_lib.PhaseHandle(self.ctx.device)      # made on first use: loads hipFFT
+
+    def _run_phase(self, proj, shape, out, call):
+        """Upload / allocate as the conventions say, run call(d_in, d_out), download a host input's result."""
+        self._ready_phase(proj)
+        temps = []
+        try:
+            d_in = self._upload(proj, temps)
+            res = out
+            if res is None:
+                res = d_in if not _is_dev(proj) else self.ctx.empty(shape, np.float32)     # a host input's upload is ours: in place
+            try:
+                extra = call(d_in, res)
+            except Exception:
+                if out is None and res is not d_in:
+                    res.free()
+                raise
+            return (res if _is_dev(proj) else res.download()), extra
+        finally:
+            self._free(temps)
+
+    def retrieve_phase(self, proj, strength=None, *, pixel_size=None, dist=None, energy=None, wavelength=None, delta_beta=None, pad=None,
+                       minus_log=True, min_ratio=1e-6, out=None, max_scratch_bytes=None, timed=False):
+        """Paganin phase retrieval of the transmission proj [n_proj][nx][nz] (float32; module docstring), what
+        normalize(minus_log=False) returns.  Give either `strength` (pixels^2) or the physical quantities of paganin_strength
+        (pixel_size, dist, one of energy / wavelength, optionally delta_beta), not both.  pad: values of edge replication on each side
+        of both axes (default from the strength).  Host in: an ndarray out.  Device in: the result goes to `out` (a float32 DeviceArray
+        of the same size; `out=proj` works in place) or a new DeviceArray.  Limits: a padded axis of at most 8192 values where
+        strength > 0 (PrepUnsupported), 0 <= strength <= 1e12.  timed=True (benchmarks): returns (result, (pad_ms, r2c_ms, filter_ms, c2r_ms,
+        crop_ms))."""
+        shape = _float32_stack(proj)
+        n, nx, nz = shape
+        physical = dict(pixel_size=pixel_size, dist=dist, energy=energy, wavelength=wavelength, delta_beta=delta_beta)
+        given = [k for k, v in physical.items() if v is not None]
+        if strength is not None:
+            if given:
+                raise ValueError("give either strength or the physical quantities (%s), not both" % ", ".join(given))
+            try:
+                strength = float(strength)
+            except (TypeError, ValueError):
+                raise ValueError("strength must be a number, got %r" % (strength,))
+        else:
+            if pixel_size is None or dist is None:
+                raise ValueError("give strength, or pixel_size, dist and one of energy / wavelength")
+            strength = paganin_strength(pixel_size, dist, energy=energy, wavelength=wavelength,
+                                        delta_beta=1000.0 if delta_beta is None else delta_beta)
+        if not (math.isfinite(strength) and 0 <= strength <= _phase_lib.MAX_STRENGTH):
+            raise ValueError("strength must be in 0 ... 1e12 pixels^2, got %r" % (strength,))
+        if pad is not None:
+            if isinstance(pad, (bool, np.bool_)) or not isinstance(pad, (int, np.integer)) or pad < 0:
+                raise ValueError("pad must be an integer >= 0 or None, got %r" % (pad,))
+        _check_min_ratio(min_ratio)
+        budget = DEFAULT_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+        if budget < 0:
+            raise ValueError("max_scratch_bytes must be >= 0 (0: no limit)")
+        _check_out(proj, out, n * nx * nz)
+        (mx, px), (mz, pz) = phase_padding(nx, strength, pad), phase_padding(nz, strength, pad)
+        if strength > 0 and max(px, pz) > _phase_lib.MAX_P:             # a = 0 pads and transforms nothing
+            raise PrepUnsupported("retrieve_phase: the padded frame %d x %d (pad %d, %d) exceeds %d values on an axis"
+                                  % (px, pz, mx, mz, _phase_lib.MAX_P))
+
+        def call(d_in, d_out):
+            return self._phase.retrieve(self.ctx.stream(), d_in.ptr, d_out.ptr, n, nx, nz, strength, mx, mz, minus_log, min_ratio, budget,
+                                        timed)
+
+        result, ms = self._run_phase(proj, shape, out, call)
+        return (result, ms) if timed else result
+
+    def minus_log(self, proj, min_ratio=1e-6, out=None):
+        """-log(fmax(proj, min_ratio)) of a float32 stack [n_proj][nx][nz]: the last step of retrieve_phase alone, for pipelines that
+        skip the retrieval.  Host in: an ndarray out; device in: `out` (may be proj) or a new DeviceArray."""
+        shape = _float32_stack(proj)
+        _check_min_ratio(min_ratio)
+        size = int(np.prod(shape))
+        _check_out(proj, out, size)
+
+        def call(d_in, d_out):
+            self._phase.minus_log(self.ctx.stream(), d_in.ptr, d_out.ptr, size, min_ratio)
+
+        return self._run_phase(proj, shape, out, call)[0]
+
+
 def reference_frames(flats, darks, method="mean", ctx=None):
     """(flat, dark) float32 reference frames: Preprocessor.reference_frames on a handle of its own."""
     p = Preprocessor(ctx)
@@ -271,5 +445,23 @@ def remove_stripe_sorting(proj, size=21, ctx=None, out=None, max_scratch_bytes=N
     p = Preprocessor(ctx)
     try:
         return p.remove_stripe_sorting(proj, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
+    finally:
+        p.close()
+
+
+def retrieve_phase(proj, strength=None, ctx=None, **kwargs):
+    """Paganin phase retrieval: Preprocessor.retrieve_phase (same keywords) on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.retrieve_phase(proj, strength, **kwargs)
+    finally:
+        p.close()
+
+
+def minus_log(proj, min_ratio=1e-6, ctx=None, out=None):
+    """-log(fmax(proj, min_ratio)): Preprocessor.minus_log on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.minus_log(proj, min_ratio=min_ratio, out=out)
     finally:
         p.close()
