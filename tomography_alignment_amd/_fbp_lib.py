@@ -5,11 +5,11 @@ As with _lib, there is NO CPU fallback: if the library or a device is missing, e
 """
 import ctypes
 import os
-import threading
 
 import numpy as np
 
-from ._lib import TomoError
+from . import _binding
+from ._binding import Handle, TomoError, _ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_FBP_LIB") or os.path.join(_HERE, "libtomo_fbp.so")   # override: development builds only
@@ -30,9 +30,6 @@ SIGNATURES = {
     "tomo_fbp_filter": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_dp]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
 
 class FbpUnsupported(TomoError):
     """The detector is wider than the kernel supports (ndx > 4096)."""
@@ -40,65 +37,16 @@ class FbpUnsupported(TomoError):
 
 def load():
     """Load libtomo_fbp.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_fbp.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/fbp`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_fbp.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_fbp_abi_version() != 1:
-                raise TomoError("libtomo_fbp.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("fbp", LIB_PATH, SIGNATURES)
 
 
-class FbpHandle(object):
+class FbpHandle(Handle):
     """One tomo_fbp handle: a device, the twiddle and response tables and the device copy of the scales.  A context manager; close()
     frees everything.  device: the tomo context's (ctx.device) -- the filter runs on that context's stream."""
 
-    def __init__(self, device=0):
-        self._h = None
-        self.lib = load()
-        h = _c_vp()
-        self._check(self.lib.tomo_fbp_create(int(device), ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device)
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            msg = (self.lib.tomo_fbp_last_error(self._h if h == "self" else h) or b"").decode(errors="replace")
-            raise (FbpUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_fbp error %d: %s" % (rc, msg))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("fbp handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_fbp_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+    NAME = "fbp"
+    load = staticmethod(load)
+    ERRORS = {ERR_UNSUPPORTED: FbpUnsupported}
 
     def set_response(self, ndx, table):
         """The response H[0 .. Npad/2] (recon/fbp.py::filter_response) for detector width ndx."""
@@ -108,11 +56,5 @@ class FbpHandle(object):
     def filter(self, stream, d_in, d_out, n_proj, ndx, ndz, scales):
         """Enqueue q = scales * filter(p) on `stream`; d_in / d_out device pointers (may be equal)."""
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(scales, np.float64), (int(n_proj),)))
-        self._check(self.lib.tomo_fbp_filter(self.handle, _c_vp(int(stream) if stream else 0), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx),
+        self._check(self.lib.tomo_fbp_filter(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx),
                                              int(ndz), s.ctypes.data_as(_c_dp)))
-
-
-def _ptr(p):
-    if isinstance(p, ctypes.c_void_p):
-        return p
-    return _c_vp(int(p)) if p else None

@@ -6,11 +6,11 @@ As with _lib, there is NO CPU fallback: if the library or a device is missing, e
 """
 import ctypes
 import os
-import threading
 
 import numpy as np
 
-from ._lib import TomoError
+from . import _binding
+from ._binding import Handle, TomoError, _ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_FSC_LIB") or os.path.join(_HERE, "libtomo_fsc.so")   # override: development builds only
@@ -42,9 +42,6 @@ SIGNATURES = {
     "tomo_fsc_take_rows": (_c_int, [_c_vp, _c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
 
 class FscUnsupported(TomoError):
     """A shape the library does not handle: an axis shorter than 2 or longer than MAX_N, more than MAX_PLANES planes."""
@@ -52,81 +49,29 @@ class FscUnsupported(TomoError):
 
 def load():
     """Load libtomo_fsc.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_fsc.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/fsc`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_fsc.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_fsc_abi_version() != 1:
-                raise TomoError("libtomo_fsc.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("fsc", LIB_PATH, SIGNATURES)
 
 
-def _raise(lib, rc, h):
-    msg = (lib.tomo_fsc_last_error(h) or b"").decode(errors="replace")
-    raise (FscUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_fsc error %d: %s" % (rc, msg))
+ERRORS = {ERR_UNSUPPORTED: FscUnsupported}
 
 
 def n_shells(ndim, nb, nx, ny, nz):
     """min(n) / 2 + 1 of a shape the library handles; FscUnsupported otherwise.  Needs no device."""
     lib = load()
     n = _c_int(0)
-    rc = lib.tomo_fsc_n_shells(int(ndim), int(nb), int(nx), int(ny), int(nz), ctypes.byref(n))
-    if rc != 0:
-        _raise(lib, rc, None)
+    _binding.check(lib, "fsc", lib.tomo_fsc_n_shells(int(ndim), int(nb), int(nx), int(ny), int(nz), ctypes.byref(n)), None, ERRORS)
     return n.value
 
 
-class FscHandle(object):
+class FscHandle(Handle):
     """One tomo_fsc handle: a device, the hipFFT plans and spectrum buffers of the shapes it has seen, and the last error.  A context
     manager.  device: the tomo context's (ctx.device) -- every call is enqueued on the stream it is given, in practice that context's,
     and only fetch() synchronises."""
 
-    def __init__(self, device=0):
-        self._h = None
-        self.lib = load()
-        h = _c_vp()
-        self._check(self.lib.tomo_fsc_create(int(device), ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device)
-        self.shape = None
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            _raise(self.lib, rc, self._h if h == "self" else h)
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("fsc handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_fsc_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+    NAME = "fsc"
+    load = staticmethod(load)
+    ERRORS = ERRORS
+    shape = None              # (ndim, nb, nx, ny, nz) of the last set_shape
 
     def set_shape(self, ndim, nb, nx, ny, nz):
         """The shape of the calls that follow; returns the number of shells.  Raises FscUnsupported before anything is launched."""
@@ -165,9 +110,3 @@ class FscHandle(object):
     def take_rows(self, stream, d_src, row_elems, first, step, count, d_dst):
         self._check(self.lib.tomo_fsc_take_rows(self.handle, _ptr(stream), _ptr(d_src), int(row_elems), int(first), int(step), int(count),
                                                 _ptr(d_dst)))
-
-
-def _ptr(p):
-    if isinstance(p, ctypes.c_void_p):
-        return p
-    return _c_vp(int(p)) if p else None

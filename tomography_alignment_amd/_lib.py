@@ -7,10 +7,16 @@ utilities/ray_voxel_utilities.py:3.)
 """
 import ctypes
 import os
-import threading
 import weakref
 
 import numpy as np
+
+try:
+    from . import _binding
+except ImportError:      # package directory itself on sys.path (reference-style `import utilities` layout)
+    import _binding
+
+TomoError = _binding.TomoError      # the class every error of the package derives from; defined there so that the side bindings share it
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Multi-process GPU work on this platform needs dmabuf IPC (RCCL's peer buffers); the variable is read when the HIP runtime
@@ -126,34 +132,9 @@ SIGNATURES = {
     "tomo_profile_get": (ctypes.c_int, [_c_vp, ctypes.c_char_p, ctypes.POINTER(_c_i64), _c_dp]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
-
-class TomoError(RuntimeError):
-    pass
-
-
 def load():
     """Load libtomo_hip.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_hip.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                "or `make -C tomography_alignment_amd/csrc`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_abi_version() != 1:
-                raise TomoError("libtomo_hip.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("hip", LIB_PATH, SIGNATURES, prefix="tomo", build_dir="csrc")
 
 
 def _ptr(x):

@@ -7,10 +7,10 @@ As with _lib, there is NO CPU fallback: if the library or a device is missing, e
 """
 import ctypes
 import os
-import threading
 
-from ._lib import TomoError
-from ._prep_lib import PrepUnsupported
+from . import _binding
+from ._binding import Handle, _ptr
+from ._prep_lib import PrepUnsupported      # preprocess has one Unsupported class, whichever of its two libraries refuses
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_PHASE_LIB") or os.path.join(_HERE, "libtomo_phase.so")   # override: development builds only
@@ -42,35 +42,13 @@ SIGNATURES = {
     "tomo_phase_minus_log": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_float]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
 
 def load():
     """Load libtomo_phase.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_phase.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/phase`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_phase.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_phase_abi_version() != 1:
-                raise TomoError("libtomo_phase.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("phase", LIB_PATH, SIGNATURES)
 
 
-def _raise(lib, rc, h):
-    msg = (lib.tomo_phase_last_error(h) or b"").decode(errors="replace")
-    raise (PrepUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_phase error %d: %s" % (rc, msg))
+ERRORS = {ERR_UNSUPPORTED: PrepUnsupported}
 
 
 def padded_length(n, m):
@@ -78,9 +56,7 @@ def padded_length(n, m):
     no device."""
     lib = load()
     p = _c_int(0)
-    rc = lib.tomo_phase_padded_length(int(n), int(m), ctypes.byref(p))
-    if rc != 0:
-        _raise(lib, rc, None)
+    _binding.check(lib, "phase", lib.tomo_phase_padded_length(int(n), int(m), ctypes.byref(p)), None, ERRORS)
     return p.value
 
 
@@ -88,51 +64,18 @@ def batch(n, px, pz, max_scratch_bytes=0):
     """The frames per batch tomo_phase_retrieve starts from for this padded shape and scratch budget (0: no limit).  Needs no device."""
     lib = load()
     b = _c_int(0)
-    rc = lib.tomo_phase_batch(int(n), int(px), int(pz), int(max_scratch_bytes), ctypes.byref(b))
-    if rc != 0:
-        _raise(lib, rc, None)
+    _binding.check(lib, "phase", lib.tomo_phase_batch(int(n), int(px), int(pz), int(max_scratch_bytes), ctypes.byref(b)), None, ERRORS)
     return b.value
 
 
-class PhaseHandle(object):
+class PhaseHandle(Handle):
     """One tomo_phase handle: a device, the hipFFT plans of the padded shapes it has seen with their shared work area, and the last
     error.  A context manager; close() frees everything.  device: the tomo context's (ctx.device) -- every call is enqueued on the
     stream it is given, in practice that context's; retrieve() waits for it."""
 
-    def __init__(self, device=0):
-        self._h = None
-        self.lib = load()
-        h = _c_vp()
-        self._check(self.lib.tomo_phase_create(int(device), ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device)
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            _raise(self.lib, rc, self._h if h == "self" else h)
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("phase handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_phase_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+    NAME = "phase"
+    load = staticmethod(load)
+    ERRORS = ERRORS
 
     def device_bytes(self):
         n = ctypes.c_int64(0)
@@ -161,9 +104,3 @@ class PhaseHandle(object):
 
     def minus_log(self, stream, d_in, d_out, count, min_ratio=1e-6):
         self._check(self.lib.tomo_phase_minus_log(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(count), float(min_ratio)))
-
-
-def _ptr(p):
-    if isinstance(p, ctypes.c_void_p):
-        return p
-    return _c_vp(int(p)) if p else None

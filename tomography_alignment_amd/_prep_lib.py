@@ -5,9 +5,9 @@ As with _lib, there is NO CPU fallback: if the library or a device is missing, e
 """
 import ctypes
 import os
-import threading
 
-from ._lib import TomoError
+from . import _binding
+from ._binding import Handle, TomoError, _ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_PREP_LIB") or os.path.join(_HERE, "libtomo_prep.so")   # override: development builds only
@@ -37,9 +37,6 @@ SIGNATURES = {
     "tomo_prep_stripe_sorting": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, ctypes.c_size_t, _c_fp]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
 
 class PrepUnsupported(TomoError):
     """A shape the kernels do not support: more than 8192 angles for the stripe removal, or a median over more than 64 frames."""
@@ -47,74 +44,24 @@ class PrepUnsupported(TomoError):
 
 def load():
     """Load libtomo_prep.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_prep.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/prep`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_prep.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_prep_abi_version() != 1:
-                raise TomoError("libtomo_prep.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("prep", LIB_PATH, SIGNATURES)
 
 
 def stripe_chunk(n_proj, ndx, ndz, max_scratch_bytes=0):
     """The z rows per chunk tomo_prep_stripe_sorting uses for this shape and scratch budget (0: no limit)."""
     lib = load()
     zc = _c_int(0)
-    if lib.tomo_prep_stripe_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)) != 0:
-        raise TomoError("tomo_prep_stripe_chunk: %s" % (lib.tomo_prep_last_error(None) or b"").decode(errors="replace"))
+    _binding.check(lib, "prep", lib.tomo_prep_stripe_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)))
     return zc.value
 
 
-class PrepHandle(object):
+class PrepHandle(Handle):
     """One tomo_prep handle: a device, the stripe scratch and the last error.  A context manager; close() frees everything.  device: the
     tomo context's (ctx.device) -- every call is enqueued on the stream it is given, in practice that context's."""
 
-    def __init__(self, device=0):
-        self._h = None
-        self.lib = load()
-        h = _c_vp()
-        self._check(self.lib.tomo_prep_create(int(device), ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device)
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            msg = (self.lib.tomo_prep_last_error(self._h if h == "self" else h) or b"").decode(errors="replace")
-            raise (PrepUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_prep error %d: %s" % (rc, msg))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("prep handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_prep_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+    NAME = "prep"
+    load = staticmethod(load)
+    ERRORS = {ERR_UNSUPPORTED: PrepUnsupported}
 
     def reference(self, stream, d_frames, dtype, n, rows, cols, method, d_out):
         self._check(self.lib.tomo_prep_reference(self.handle, _ptr(stream), _ptr(d_frames), int(dtype), int(n), int(rows), int(cols),
@@ -133,9 +80,3 @@ class PrepHandle(object):
         self._check(self.lib.tomo_prep_stripe_sorting(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
                                                       int(size), int(max_scratch_bytes), ms))
         return tuple(ms) if timed else None
-
-
-def _ptr(p):
-    if isinstance(p, ctypes.c_void_p):
-        return p
-    return _c_vp(int(p)) if p else None

@@ -6,9 +6,9 @@ As with _lib, there is NO CPU fallback: if the library or a device is missing, e
 """
 import ctypes
 import os
-import threading
 
-from ._lib import TomoError
+from . import _binding
+from ._binding import Handle, TomoError, _ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_PYR_LIB") or os.path.join(_HERE, "libtomo_pyr.so")   # override: development builds only
@@ -32,9 +32,6 @@ SIGNATURES = {
     "tomo_pyr_prolong_vol": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_float, _c_vp]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
 
 class PyrUnsupported(TomoError):
     """A binning the kernels do not support: a factor other than 2, 4 or 8, or an extent the factor does not divide."""
@@ -42,65 +39,16 @@ class PyrUnsupported(TomoError):
 
 def load():
     """Load libtomo_pyr.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_pyr.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/pyr`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_pyr.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_pyr_abi_version() != 1:
-                raise TomoError("libtomo_pyr.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("pyr", LIB_PATH, SIGNATURES)
 
 
-class PyrHandle(object):
+class PyrHandle(Handle):
     """One tomo_pyr handle: a device and the last error.  A context manager.  device: the tomo context's (ctx.device) -- every call is
     enqueued on the stream it is given, in practice that context's, and none synchronises."""
 
-    def __init__(self, device=0):
-        self._h = None
-        self.lib = load()
-        h = _c_vp()
-        self._check(self.lib.tomo_pyr_create(int(device), ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device)
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            msg = (self.lib.tomo_pyr_last_error(self._h if h == "self" else h) or b"").decode(errors="replace")
-            raise (PyrUnsupported if rc == ERR_UNSUPPORTED else TomoError)("libtomo_pyr error %d: %s" % (rc, msg))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("pyr handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_pyr_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+    NAME = "pyr"
+    load = staticmethod(load)
+    ERRORS = {ERR_UNSUPPORTED: PyrUnsupported}
 
     def bin_sino(self, stream, d_src, n, nx, nz, f, scale, d_dst):
         self._check(self.lib.tomo_pyr_bin_sino(self.handle, _ptr(stream), _ptr(d_src), int(n), int(nx), int(nz), int(f), float(scale),
@@ -113,9 +61,3 @@ class PyrHandle(object):
     def prolong_vol(self, stream, d_src, nx, ny, nz, scale, d_dst):
         self._check(self.lib.tomo_pyr_prolong_vol(self.handle, _ptr(stream), _ptr(d_src), int(nx), int(ny), int(nz), float(scale),
                                                   _ptr(d_dst)))
-
-
-def _ptr(p):
-    if isinstance(p, ctypes.c_void_p):
-        return p
-    return _c_vp(int(p)) if p else None

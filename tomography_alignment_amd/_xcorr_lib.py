@@ -5,11 +5,11 @@ As with _lib, there is NO CPU fallback: if the library, hipFFT or a device is mi
 """
 import ctypes
 import os
-import threading
 
 import numpy as np
 
-from ._lib import TomoError
+from . import _binding
+from ._binding import Handle, TomoError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOMO_XCORR_LIB") or os.path.join(_HERE, "libtomo_xcorr.so")   # override: development builds only
@@ -34,30 +34,10 @@ SIGNATURES = {
 }
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}
 
-_lib = None
-_lock = threading.Lock()
-
 
 def load():
     """Load libtomo_xcorr.so and bind every symbol; raises TomoError (never falls back) on failure."""
-    global _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise TomoError("libtomo_xcorr.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C tomography_alignment_amd/csrc/xcorr`; there is no CPU fallback" % LIB_PATH)
-            try:
-                lib = ctypes.CDLL(LIB_PATH)      # OSError here when hipFFT cannot be found
-            except OSError as e:
-                raise TomoError("cannot load %s: %s" % (LIB_PATH, e))
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)          # AttributeError if include/tomo_xcorr.h and the .so disagree
-                fn.restype = res
-                fn.argtypes = args
-            if lib.tomo_xcorr_abi_version() != 1:
-                raise TomoError("libtomo_xcorr.so ABI version mismatch")
-            _lib = lib
-    return _lib
+    return _binding.load("xcorr", LIB_PATH, SIGNATURES)
 
 
 def device_bytes():
@@ -69,52 +49,24 @@ def _dp(a):
     return a.ctypes.data_as(_c_dp)
 
 
-class XcorrHandle(object):
+class XcorrHandle(Handle):
     """One tomo_xcorr handle: a device, a stream, the hipFFT plans and the work buffers, all kept between calls on it.  A context
     manager; close() frees everything.  The device is chosen as _lib.Context chooses it: LOCAL_RANK modulo the device count."""
 
+    NAME = "xcorr"
+    load = staticmethod(load)
+
     def __init__(self, device=None):
         self._h = None
-        self.lib = load()
+        lib = load()
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0"))
         n = ctypes.c_int(0)
-        rc = self.lib.tomo_xcorr_device_count(ctypes.byref(n))
+        rc = lib.tomo_xcorr_device_count(ctypes.byref(n))
         if rc != 0 or n.value < 1:
             raise TomoError("no HIP device visible (rc=%d: %s); this package has no CPU path"
-                            % (rc, (self.lib.tomo_xcorr_last_error(None) or b"").decode()))
-        h = _c_vp()
-        self._check(self.lib.tomo_xcorr_create(int(device) % n.value, ctypes.byref(h)), None)
-        self._h = h
-        self.device = int(device) % n.value
-
-    def _check(self, rc, h="self"):
-        if rc != 0:
-            msg = self.lib.tomo_xcorr_last_error(self._h if h == "self" else h) or b""
-            raise TomoError("libtomo_xcorr error %d: %s" % (rc, msg.decode(errors="replace")))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TomoError("xcorr handle closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self.lib.tomo_xcorr_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+                            % (rc, (lib.tomo_xcorr_last_error(None) or b"").decode()))
+        Handle.__init__(self, int(device) % n.value)
 
     def last_timing(self):
         """{'plan_s', 'upload_ms', 'steps_ms', 'download_ms'} of the last chain / batch call on this handle (device events; plan

@@ -19,6 +19,11 @@
 
 #include "../../../include/tomo_fbp.h"
 
+namespace {
+constexpr int SIDE_ERR_ARG = TOMO_FBP_ERR_ARG, SIDE_ERR_HIP = TOMO_FBP_ERR_HIP, SIDE_ERR_NODEV = TOMO_FBP_ERR_NODEV;
+}
+#include "../tomo_side_host.h"
+
 #ifndef TOMO_FBP_LDS_KIB
 #define TOMO_FBP_LDS_KIB 64     // LDS of the complex data per work-group (before padding): 64 -> two work-groups per CU
 #endif
@@ -27,7 +32,6 @@ namespace {
 
 constexpr double PI = 3.141592653589793238462643383279502884;
 constexpr int MIN_LOGN = 6;                      // Npad 64 .. 8192 (launch<6..13>)
-thread_local std::string g_err;
 
 template <int LOGN>
 struct Cfg {
@@ -216,17 +220,6 @@ struct tomo_fbp {
 
 namespace {
 
-int fail(tomo_fbp *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess) return fail(h, TOMO_FBP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 int log2_npad(int ndx) {
     int l = MIN_LOGN;
     while ((1 << l) < 2 * ndx) ++l;
@@ -265,11 +258,7 @@ extern "C" {
 TOMO_API int tomo_fbp_abi_version(void) { return 1; }
 
 TOMO_API int tomo_fbp_create(int device, tomo_fbp **out) {
-    if (!out) return fail(nullptr, TOMO_FBP_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_FBP_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_FBP_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     tomo_fbp *h = new tomo_fbp();
     h->device = device;
     hipError_t e = hipSetDevice(device);
@@ -295,7 +284,7 @@ TOMO_API int tomo_fbp_destroy(tomo_fbp *h) {
     return TOMO_FBP_OK;
 }
 
-TOMO_API const char *tomo_fbp_last_error(tomo_fbp *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_fbp_last_error(tomo_fbp *h) { return last_error(h); }
 
 TOMO_API int tomo_fbp_set_response(tomo_fbp *h, int ndx, const double *table) {
     if (!h || !table) return fail(h, TOMO_FBP_ERR_ARG, "tomo_fbp_set_response: NULL");

@@ -26,8 +26,11 @@
 #include "../../../include/tomo_fsc.h"
 
 namespace {
+constexpr int SIDE_ERR_ARG = TOMO_FSC_ERR_ARG, SIDE_ERR_HIP = TOMO_FSC_ERR_HIP, SIDE_ERR_NODEV = TOMO_FSC_ERR_NODEV, SIDE_ERR_FFT = TOMO_FSC_ERR_FFT;
+}
+#include "../tomo_side_host.h"
 
-thread_local std::string g_err;
+namespace {
 
 constexpr int TPB = 256;             // threads per block of the streaming kernels
 constexpr int SUM_G = 256;           // blocks per plane of the first-stage sums (== TPB: the second stage is one partial per thread)
@@ -257,11 +260,6 @@ struct Plan {
     size_t work_bytes = 0;
 };
 
-struct Buf {
-    void *p = nullptr;
-    size_t n = 0;
-};
-
 }  // namespace
 
 struct tomo_fsc {
@@ -276,40 +274,6 @@ struct tomo_fsc {
 };
 
 namespace {
-
-int fail(tomo_fsc *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                              \
-    do {                                                                                                             \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) return fail(h, TOMO_FSC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
-    } while (0)
-#define FFTCHK(h, call)                                                                                                             \
-    do {                                                                                                                            \
-        hipfftResult r_ = (call);                                                                                                   \
-        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_FSC_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
-#define CHK(expr)                           \
-    do {                                    \
-        int rc_ = (expr);                   \
-        if (rc_ != TOMO_FSC_OK) return rc_; \
-    } while (0)
-
-// A work buffer of at least `bytes`, grown (never shrunk) on demand.
-int grow(tomo_fsc *h, Buf &b, size_t bytes) {
-    if (b.n >= bytes) return TOMO_FSC_OK;
-    if (b.p) {
-        HIPCHK(h, hipFree(b.p));
-        b.p = nullptr;
-        b.n = 0;
-    }
-    HIPCHK(h, hipMalloc(&b.p, bytes));
-    b.n = bytes;
-    return TOMO_FSC_OK;
-}
 
 int make_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, int nz, Shape *out) {
     if (ndim != 2 && ndim != 3) return fail(h, TOMO_FSC_ERR_UNSUPPORTED, "tomo_fsc: ndim must be 2 or 3, got " + std::to_string(ndim));
@@ -401,11 +365,7 @@ extern "C" {
 TOMO_API int tomo_fsc_abi_version(void) { return 1; }
 
 TOMO_API int tomo_fsc_create(int device, tomo_fsc **out) {
-    if (!out) return fail(nullptr, TOMO_FSC_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_FSC_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_FSC_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     tomo_fsc *h = new tomo_fsc();
     h->device = device;
     *out = h;
@@ -425,7 +385,7 @@ TOMO_API int tomo_fsc_destroy(tomo_fsc *h) {
     return TOMO_FSC_OK;
 }
 
-TOMO_API const char *tomo_fsc_last_error(tomo_fsc *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_fsc_last_error(tomo_fsc *h) { return last_error(h); }
 
 TOMO_API int tomo_fsc_n_shells(int ndim, int nb, int nx, int ny, int nz, int *n_shells) {
     if (!n_shells) return fail(nullptr, TOMO_FSC_ERR_ARG, "tomo_fsc_n_shells: NULL");

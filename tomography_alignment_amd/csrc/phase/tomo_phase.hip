@@ -30,8 +30,11 @@
 #include "../../../include/tomo_phase.h"
 
 namespace {
+constexpr int SIDE_ERR_ARG = TOMO_PHASE_ERR_ARG, SIDE_ERR_HIP = TOMO_PHASE_ERR_HIP, SIDE_ERR_NODEV = TOMO_PHASE_ERR_NODEV, SIDE_ERR_FFT = TOMO_PHASE_ERR_FFT;
+}
+#include "../tomo_side_host.h"
 
-thread_local std::string g_err;
+namespace {
 
 constexpr int TPB = 256;
 constexpr int MAX_BATCH = 65535;                 // frames of one batch: the y extent of a grid
@@ -147,37 +150,14 @@ struct tomo_phase {
     std::string err;
     std::map<std::tuple<int, int, int>, Plan> plans;
     std::map<std::tuple<int, int, int>, int> lowered;   // (px, pz, first batch) -> the batch a too large work area lowered it to
-    void *work = nullptr;
-    size_t work_cap = 0;
-    double *tables = nullptr;    // tx[px], tz[pzh]
-    size_t tables_cap = 0;
+    Buf work;                    // the hipFFT work area all plans share
+    Buf tables;                  // double tx[px], tz[pzh]
     std::vector<double> host_tables;
     hipEvent_t ev[TOMO_PHASE_MS_N + 1] = {};
     double t_plan = 0.0;
 };
 
 namespace {
-
-int fail(tomo_phase *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess) return fail(h, TOMO_PHASE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define FFTCHK(h, call)                                                                                                               \
-    do {                                                                                                                              \
-        hipfftResult r_ = (call);                                                                                                     \
-        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_PHASE_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
-#define CHK(expr)                             \
-    do {                                      \
-        int rc_ = (expr);                     \
-        if (rc_ != TOMO_PHASE_OK) return rc_; \
-    } while (0)
 
 // The smallest even 2^i 3^j 5^k >= want (want >= 1); 0 if there is none up to TOMO_PHASE_MAX_P.
 int fast_even(long long want) {
@@ -249,19 +229,6 @@ void drop_plan(tomo_phase *h, int px, int pz, int b) {
     h->plans.erase(it);
 }
 
-// The shared work area, grown (never shrunk) on demand.  Only called while nothing of this handle is in flight.
-int grow_work(tomo_phase *h, size_t bytes) {
-    if (h->work_cap >= bytes) return TOMO_PHASE_OK;
-    if (h->work) {
-        HIPCHK(h, hipFree(h->work));
-        h->work = nullptr;
-        h->work_cap = 0;
-    }
-    HIPCHK(h, hipMalloc(&h->work, bytes));
-    h->work_cap = bytes;
-    return TOMO_PHASE_OK;
-}
-
 inline dim3 grid(long long per_frame, int b) { return dim3((unsigned)((per_frame + TPB - 1) / TPB), (unsigned)b); }
 
 int launch_log(tomo_phase *h, hipStream_t st, const float *d_in, float *d_out, size_t count, float min_ratio) {
@@ -277,7 +244,7 @@ int launch_log(tomo_phase *h, hipStream_t st, const float *d_in, float *d_out, s
 // One batch of b frames, enqueued on st.  ms: NULL or the five pass times to add to (synchronises).
 int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, Plan *plan, int b, const float *d_in, float *d_out, float *buf, int minus_log,
               float min_ratio, float *ms) {
-    const double *tx = h->tables, *tz = h->tables + g.px;
+    const double *tx = static_cast<const double *>(h->tables.p), *tz = tx + g.px;
     const int per_row = (g.pzh + 1) / 2 + 1;
     int e = 0;
     if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
@@ -285,14 +252,14 @@ int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, Plan *plan, int b, 
     HIPCHK(h, hipGetLastError());
     if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
     FFTCHK(h, hipfftSetStream(plan->r2c, st));
-    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->r2c, h->work));
+    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->r2c, h->work.p));
     FFTCHK(h, hipfftExecR2C(plan->r2c, (hipfftReal *)buf, (hipfftComplex *)buf));
     if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
     hipLaunchKernelGGL(k_filter, grid((long long)g.px * per_row, b), dim3(TPB), 0, st, (float2 *)buf, g, tx, tz, per_row);
     HIPCHK(h, hipGetLastError());
     if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
     FFTCHK(h, hipfftSetStream(plan->c2r, st));
-    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->c2r, h->work));
+    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->c2r, h->work.p));
     FFTCHK(h, hipfftExecC2R(plan->c2r, (hipfftComplex *)buf, (hipfftReal *)buf));
     if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
     const bool v4 = g.nz % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
@@ -330,14 +297,8 @@ int retrieve(tomo_phase *h, hipStream_t st, const Shape &g, int n, double a, con
         h->host_tables[g.px + k] = N * (1.0 + a * (f * f));
     }
     const size_t tb = sizeof(double) * h->host_tables.size();
-    if (h->tables_cap < tb) {
-        if (h->tables) HIPCHK(h, hipFree(h->tables));
-        h->tables = nullptr;
-        h->tables_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->tables, tb));
-        h->tables_cap = tb;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->tables, h->host_tables.data(), tb, hipMemcpyHostToDevice, st));
+    CHK(grow(h, h->tables, tb));
+    HIPCHK(h, hipMemcpyAsync(h->tables.p, h->host_tables.data(), tb, hipMemcpyHostToDevice, st));
 
     // the batch: first with the work area taken to be one spectrum a frame, then with what the plan asks for
     const size_t fb = frame_bytes(g.px, g.pz);
@@ -357,7 +318,8 @@ int retrieve(tomo_phase *h, hipStream_t st, const Shape &g, int n, double a, con
     }
     Plan *tail = nullptr;
     if (n % b) CHK(get_plan(h, g.px, g.pz, n % b, &tail));
-    CHK(grow_work(h, std::max(plan->work_bytes, tail ? tail->work_bytes : (size_t)0)));
+    // retrieve() waits for the stream before it returns, so nothing of this handle is in flight when the work area is replaced
+    CHK(grow(h, h->work, std::max(plan->work_bytes, tail ? tail->work_bytes : (size_t)0)));
     HIPCHK(h, hipMalloc((void **)spec, (size_t)b * fb));
     const size_t in_frame = (size_t)g.nx * g.nz;
     for (int f0 = 0; f0 < n; f0 += b) {
@@ -375,11 +337,7 @@ extern "C" {
 TOMO_API int tomo_phase_abi_version(void) { return 1; }
 
 TOMO_API int tomo_phase_create(int device, tomo_phase **out) {
-    if (!out) return fail(nullptr, TOMO_PHASE_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_PHASE_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_PHASE_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipSetDevice failed");
     tomo_phase *h = new tomo_phase();
     h->device = device;
@@ -401,15 +359,15 @@ TOMO_API int tomo_phase_destroy(tomo_phase *h) {
         hipfftDestroy(kv.second.r2c);
         hipfftDestroy(kv.second.c2r);
     }
-    if (h->work) (void)hipFree(h->work);
-    if (h->tables) (void)hipFree(h->tables);
+    if (h->work.p) (void)hipFree(h->work.p);
+    if (h->tables.p) (void)hipFree(h->tables.p);
     for (hipEvent_t &e : h->ev)
         if (e) (void)hipEventDestroy(e);
     delete h;
     return TOMO_PHASE_OK;
 }
 
-TOMO_API const char *tomo_phase_last_error(tomo_phase *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_phase_last_error(tomo_phase *h) { return last_error(h); }
 
 TOMO_API int tomo_phase_padded_length(int n, int m, int *out) {
     if (!out) return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_padded_length: NULL");
@@ -426,7 +384,7 @@ TOMO_API int tomo_phase_batch(int n, int px, int pz, size_t max_scratch_bytes, i
 
 TOMO_API int tomo_phase_device_bytes(tomo_phase *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_device_bytes: NULL");
-    *bytes = (int64_t)(h->work_cap + h->tables_cap);
+    *bytes = (int64_t)(h->work.n + h->tables.n);
     return TOMO_PHASE_OK;
 }
 

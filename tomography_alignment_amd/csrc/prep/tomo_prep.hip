@@ -22,8 +22,11 @@
 #include "../../../include/tomo_prep.h"
 
 namespace {
+constexpr int SIDE_ERR_ARG = TOMO_PREP_ERR_ARG, SIDE_ERR_HIP = TOMO_PREP_ERR_HIP, SIDE_ERR_NODEV = TOMO_PREP_ERR_NODEV;
+}
+#include "../tomo_side_host.h"
 
-thread_local std::string g_err;
+namespace {
 
 constexpr int SORT_KEYS = 8192;        // 64-bit keys per K1 work-group (64 KiB of LDS)
 constexpr int SCATTER_VALS = 16384;    // float32 values per K3 work-group (64 KiB of LDS)
@@ -248,8 +251,7 @@ __global__ __launch_bounds__(SCATTER_T) void k_stripe_scatter(const float *__res
 struct tomo_prep {
     int device = 0;
     std::string err;
-    void *d_scratch = nullptr;                 // stripe scratch: S, M (float32) and P (uint16) of one chunk
-    size_t scratch_cap = 0;
+    Buf scratch;                               // stripe scratch: S, M (float32) and P (uint16) of one chunk
     hipStream_t last_stream = nullptr;         // the stream the scratch was last used on
     hipEvent_t ev_done = nullptr;              // after the last use of the scratch
     hipEvent_t ev_pass[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -257,17 +259,6 @@ struct tomo_prep {
 };
 
 namespace {
-
-int fail(tomo_prep *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess) return fail(h, TOMO_PREP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
-    } while (0)
 
 template <typename K>
 int allow_lds(tomo_prep *h, K kernel) {
@@ -349,11 +340,7 @@ extern "C" {
 TOMO_API int tomo_prep_abi_version(void) { return 1; }
 
 TOMO_API int tomo_prep_create(int device, tomo_prep **out) {
-    if (!out) return fail(nullptr, TOMO_PREP_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_PREP_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_PREP_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     tomo_prep *h = new tomo_prep();
     h->device = device;
     hipError_t e = hipSetDevice(device);
@@ -371,7 +358,7 @@ TOMO_API int tomo_prep_destroy(tomo_prep *h) {
     if (!h) return TOMO_PREP_OK;
     (void)hipSetDevice(h->device);
     if (h->pending) (void)hipEventSynchronize(h->ev_done);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
+    if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     for (hipEvent_t ev : h->ev_pass)
         if (ev) (void)hipEventDestroy(ev);
@@ -379,7 +366,7 @@ TOMO_API int tomo_prep_destroy(tomo_prep *h) {
     return TOMO_PREP_OK;
 }
 
-TOMO_API const char *tomo_prep_last_error(tomo_prep *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_prep_last_error(tomo_prep *h) { return last_error(h); }
 
 TOMO_API int tomo_prep_reference(tomo_prep *h, void *stream, const void *d_frames, int dtype, int n, int rows, int cols, int method,
                                  float *d_out) {
@@ -448,17 +435,11 @@ TOMO_API int tomo_prep_stripe_sorting(tomo_prep *h, void *stream, const float *d
     const int zc = chunk_for(n_proj, ndx, ndz, max_scratch_bytes);
     const size_t nchunk = (size_t)n_proj * ndx * zc;
     const size_t need = nchunk * 10;
-    if (h->pending && (need > h->scratch_cap || st != h->last_stream)) {     // the scratch is replaced or used on another stream
+    if (h->pending && (need > h->scratch.n || st != h->last_stream)) {     // the scratch is replaced or used on another stream
         int rc = drain(h);
         if (rc) return rc;
     }
-    if (need > h->scratch_cap) {
-        if (h->d_scratch) HIPCHK(h, hipFree(h->d_scratch));
-        h->d_scratch = nullptr;
-        h->scratch_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_scratch, need));
-        h->scratch_cap = need;
-    }
+    CHK(grow(h, h->scratch, need));
     static bool attr = false;
     if (!attr) {
         int rc = allow_lds(h, k_stripe_sort);
@@ -466,7 +447,7 @@ TOMO_API int tomo_prep_stripe_sorting(tomo_prep *h, void *stream, const float *d
         if (rc) return rc;
         attr = true;
     }
-    float *S = static_cast<float *>(h->d_scratch);
+    float *S = static_cast<float *>(h->scratch.p);
     float *M = S + nchunk;
     uint16_t *P = reinterpret_cast<uint16_t *>(M + nchunk);
     const int logNp = ilog2_ceil(n_proj), Np = 1 << logNp;

@@ -15,8 +15,11 @@
 #include "../../../include/tomo_pyr.h"
 
 namespace {
+constexpr int SIDE_ERR_ARG = TOMO_PYR_ERR_ARG, SIDE_ERR_HIP = TOMO_PYR_ERR_HIP, SIDE_ERR_NODEV = TOMO_PYR_ERR_NODEV;
+}
+#include "../tomo_side_host.h"
 
-thread_local std::string g_err;
+namespace {
 
 constexpr int BIN_T = 256;
 constexpr int PRO_T = 256;
@@ -130,17 +133,6 @@ struct tomo_pyr {
 
 namespace {
 
-int fail(tomo_pyr *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                              \
-    do {                                                                                                             \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) return fail(h, TOMO_PYR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
-    } while (0)
-
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 bool overlap(const float *a, size_t na, const float *b, size_t nb) {
@@ -183,11 +175,7 @@ extern "C" {
 TOMO_API int tomo_pyr_abi_version(void) { return 1; }
 
 TOMO_API int tomo_pyr_create(int device, tomo_pyr **out) {
-    if (!out) return fail(nullptr, TOMO_PYR_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_PYR_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_PYR_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     tomo_pyr *h = new tomo_pyr();
     h->device = device;
     *out = h;
@@ -199,7 +187,7 @@ TOMO_API int tomo_pyr_destroy(tomo_pyr *h) {
     return TOMO_PYR_OK;
 }
 
-TOMO_API const char *tomo_pyr_last_error(tomo_pyr *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_pyr_last_error(tomo_pyr *h) { return last_error(h); }
 
 TOMO_API int tomo_pyr_bin_sino(tomo_pyr *h, void *stream, const float *d_src, int n, int nx, int nz, int f, float scale, float *d_dst) {
     if (!h) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_sino: NULL handle");

@@ -1,0 +1,18 @@
+# The build of one side library, libtomo_$(NAME).so (gfx950 only), from csrc/$(NAME)/tomo_$(NAME).hip: included by csrc/<name>/Makefile,
+# which sets NAME and, for a library that uses hipFFT, LIBS = $(HIPFFT).  Same compiler flags as ../Makefile.  Each is a library of its
+# own so that the projector's sources (and the kernel-source hash they define) stay as they are.
+HIPCC ?= /opt/rocm/bin/hipcc
+ARCH ?= gfx950
+HIPFFT = -L/opt/rocm/lib -lhipfft -Wl,-rpath,/opt/rocm/lib
+CXXFLAGS ?= -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -munsafe-fp-atomics -ffp-contract=fast -fno-slp-vectorize \
+            -Wall -Wno-unused-function -DTOMO_$(shell echo $(NAME) | tr a-z A-Z)_BUILD
+LDFLAGS ?= $(strip -shared $(LIBS))
+SRCS = tomo_$(NAME).hip
+HDRS = ../../../include/tomo_$(NAME).h ../tomo_side_host.h
+OUT = ../../libtomo_$(NAME).so
+all: $(OUT)
+$(OUT): $(SRCS) $(HDRS)
+	$(HIPCC) $(CXXFLAGS) $(EXTRA) $(SRCS) -o $@ $(LDFLAGS)
+clean:
+	rm -f $(OUT)
+.PHONY: all clean

@@ -16,13 +16,17 @@
 #include "../../../include/tomo_xcorr.h"
 
 namespace {
+constexpr int SIDE_ERR_ARG = TOMO_XCORR_ERR_ARG, SIDE_ERR_HIP = TOMO_XCORR_ERR_HIP, SIDE_ERR_NODEV = TOMO_XCORR_ERR_NODEV, SIDE_ERR_FFT = TOMO_XCORR_ERR_FFT;
+}
+#include "../tomo_side_host.h"
+
+namespace {
 
 constexpr int TPB = 256;        // threads per block of every kernel
 constexpr int G = 256;          // blocks of every first-stage reduction (== TPB: the second stage is one block, one partial per thread)
 constexpr double PI = 3.141592653589793238462643383279502884;
 
 std::atomic<int64_t> g_device_bytes{0};
-thread_local std::string g_err;
 
 // ---------------------------------------------------------------------------------------------------------------------- kernels
 
@@ -383,11 +387,6 @@ __global__ __launch_bounds__(TPB) void k_pcc_scalars(const double *part_src, con
 
 // ---------------------------------------------------------------------------------------------------------------------- host side
 
-struct Buf {
-    void *p = nullptr;
-    size_t n = 0;
-};
-
 }  // namespace
 
 struct tomo_xcorr {
@@ -403,43 +402,14 @@ struct tomo_xcorr {
 
 namespace {
 
-int fail(tomo_xcorr *h, int code, const std::string &msg) {
-    if (h) h->err = msg; else g_err = msg;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                                                 \
-    do {                                                                                                                \
-        hipError_t e_ = (call);                                                                                         \
-        if (e_ != hipSuccess) return fail(h, TOMO_XCORR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-#define FFTCHK(h, call)                                                                                                 \
-    do {                                                                                                                \
-        hipfftResult r_ = (call);                                                                                       \
-        if (r_ != HIPFFT_SUCCESS) return fail(h, TOMO_XCORR_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
-#define CHK(expr)                    \
-    do {                             \
-        int rc_ = (expr);            \
-        if (rc_ != TOMO_XCORR_OK) return rc_; \
-    } while (0)
-
 // A named work buffer of at least `bytes`, grown (never shrunk) on demand and counted in g_device_bytes.
 int buf(tomo_xcorr *h, const char *name, size_t bytes, void **out) {
     Buf &b = h->bufs[name];
-    if (b.n < bytes) {
-        if (b.p) {
-            HIPCHK(h, hipFree(b.p));
-            g_device_bytes -= (int64_t)b.n;
-            b.p = nullptr;
-            b.n = 0;
-        }
-        HIPCHK(h, hipMalloc(&b.p, bytes));
-        b.n = bytes;
-        g_device_bytes += (int64_t)bytes;
-    }
+    const int64_t had = (int64_t)b.n;
+    const int rc = grow(h, b, bytes);
+    g_device_bytes += (int64_t)b.n - had;       // whatever grow() freed or got, also where it failed half way
     *out = b.p;
-    return TOMO_XCORR_OK;
+    return rc;
 }
 
 template <class P>
@@ -738,11 +708,7 @@ TOMO_API int tomo_xcorr_device_count(int *n) {
 }
 
 TOMO_API int tomo_xcorr_create(int device, tomo_xcorr **out) {
-    if (!out) return fail(nullptr, TOMO_XCORR_ERR_ARG, "NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(nullptr, TOMO_XCORR_ERR_NODEV, "no HIP device");
-    if (device < 0 || device >= n) return fail(nullptr, TOMO_XCORR_ERR_ARG, "device out of range");
+    CHK(check_create(device, out));
     tomo_xcorr *h = new tomo_xcorr();
     h->device = device;
     hipError_t e = hipSetDevice(device);
@@ -774,7 +740,7 @@ TOMO_API int tomo_xcorr_destroy(tomo_xcorr *h) {
     return TOMO_XCORR_OK;
 }
 
-TOMO_API const char *tomo_xcorr_last_error(tomo_xcorr *h) { return h ? h->err.c_str() : g_err.c_str(); }
+TOMO_API const char *tomo_xcorr_last_error(tomo_xcorr *h) { return last_error(h); }
 
 TOMO_API int64_t tomo_xcorr_device_bytes(void) { return g_device_bytes.load(); }
 

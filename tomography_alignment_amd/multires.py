@@ -25,14 +25,11 @@ ValueError before the library is loaded; nothing here synchronises.
 """
 import numpy as np
 
-from . import _lib, _pyr_lib
+from . import _pyr_lib
+from ._ops import HandleOwner, _is_dev
 from ._pyr_lib import PyrUnsupported  # noqa: F401  (re-exported)
 
 FACTORS = _pyr_lib.FACTORS
-
-
-def _is_dev(a):
-    return isinstance(a, _lib.DeviceArray)
 
 
 def _shape_of(a, shape, what, ndim):
@@ -79,38 +76,13 @@ def level_geometry(n_proj, vox_shape, f=1):
     return geometry.Geometry(int(n_proj), np.array([nx // f, ny // f, nz // f]), np.ones(3), np.array([nx // f, nz // f]), np.ones(2))
 
 
-class Pyramid(object):
+class Pyramid(HandleOwner):
     """One libtomo_pyr handle reused across calls.  ctx: the _lib.Context whose device and stream the work uses (work is enqueued on
     ctx.stream(), in order with the projector work around it); default the context of the first DeviceArray passed in, or a context of
     the handle's own.  Arguments are checked before the context or the handle is made."""
 
-    def __init__(self, ctx=None):
-        self.ctx = ctx
-        self.handle = None
-        self._own_ctx = None
-
-    def _ready(self, like):
-        if self.ctx is None:
-            if _is_dev(like):
-                self.ctx = like.ctx
-            else:
-                self.ctx = self._own_ctx = _lib.Context()
-        if self.handle is None:
-            self.handle = _pyr_lib.PyrHandle(self.ctx.device)
-
-    def close(self):
-        if self.handle is not None:
-            self.handle.close()
-            self.handle = None
-        if self._own_ctx is not None:
-            self._own_ctx.close()
-            self._own_ctx = self.ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def _new_handle(self):
+        return _pyr_lib.PyrHandle(self.ctx.device)
 
     def _run(self, src, oshape, out, launch):
         """Upload a host source, allocate the destination unless `out` is given, launch; device in -> device out, host in -> host out."""

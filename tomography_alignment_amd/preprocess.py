@@ -57,16 +57,13 @@ import math
 
 import numpy as np
 
-from . import _lib, _phase_lib, _prep_lib
+from . import _phase_lib, _prep_lib
+from ._ops import HandleOwner, _is_dev
 from ._prep_lib import PrepUnsupported  # noqa: F401  (re-exported)
 
 DEFAULT_SCRATCH_BYTES = 2 << 30
 METHODS = {"mean": _prep_lib.MEAN, "median": _prep_lib.MEDIAN}
 _DTYPES = {np.dtype(np.uint16): _prep_lib.U16, np.dtype(np.float32): _prep_lib.F32}
-
-
-def _is_dev(a):
-    return isinstance(a, _lib.DeviceArray)
 
 
 def _shape_dtype(a, what, ndims):
@@ -168,36 +165,23 @@ def _float32_stack(proj):
     return shape
 
 
-class Preprocessor(object):
+class Preprocessor(HandleOwner):
     """One libtomo_prep handle and its scratch, reused across calls.  ctx: the _lib.Context whose device and stream the work uses (work
     is enqueued on ctx.stream(), in order with the projector work that follows); default the context of the first DeviceArray passed in,
     or a context of the handle's own.  Arguments are checked before the context or the handle is made."""
 
     def __init__(self, ctx=None):
-        self.ctx = ctx
-        self.handle = None
-        self._own_ctx = None
+        HandleOwner.__init__(self, ctx)
         self._phase = None
 
-    def _ready(self, like):
-        if self.ctx is None:
-            if _is_dev(like):
-                self.ctx = like.ctx
-            else:
-                self.ctx = self._own_ctx = _lib.Context()
-        if self.handle is None:
-            self.handle = _prep_lib.PrepHandle(self.ctx.device)
+    def _new_handle(self):
+        return _prep_lib.PrepHandle(self.ctx.device)
 
     def close(self):
         if self._phase is not None:
             self._phase.close()
             self._phase = None
-        if self.handle is not None:
-            self.handle.close()
-            self.handle = None
-        if self._own_ctx is not None:
-            self._own_ctx.close()
-            self._own_ctx = self.ctx = None
+        HandleOwner.close(self)
 
     def _upload(self, a, temps):
         if _is_dev(a):
@@ -332,13 +316,8 @@ class Preprocessor(object):
             self._free(temps)
         return (result, ms) if timed else result
 
-
     def _ready_phase(self, like):
-        if self.ctx is None:
-            if _is_dev(like):
-                self.ctx = like.ctx
-            else:
-                self.ctx = self._own_ctx = _lib.Context()
+        self._ready_ctx(like)
         if self._phase is None:
             self._phase = _phase_lib.PhaseHandle(self.ctx.device)      # made on first use: loads hipFFT
 

@@ -32,8 +32,9 @@ here are lower -- more lenient -- than a corrected one would be).
 """
 import numpy as np
 
-from . import _fsc_lib, _lib
+from . import _fsc_lib
 from ._fsc_lib import FscUnsupported  # noqa: F401  (re-exported)
+from ._ops import HandleOwner, _is_dev
 from .recon import fbp, sirt, sirt_mpi
 
 THRESHOLDS = ("half-bit", "one-bit", "0.143", "0.5")
@@ -141,10 +142,6 @@ def half_weights(phi, parity):
     return fbp.angle_weights(np.asarray(phi, np.float64).ravel()[parity::2])
 
 
-def _is_dev(a):
-    return isinstance(a, _lib.DeviceArray)
-
-
 def _shape_of(a, shape, ndim, what):
     own = tuple(a.shape) if _is_dev(a) else np.shape(a)
     shape = tuple(int(v) for v in (own if shape is None else shape))
@@ -157,37 +154,12 @@ def _shape_of(a, shape, ndim, what):
     return shape
 
 
-class Resolution(object):
+class Resolution(HandleOwner):
     """One libtomo_fsc handle and its hipFFT plans reused across calls.  ctx: the _lib.Context whose device and stream the work uses
     (default: that of the first DeviceArray passed in, or a context of the handle's own)."""
 
-    def __init__(self, ctx=None):
-        self.ctx = ctx
-        self.handle = None
-        self._own_ctx = None
-
-    def _ready(self, like):
-        if self.ctx is None:
-            if _is_dev(like):
-                self.ctx = like.ctx
-            else:
-                self.ctx = self._own_ctx = _lib.Context()
-        if self.handle is None:
-            self.handle = _fsc_lib.FscHandle(self.ctx.device)
-
-    def close(self):
-        if self.handle is not None:
-            self.handle.close()
-            self.handle = None
-        if self._own_ctx is not None:
-            self._own_ctx.close()
-            self._own_ctx = self.ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def _new_handle(self):
+        return _fsc_lib.FscHandle(self.ctx.device)
 
     def device_bytes(self):
         return 0 if self.handle is None else self.handle.device_bytes()
