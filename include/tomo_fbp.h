@@ -46,7 +46,8 @@ TOMO_API int tomo_fbp_create(int device, tomo_fbp **h);
 TOMO_API int tomo_fbp_destroy(tomo_fbp *h);
 TOMO_API const char *tomo_fbp_last_error(tomo_fbp *h);
 /* The response for detector width ndx: table = H[0 .. Npad/2] (float64, host).  Replaces the previous one (after the work queued
- * with it has finished). */
+ * with it has finished).  The table carries no length: exactly Npad/2 + 1 doubles are read, Npad = max(64, smallest power of two
+ * >= 2 ndx), so the caller's table must hold that many (the Python binding checks it before the call). */
 TOMO_API int tomo_fbp_set_response(tomo_fbp *h, int ndx, const double *table);
 /* q = scale * filter(p) for n_proj projections of ndx x ndz, enqueued on `stream` (a hipStream_t; NULL: the null stream).
  * d_out may alias d_in (in place).  h_scale: n_proj float64 scales (host; copied before the call returns). */

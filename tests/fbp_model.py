@@ -1,4 +1,5 @@
-"""float64 model of recon/fbp.py (numpy FFT filter + the CPU oracle's adjoint) and the blob phantom the FBP accuracy tests use.
+"""float64 model of recon/fbp.py (numpy FFT filter + the CPU oracle's adjoint), the per-column-pair error measure of the filter tests and
+the blob phantom the FBP accuracy tests use.
 Used by tests/test_fbp.py (CPU) and tests/test_gpu_fbp.py."""
 import numpy as np
 
@@ -17,6 +18,22 @@ def filter_model(p, filter="ramp", scales=None):
     if scales is not None:
         q = q * np.asarray(scales, np.float64)[:, None, None]
     return q
+
+
+def pair_errs(got, ref):
+    """max|got - ref| / max|ref| per projection and column pair (2s, 2s+1) -- the two columns one complex signal of the kernel carries --
+    both maxima over the pair's two columns and all rows; a trailing lone column is a pair of its own.  Shape (n_proj, ceil(ndz / 2))."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    out = np.empty((ref.shape[0], (ref.shape[2] + 1) // 2))
+    for s in range(out.shape[1]):
+        r = ref[:, :, 2 * s:2 * s + 2]
+        out[:, s] = np.max(np.abs(got[:, :, 2 * s:2 * s + 2] - r), axis=(1, 2)) / np.maximum(np.max(np.abs(r), axis=(1, 2)), 1e-300)
+    return out
+
+
+def pair_err(got, ref):
+    """The worst pair of pair_errs."""
+    return float(np.max(pair_errs(got, ref)))
 
 
 def fbp_model(og, proj, phi, alpha=None, beta=None, xyz=None, filter="ramp", weights=None):

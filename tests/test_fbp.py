@@ -28,6 +28,43 @@ def test_ramp_response_is_abs_f_within_the_truncation_bound(ndx):
     assert H[0] > 0
 
 
+def test_padded_length_is_the_integer_rule_at_every_width():
+    """tomo_fbp_set_response takes the table without a length and reads Npad/2 + 1 doubles, Npad from the library's integer log2_npad
+    (Npad = 64 << l for the first l with 64 << l >= 2 ndx); padded_length and the binding's response_length must give the same.
+    Every supported width, and the first unsupported one (its table is still handed to the library, which refuses it)."""
+    for ndx in range(1, fbp.MAX_NDX + 2):
+        npad = max(64, 1 << (2 * ndx - 1).bit_length())
+        assert npad >= 2 * ndx and (npad == 64 or npad < 4 * ndx)
+        assert fbp.padded_length(ndx) == npad, ndx
+        assert _fbp_lib.response_length(ndx) == npad // 2 + 1, ndx
+        if ndx <= fbp.MAX_NDX:
+            assert fbp.filter_response(ndx).size == npad // 2 + 1, ndx
+    for ndx in (1, 2, 31, 32, 33, 64, 65, 100, 128, 129, 256, 257, 1024, 1025, 2048, 2049, 4096):
+        for name in fbp.FILTERS:
+            assert fbp.filter_response(ndx, name).size == fbp.padded_length(ndx) // 2 + 1, (ndx, name)
+    assert fbp.filter_response(4096).size == 4097 and fbp.filter_response(1).size == 33
+
+
+def test_set_response_checks_the_length_before_the_c_call():
+    h = object.__new__(_fbp_lib.FbpHandle)          # no library, no handle: anything past the length check would raise AttributeError
+    for ndx, n in ((100, 128), (100, 130), (32, 65), (33, 33), (4096, 4096), (1, 1)):
+        with pytest.raises(ValueError, match="Npad/2 \\+ 1"):
+            h.set_response(ndx, np.zeros(n))
+
+
+def test_pair_err_on_known_arrays():
+    ref = np.zeros((2, 4, 5))
+    ref[0, :, 0], ref[0, :, 1], ref[0, :, 4], ref[1] = 1.0, 100.0, 2.0, 1.0
+    got = ref.copy()
+    got[0, 2, 0] += 0.5          # pair 0 of projection 0: 0.5 / 100
+    got[0, 1, 4] -= 0.5          # the lone last column: 0.5 / 2
+    got[1, 3, 3] += 0.125        # pair 1 of projection 1: 0.125 / 1
+    e = fm.pair_errs(got, ref)
+    assert e.shape == (2, 3)
+    assert np.array_equal(e, [[0.005, 0.0, 0.25], [0.0, 0.125, 0.0]])
+    assert fm.pair_err(got, ref) == 0.25
+
+
 def test_windows_at_zero_and_nyquist():
     expect = {"ramp": (1.0, 1.0), "shepp-logan": (1.0, 2 / np.pi), "cosine": (1.0, 0.0), "hamming": (1.0, 0.08), "hann": (1.0, 0.0)}
     for name, (w0, wn) in expect.items():

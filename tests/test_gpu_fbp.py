@@ -11,6 +11,7 @@ import pytest
 
 import fbp_model as fm
 from conftest import ROOT, rel_max
+from fbp_model import pair_err, pair_errs
 from oracle import oracle as orc
 
 from tomography_alignment_amd import _fbp_lib, _lib
@@ -91,6 +92,213 @@ def test_wider_than_4096_is_unsupported_and_writes_nothing(ctx):
         assert np.all(d.download() == 7.0)
         with pytest.raises(_lib.TomoError):          # a width whose response was not set
             h.filter(ctx.stream(), d.ptr, d.ptr, 2, 100, 3, [1.0, 1.0])
+
+
+def _columns_per_group(ndx):
+    """Cfg<LOGN>::C of csrc/fbp/tomo_fbp.hip: a work-group holds S = (TOMO_FBP_LDS_KIB * 1024 / 8) >> LOGN complex signals of Npad
+    values (at least one), two detector columns each.  8192 is the shipped TOMO_FBP_LDS_KIB = 64."""
+    return 2 * max(1, 8192 // fbp.padded_length(ndx))
+
+
+def _per_projection(got, ref):
+    return [rel_max(got[i], ref[i]) for i in range(ref.shape[0])]
+
+
+# LOGN -> the smallest and the largest detector width that pad to Npad = 2^LOGN
+WIDTHS = {6: (1, 32), 7: (33, 64), 8: (65, 128), 9: (129, 256), 10: (257, 512), 11: (513, 1024), 12: (1025, 2048), 13: (2049, 4096)}
+
+
+@pytest.mark.parametrize("logn", sorted(WIDTHS))
+def test_every_fft_length_at_both_ends_of_its_width_range(ctx, logn):
+    """Every k_ramp_filter<LOGN> (6, 9 and 12 start with a radix-8 pass, the others with radix 2 or 4), with one partly filled
+    work-group per projection, a full one, and two or three chunks whose last holds one lone column; measured per projection."""
+    worst, k = 0.0, 0
+    for ndx in WIDTHS[logn]:
+        assert fbp.padded_length(ndx) == 1 << logn
+        C = _columns_per_group(ndx)
+        rng = np.random.default_rng(100 * ndx + logn)
+        with _fbp_lib.FbpHandle(ctx.device) as h:
+            for a, ndz in enumerate(sorted({1, C - 1, C, C + 1, 2 * C + 1} - {0})):
+                n = 3
+                p = rng.standard_normal((n, ndx, ndz)).astype(np.float32)
+                scales = rng.uniform(0.5, 2.0, n)
+                names = fbp.FILTERS if ndz == C + 1 else ("ramp", fbp.FILTERS[1 + a % 4])
+                for name in names:
+                    h.set_response(ndx, fbp.filter_response(ndx, name))
+                    ref = fm.filter_model(p, name, scales)
+                    got = _filter_gpu(ctx, h, p, scales, in_place=bool(k % 2))
+                    k += 1
+                    e = _per_projection(got, ref)
+                    worst = max(worst, max(e))
+                    assert max(e) <= 1e-5, (ndx, ndz, name, e)
+    print("filter parity LOGN %d (ndx %d and %d, C %d): worst per-projection rel_max %.2e over %d launches"
+          % (logn, WIDTHS[logn][0], WIDTHS[logn][1], C, worst, k))
+
+
+def _structured(ndx, rng):
+    """One projection of eight columns, ordered so that unlike kinds share a complex signal."""
+    x = np.arange(ndx)
+    cols = [np.ones(ndx),                                   # constant: all of it at DC and the lowest bins
+            (x == 0) * 1.0,                                 # impulse at row 0
+            (x == ndx - 1) * 1.0,                           # impulse at the last row
+            2 + np.cos(2 * np.pi * x / ndx),
+            (x >= ndx // 3) * 1.0,                          # step
+            1.0 - 2.0 * (x % 2),                            # alternating +-1: the Nyquist bin
+            rng.standard_normal(ndx),
+            1000 + rng.standard_normal(ndx)]
+    return np.stack(cols, axis=1)[None]
+
+
+@pytest.mark.parametrize("ndx", [20] + [WIDTHS[l][1] for l in sorted(WIDTHS)])
+def test_structured_columns_per_pair(ctx, ndx):
+    """Inputs with their weight at DC, at Nyquist and at single rows, each pair of columns measured against its own maximum: a wrong
+    H[0] or H[min(i, N - i)] off by one, which white noise under an array-wide maximum hides, moves these by far more than 1e-5
+    (H[0] = 0 moves every pair by 1.7e-5 ... 1.2e-2).  Measured on an MI355X: worst pair 2.2e-7 (ndx 20) ... 4.4e-7 (ndx 4096); a
+    float32 two-columns-per-signal FFT on the CPU is within 5e-7 of the model."""
+    logn = fbp.padded_length(ndx).bit_length() - 1
+    base = _structured(ndx, np.random.default_rng(ndx))
+    worst, k = 0.0, 0
+    with _fbp_lib.FbpHandle(ctx.device) as h:
+        for amp in ((1, 1, 1, 1, 1, 1, 1, 1), (1, 1, 1e3, 1e-3, 1, 1, 1, 1)):
+            p = (base * np.array(amp, np.float64)).astype(np.float32)
+            for name in fbp.FILTERS:
+                h.set_response(ndx, fbp.filter_response(ndx, name))
+                ref = fm.filter_model(p, name, [1.3])
+                got = _filter_gpu(ctx, h, p, [1.3], in_place=bool(k % 2))
+                k += 1
+                e = pair_errs(got, ref)
+                assert pair_err(got, ref) == e.max()
+                worst = max(worst, e.max())
+                assert e.max() <= 1e-5, (ndx, amp, name, "per pair (1,2) (3,4) (5,6) (7,8):", e[0])
+    print("structured columns LOGN %d (ndx %d): worst pair_err %.2e over 2 amplitude sets x %s" % (logn, ndx, worst, ", ".join(fbp.FILTERS)))
+
+
+@pytest.mark.parametrize("z0", [70, 5, 128], ids=["even", "odd", "lone-last"])
+def test_a_non_finite_value_stays_in_its_column_pair(ctx, z0):
+    """Columns 2s and 2s+1 share one complex signal, so a NaN or an infinity spoils its own column and its partner (DESIGN.md 7b,
+    Limits); every other column, and every other projection, must not change by a bit."""
+    ndx = 100
+    C = _columns_per_group(ndx)
+    ndz = 2 * C + 1
+    assert C == 64 and z0 < ndz
+    rng = np.random.default_rng(z0)
+    p = rng.standard_normal((3, ndx, ndz)).astype(np.float32)
+    scales = [0.7, 1.1, 1.9]
+    keep = np.ones(p.shape, bool)
+    keep[1, :, z0 & ~1:(z0 & ~1) + 2] = False
+    with _fbp_lib.FbpHandle(ctx.device) as h:
+        h.set_response(ndx, fbp.filter_response(ndx, "hamming"))
+        clean = _filter_gpu(ctx, h, p, scales, in_place=False)
+        assert np.all(np.isfinite(clean)) and max(_per_projection(clean, fm.filter_model(p, "hamming", scales))) <= 1e-5
+        for bad in (np.nan, np.inf):
+            q = p.copy()
+            q[1, 37, z0] = bad
+            got = _filter_gpu(ctx, h, q, scales, in_place=bool(z0 % 2))
+            same = got.view(np.uint32)[keep] == clean.view(np.uint32)[keep]
+            print("%s at projection 1, column %d: %d of %d values outside its pair differ; %d of %d inside are non-finite"
+                  % (bad, z0, np.count_nonzero(~same), same.size, np.count_nonzero(~np.isfinite(got[~keep])), np.count_nonzero(~keep)))
+            assert np.all(same), (bad, z0, np.argwhere(~(got.view(np.uint32) == clean.view(np.uint32)) & keep)[:5])
+
+
+@pytest.mark.parametrize("ndx", [WIDTHS[6][1], WIDTHS[9][1], WIDTHS[13][1]])
+def test_a_column_pair_filters_the_same_wherever_it_lies(ctx, ndx):
+    """The same two columns as the first pair of the only projection, and as the first pair of the third chunk of the last projection
+    (another chunk, another blockIdx, another base offset): the same result up to the order of the sums."""
+    C = _columns_per_group(ndx)
+    rng = np.random.default_rng(ndx + 1)
+    cols = rng.standard_normal((ndx, 2)).astype(np.float32)
+    big = rng.standard_normal((3, ndx, 2 * C + 2)).astype(np.float32)
+    big[2, :, 2 * C:] = cols
+    with _fbp_lib.FbpHandle(ctx.device) as h:
+        h.set_response(ndx, fbp.filter_response(ndx, "shepp-logan"))
+        a = _filter_gpu(ctx, h, cols[None], [1.7], in_place=False)
+        b = _filter_gpu(ctx, h, big, [0.6, 1.2, 1.7], in_place=True)[2:, :, 2 * C:]
+    assert pair_err(a, fm.filter_model(cols[None], "shepp-logan", [1.7])) <= 1e-5
+    e = pair_err(b, a)
+    print("placement ndx %d (C %d): pair_err %.2e between z = 0, 1 of 1 projection and z = %d, %d of projection 2 of 3; bit-equal: %s"
+          % (ndx, C, e, 2 * C, 2 * C + 1, np.array_equal(a.view(np.uint32), b.view(np.uint32))))
+    assert e <= 1e-6
+
+
+def _buffers(ctx, p):
+    """The uploaded input and a zeroed output.  Uploads synchronise the context's stream, so whatever must stay queued behind a filter
+    gets its buffers before that filter is issued."""
+    return ctx.to_device(p), ctx.zeros(p.shape)
+
+
+def _enqueue(h, st, bufs, shape, scales):
+    """filter() out of place on stream st: no upload, no allocation, no sync."""
+    h.filter(st, bufs[0].ptr, bufs[1].ptr, shape[0], shape[1], shape[2], scales)
+
+
+def test_one_handle_through_a_sequence(ctx):
+    """One handle: the tables replaced when the FFT length goes down, up, stays and comes back; the scale buffers grown and then larger
+    than needed; two filters queued with no sync between them (they share the pinned scale staging); the response replaced while a
+    filter is still queued; an empty call; a scales array of the wrong length."""
+    rng = np.random.default_rng(4)
+    with _fbp_lib.FbpHandle(ctx.device) as h:
+        for ndx, name, n, ndz in ((2048, "ramp", 2, 5), (20, "cosine", 5, 70), (300, "shepp-logan", 1, 9), (300, "hamming", 1, 9),
+                                  (2048, "hann", 2, 3)):
+            p = rng.standard_normal((n, ndx, ndz)).astype(np.float32)
+            scales = rng.uniform(0.5, 2.0, n)
+            h.set_response(ndx, fbp.filter_response(ndx, name))
+            e = _per_projection(_filter_gpu(ctx, h, p, scales, in_place=False), fm.filter_model(p, name, scales))
+            print("sequence: ndx %4d %-11s n_proj %d: worst per-projection rel_max %.2e" % (ndx, name, n, max(e)))
+            assert max(e) <= 1e-5, (ndx, name, n, e)
+
+        # two filters back to back (2048, hann): different inputs, outputs, scales and projection counts, one sync
+        p1, p2 = rng.standard_normal((2, 2048, 3)).astype(np.float32), rng.standard_normal((4, 2048, 5)).astype(np.float32)
+        s1, s2 = rng.uniform(0.5, 2.0, 2), rng.uniform(2.0, 8.0, 4)
+        b1, b2, st = _buffers(ctx, p1), _buffers(ctx, p2), ctx.stream()
+        _enqueue(h, st, b1, p1.shape, s1)
+        _enqueue(h, st, b2, p2.shape, s2)          # rewrites the pinned scales the first filter's copy reads: tomo_fbp_filter waits first
+        ctx.sync()
+        e1 = _per_projection(b1[1].download(), fm.filter_model(p1, "hann", s1))
+        e2 = _per_projection(b2[1].download(), fm.filter_model(p2, "hann", s2))
+        print("sequence: two filters, one sync: worst per-projection rel_max %.2e and %.2e" % (max(e1), max(e2)))
+        assert max(e1) <= 1e-5 and max(e2) <= 1e-5, (e1, e2)
+
+        # the response replaced at the same FFT length while the filter that reads the old one is still queued
+        p = rng.standard_normal((3, 300, 40)).astype(np.float32)
+        s = rng.uniform(0.5, 2.0, 3)
+        ramp, hann = fbp.filter_response(300, "ramp"), fbp.filter_response(300, "hann")
+        bA, bB = _buffers(ctx, p), _buffers(ctx, p)
+        h.set_response(300, ramp)
+        _enqueue(h, st, bA, p.shape, s)
+        h.set_response(300, hann)
+        _enqueue(h, st, bB, p.shape, s)
+        ctx.sync()
+        A, B = bA[1].download(), bB[1].download()
+        eA, eB = _per_projection(A, fm.filter_model(p, "ramp", s)), _per_projection(B, fm.filter_model(p, "hann", s))
+        print("sequence: ramp, set_response(hann), hann, one sync: worst per-projection rel_max %.2e (ramp) and %.2e (hann); "
+              "ramp vs hann differ by %.2e" % (max(eA), max(eB), rel_max(A, B)))
+        assert max(eA) <= 1e-5 and max(eB) <= 1e-5, (eA, eB)
+
+        # no projections: nothing is launched; scales of the wrong length: the binding raises, and nothing is launched either
+        d = ctx.to_device(np.full((3, 300, 4), 7.0, np.float32))
+        h.filter(ctx.stream(), d.ptr, d.ptr, 0, 300, 4, [])
+        for bad in ([1.0, 2.0], [1.0, 2.0, 3.0, 4.0], []):
+            with pytest.raises(ValueError):
+                h.filter(ctx.stream(), d.ptr, d.ptr, 3, 300, 4, bad)
+        ctx.sync()
+        assert np.all(d.download() == 7.0)
+
+
+def test_a_response_table_of_the_wrong_length_is_refused(ctx):
+    """tomo_fbp_set_response reads Npad/2 + 1 doubles from a bare pointer; the binding refuses any other length before the call, and the
+    handle keeps the response it had."""
+    rng = np.random.default_rng(9)
+    p = rng.standard_normal((2, 100, 5)).astype(np.float32)
+    good = fbp.filter_response(100, "hann")
+    assert good.size == 129 == _fbp_lib.response_length(100)
+    with _fbp_lib.FbpHandle(ctx.device) as h:
+        h.set_response(100, good)
+        for ndx, table in ((100, good[:-1]), (100, np.append(good, 0.0)), (300, good), (20, good)):
+            with pytest.raises(ValueError):
+                h.set_response(ndx, table)
+        e = _per_projection(_filter_gpu(ctx, h, p, [1.0, 2.0], in_place=True), fm.filter_model(p, "hann", [1.0, 2.0]))
+        print("after four refused tables: worst per-projection rel_max %.2e" % max(e))
+        assert max(e) <= 1e-5
 
 
 def _case(N, n, seed, perturbed):

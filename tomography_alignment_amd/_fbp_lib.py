@@ -35,6 +35,12 @@ class FbpUnsupported(TomoError):
     """The detector is wider than the kernel supports (ndx > 4096)."""
 
 
+def response_length(ndx):
+    """Npad/2 + 1, the number of doubles tomo_fbp_set_response reads for detector width ndx (Npad: recon/fbp.py::padded_length)."""
+    from .recon.fbp import padded_length
+    return padded_length(ndx) // 2 + 1
+
+
 def load():
     """Load libtomo_fbp.so and bind every symbol; raises TomoError (never falls back) on failure."""
     return _binding.load("fbp", LIB_PATH, SIGNATURES)
@@ -49,8 +55,13 @@ class FbpHandle(Handle):
     ERRORS = {ERR_UNSUPPORTED: FbpUnsupported}
 
     def set_response(self, ndx, table):
-        """The response H[0 .. Npad/2] (recon/fbp.py::filter_response) for detector width ndx."""
+        """The response H[0 .. Npad/2] (recon/fbp.py::filter_response) for detector width ndx.  The C call takes the table without a
+        length and reads response_length(ndx) doubles from it, so any other length is a ValueError here, before the call."""
         t = np.ascontiguousarray(table, np.float64)
+        # ndx < 1 has no length to check: it goes to the library, which refuses it (TOMO_FBP_ERR_ARG) before it reads the table
+        if int(ndx) >= 1 and t.size != response_length(ndx):
+            raise ValueError("set_response: the table for ndx %d must hold Npad/2 + 1 = %d values, not %d"
+                             % (int(ndx), response_length(ndx), t.size))
         self._check(self.lib.tomo_fbp_set_response(self.handle, int(ndx), t.ctypes.data_as(_c_dp)))
 
     def filter(self, stream, d_in, d_out, n_proj, ndx, ndz, scales):

@@ -39,11 +39,12 @@ FILTERS = tuple(_WINDOWS)
 
 
 def padded_length(ndx):
-    """Npad = max(64, smallest power of two >= 2 ndx)."""
+    """Npad = max(64, smallest power of two >= 2 ndx), in integers as the library's log2_npad computes it: the response table handed to
+    tomo_fbp_set_response must hold exactly Npad/2 + 1 values."""
     ndx = int(ndx)
     if ndx < 1:
         raise ValueError("padded_length: ndx must be >= 1")
-    return max(64, 1 << int(np.ceil(np.log2(2 * ndx))))
+    return max(64, 1 << (2 * ndx - 1).bit_length())
 
 
 def ramlak_kernel(npad):
