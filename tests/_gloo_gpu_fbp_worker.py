@@ -1,14 +1,9 @@
 """Worker of tests/test_gpu_fbp.py: one rank of the angle-sharded FBP (recon/fbp_mpi.py) with the REAL HIP backend (every rank opens its
-own context on GPU 0) and tests/_gloo_gpu_worker.py's host-staged gloo communicator standing in for RCCL.  Every rank writes what it
+own context on GPU 0) and tests/backends.py's host-staged gloo communicator standing in for RCCL.  Every rank writes what it
 computed to <out>.rank<r>.npz."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+from gloo_world import rank_main
 
 
 def problem():
@@ -28,16 +23,11 @@ def problem():
     return N, phi, alpha, beta, xyz, cor, p
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from _gloo_gpu_worker import HostStagedComm
+def body(comm, ctx):
     from tomography_alignment_amd import _lib
     from tomography_alignment_amd.recon import fbp_mpi
     from tomography_alignment_amd.utilities.geometry import Geometry
 
-    ctx = _lib.Context(0)
-    comm = HostStagedComm(ctx)
     N, phi, alpha, beta, xyz, cor, p = problem()
     geo = Geometry(phi.size, np.array([N, N, N]), np.ones(3), np.array([N, N]), np.ones(2), cor_shift=cor)
     angles = np.array([phi, alpha, beta]).T
@@ -46,11 +36,8 @@ def main(out_path):
         f = fbp_mpi.FBP(comm, geo, p, angles, xyz, options={"filter": filt})
         out[filt] = f.run()
         out[filt + "_rows"] = np.asarray(f.my_index)
-    np.savez(out_path + ".rank%d.npz" % comm.rank, **out)
-    dist.barrier()
-    ctx.close()
-    dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body, gpu=True, per_rank=True)

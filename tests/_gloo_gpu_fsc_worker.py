@@ -1,27 +1,17 @@
 """Worker of tests/test_gpu_resolution.py: one rank of resolution.half_set_fsc with the REAL HIP backend (every rank opens its own context
-on GPU 0) and tests/_gloo_gpu_worker.py's host-staged gloo communicator standing in for RCCL.  The rank computes the curve once from the
+on GPU 0) and tests/backends.py's host-staged gloo communicator standing in for RCCL.  The rank computes the curve once from the
 host array of all projections and once from a device buffer that holds only its own np.array_split block, and writes both, and the raw
 table of the second, to <out>.rank<r>.npz."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+from gloo_world import rank_main
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from _gloo_gpu_worker import HostStagedComm
+def body(comm, ctx):
     from tomography_alignment_amd import _lib, resolution
     from tomography_alignment_amd.examples import generate_data
     from tomography_alignment_amd.utilities.geometry import Geometry
 
-    ctx = _lib.Context(0)
-    comm = HostStagedComm(ctx)
     d = generate_data.make(64, 90, seed=3)
     n = d["phi"].size
     geo = Geometry(n, np.array([64, 64, 64]), np.ones(3), np.array([64, 64]), np.ones(2))
@@ -34,11 +24,8 @@ def main(out_path):
     d_p = ctx.to_device(proj.reshape(n, -1)[mine].ravel())
     c = resolution.half_set_fsc(geo, d_p, angles, d["xyz"], comm=comm)
     out.update(device_fsc=c.fsc, device_count=c.count, device_PA=c.PA, table=np.array([c.C, c.PA, c.PB, c.count]), rows=mine)
-    np.savez(out_path + ".rank%d.npz" % comm.rank, **out)
-    dist.barrier()
-    ctx.close()
-    dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body, gpu=True, per_rank=True)

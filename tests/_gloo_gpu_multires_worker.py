@@ -1,29 +1,19 @@
 """Worker of tests/test_gpu_multires.py: one rank of the angle-sharded examples/align_rigid.run_multires with the REAL HIP backend (every
-rank opens its own context on GPU 0) and tests/_gloo_gpu_worker.py's host-staged gloo communicator standing in for RCCL.  Every rank
+rank opens its own context on GPU 0) and tests/backends.py's host-staged gloo communicator standing in for RCCL.  Every rank
 writes what it computed to <out>.rank<r>.npz."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+from gloo_world import rank_main
 
 
-def main(out_path):
+def body(comm, ctx):
     import torch
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from _gloo_gpu_worker import HostStagedComm
     from tomography_alignment_amd import _lib
     from tomography_alignment_amd.backend import HipBackend
     from tomography_alignment_amd.examples import align_rigid
     from tomography_alignment_amd.utilities.geometry import Geometry
     from tomography_alignment_amd.utilities.generate_phantom import shepp3d
 
-    ctx = _lib.Context(0)
-    comm = HostStagedComm(ctx)
     N, n_proj = 48, 12                                                    # the problem of _gloo_gpu_worker.align_rigid_stages
     rng = np.random.default_rng(17)
     x = shepp3d(N).astype(np.float32)
@@ -35,18 +25,15 @@ def main(out_path):
     full = HipBackend(geo, ctx=ctx)
     b = full.forward(_lib.poses_array(phi, alpha, beta, xyz, np.zeros(3)), full.upload(x), full.empty(n_proj * N * N)).download().reshape(n_proj, N, N)
     t = torch.from_numpy(np.ascontiguousarray(b))                         # rank 0's copy on every rank (float32 atomics in the forward projector)
-    dist.broadcast(t, src=0)
+    comm.dist.broadcast(t, src=0)
     data = dict(projections=t.numpy(), phi=phi, phantom=x, xyz=xyz, alpha=alpha, beta=beta)
     rec, a, bb, tt, hist = align_rigid.run_multires(data, levels=3, n_outer=(2, 2, 2), sirt_iters=8, verbose=False, comm=comm)
     spread = max(comm.allreduce_max(float(v)) + comm.allreduce_max(-float(v)) for v in np.concatenate([a, bb, tt.ravel()]))
-    np.savez(out_path + ".rank%d.npz" % comm.rank, rec=rec, alpha=a, beta=bb, xyz=tt, spread=spread, injected=np.abs(xyz[:, [0, 2]]).mean(),
-             rmse=np.array([h["rmse"] for h in hist]), shift_err=np.array([h["shift_err_px"] for h in hist]),
-             tilt_err=np.array([h["tilt_err_deg"] for h in hist]), factor=np.array([h["factor"] for h in hist]),
-             ranks=np.array([h["ranks"] for h in hist]))
-    dist.barrier()
-    ctx.close()
-    dist.destroy_process_group()
+    return dict(rec=rec, alpha=a, beta=bb, xyz=tt, spread=spread, injected=np.abs(xyz[:, [0, 2]]).mean(),
+                rmse=np.array([h["rmse"] for h in hist]), shift_err=np.array([h["shift_err_px"] for h in hist]),
+                tilt_err=np.array([h["tilt_err_deg"] for h in hist]), factor=np.array([h["factor"] for h in hist]),
+                ranks=np.array([h["ranks"] for h in hist]))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body, gpu=True, per_rank=True)

@@ -1,105 +1,10 @@
 """Worker of tests/test_gpu_dist.py: one rank of an angle-sharded SIRT run with the REAL HIP backend (every rank opens its own
-context on GPU 0) and a host-staged torch.distributed/gloo communicator standing in for RCCL (two RCCL ranks cannot share one GPU;
-the 1-GPU boxes of this pool cannot run RCCL with more than one rank).  What this exercises that nothing else does: the sharded
+context on GPU 0) and tests/backends.py's host-staged torch.distributed/gloo communicator standing in for RCCL.  What this exercises that nothing else does: the sharded
 solver's slab pipeline (tomo_adjoint_xslab / tomo_forward_xslab / tomo_vec_update_acc on views) with world size 2, i.e. partial
 volumes that really differ between ranks and are summed by a collective.  Rank 0 writes the results."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-
-class HostStagedComm(object):
-    """RcclComm's method set over gloo: device buffers are all-reduced through the host.  The asynchronous forms complete at once."""
-
-    def __init__(self, ctx):
-        import torch.distributed as dist
-        self.dist = dist
-        self.rank, self.size = dist.get_rank(), dist.get_world_size()
-        self.ctx = ctx
-        self.n_vol_allreduce = self.n_slab_allreduce = self.n_wait = 0
-
-    def _ar(self, buf):
-        import torch
-        if buf.size:
-            h = buf.download()
-            t = torch.from_numpy(h)
-            self.dist.all_reduce(t)
-            buf.upload(h)
-        return buf
-
-    def allreduce_sum_(self, buf):
-        self.n_vol_allreduce += 1
-        return self._ar(buf)
-
-    def allreduce_sum_async(self, buf):
-        self.n_slab_allreduce += 1
-        return self._ar(buf)
-
-    def wait_next(self):
-        self.n_wait += 1
-
-    # round 4: reduce-scatter (the pieces this rank does not own are left as NaN, as undefined as RCCL leaves them) and all-gather
-    def reduce_scatter_sum_async(self, buf, n_per_rank):
-        import torch
-        n = int(n_per_rank)
-        if n:
-            seg = buf.view(0, n * self.size)
-            h = seg.download()
-            self.dist.all_reduce(torch.from_numpy(h))
-            mine = h[self.rank * n:(self.rank + 1) * n].copy()
-            if self.size > 1:
-                h[:] = np.nan
-            h[self.rank * n:(self.rank + 1) * n] = mine
-            seg.upload(h)
-        self.n_rs = getattr(self, "n_rs", 0) + 1
-        return buf
-
-    def allgather_async(self, buf, n_per_rank):
-        import torch
-        n = int(n_per_rank)
-        if n:
-            seg = buf.view(0, n * self.size)
-            h = seg.download()
-            parts = [torch.empty(n, dtype=torch.float32) for _ in range(self.size)]
-            self.dist.all_gather(parts, torch.from_numpy(h[self.rank * n:(self.rank + 1) * n].copy()))
-            for q, part in enumerate(parts):
-                h[q * n:(q + 1) * n] = part.numpy()
-            seg.upload(h)
-        self.n_ag = getattr(self, "n_ag", 0) + 1
-        return buf
-
-    def wait_next_gather(self):
-        pass
-
-    def join(self):
-        pass
-
-    def allreduce_scalar(self, v):
-        import torch
-        t = torch.tensor([float(v)], dtype=torch.float64)
-        self.dist.all_reduce(t)
-        return float(t[0])
-
-    def allreduce_max(self, v):
-        import torch
-        t = torch.tensor([float(v)], dtype=torch.float64)
-        self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
-        return float(t[0])
-
-    def allreduce_array(self, a):
-        import torch
-        t = torch.from_numpy(np.ascontiguousarray(a, np.float64))
-        self.dist.all_reduce(t)
-        a[...] = t.numpy()
-        return a
-
-    def barrier(self):
-        self.dist.barrier()
+from gloo_world import rank_main
 
 
 def align_rigid_stages(ctx, comm, out):
@@ -181,16 +86,12 @@ def align_rigid_stages(ctx, comm, out):
     comm.force_pipeline = False
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
+def body(comm, ctx):
     from tomography_alignment_amd import _lib
     from tomography_alignment_amd.backend import HipBackend
     from tomography_alignment_amd.recon import sirt_mpi
     from tomography_alignment_amd.utilities.geometry import Geometry
 
-    ctx = _lib.Context(0)
-    comm = HostStagedComm(ctx)
     # 6 tile columns, ragged in every axis; 200 planes = two 128-plane blocks of the flat forward / four 64-plane chunks of the gather
     # back-projection, the object in planes 70 .. 149 only: all-zero images, empty sinogram planes and z chunks that end at once take part
     shape, ndet, n_proj = (80, 40, 200), (72, 210), 12
@@ -254,11 +155,8 @@ def main(out_path):
         out["one_angle_%s_rec" % mode], out["one_angle_%s_err" % mode] = r1, e1
     comm.force_pipeline = False
     out["one_angle_empty_ranks"] = np.array(int(round(comm.allreduce_scalar(1.0 if mine1.size == 0 else 0.0))))
-    if comm.rank == 0:
-        np.savez(out_path, **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out if comm.rank == 0 else None
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body, gpu=True)

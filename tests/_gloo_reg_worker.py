@@ -1,23 +1,15 @@
 """Worker of tests/test_regularized_recon.py: one rank of the angle-sharded RegularizedRecon over torch.distributed (gloo, CPU) with the
 numpy stand-in backend.  Every rank writes what it computed to <out>.rank<r>.npz."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+from gloo_world import rank_main
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from backends import Buf, GlooComm
+def body(comm, ctx):
+    from backends import Buf
     from reg_standin import RegOracleBackend, SHARD_CASES, shard_problem
     from tomography_alignment_amd.recon import regularized_mpi
 
-    comm = GlooComm()
     geo, b, angles, xyz, x = shard_problem()
     my = np.array_split(np.arange(angles.shape[0]), comm.size)[comm.rank]
     shard = regularized_mpi._shard_geometry(geo, my)
@@ -39,10 +31,8 @@ def main(out_path):
     a = rng.standard_normal(37) * 1.1
     comm.allreduce_array(a)
     out["probe_vol"], out["probe_arr"] = v.a.copy(), a
-    np.savez(out_path + ".rank%d.npz" % comm.rank, **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body, per_rank=True)

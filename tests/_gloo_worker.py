@@ -1,23 +1,19 @@
 """Worker of tests/test_dist_gloo.py: one rank of an angle-sharded SIRT / CGLS run over torch.distributed
 (gloo, CPU) with the oracle-backed stand-in backend.  Rank 0 writes the results."""
 import os
-import sys
 
 import numpy as np
 
+from gloo_world import rank_main
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from backends import OracleBackend, GlooComm
+def body(comm, ctx):
+    from backends import OracleBackend
     from tomography_alignment_amd.utilities.geometry import Geometry
     from tomography_alignment_amd.recon import sirt_mpi, cgls_mpi
 
-    comm = GlooComm()
     g = np.load(os.path.join(HERE, "golden", "g5_sirt.npz"))
     N, n_proj = 32, 16
     rng = np.random.default_rng(42)
@@ -144,17 +140,16 @@ def main(out_path):
     if comm.rank == 0:
         extra = {"c_%s_%s" % (t, n): v[i] for t, v in cvar.items() for i, n in enumerate(("rec", "err"))}
         extra.update({"st_" + k: v for k, v in st.items()})
-        np.savez(out_path, c_counts=c_counts, rec=rec, e_rec=e_rec, e_a=e_a, e_b=e_b, e_xyz=e_xyz, e_rmse=np.array([h["rmse"] for h in e_hist]),
-                 e_residual=np.array([h["residual"] for h in e_hist]), e_shift_err=np.array([h["shift_err_px"] for h in e_hist]),
-                 e_uploaded_rows=e_uploaded_rows, e_true=te, e_spread=e_spread, **extra, err=err, crec=crec, cerr=cerr, n_allreduce_sirt=n_allreduce_sirt, cor=cor,
-                 n_slab_sirt=n_slab_sirt, pipelined=pipelined, n_rs=n_rs, n_ag=n_ag, n_wg=n_wg, slab_sizes=slab_sizes, rec_a=rec_a, err_a=err_a,
-                 n_slab_allreduce_form=n_slab_allreduce_form, err_gt_sharded=err_gt_sharded, err_gt_allreduce=err_gt_allreduce, rank_spread=rank_spread, n_fwd_whole=n_fwd_whole, rec_d=rec_d, err_d=err_d,
-                 declined_pipelined=declined["pipelined"], declined_n_vol=declined["n_vol"], declined_n_slab=declined["n_slab"],
-                 rec_g=rec_g, err_g=err_g, rec_p=rec_p, err_p=err_p, rec_r=rec_r, err_r=err_r,
-                 align_x=ares["x"], align_fun=ares["fun"], align_true=true, align_nfev=ares["nfev"])
-    dist.barrier()
-    dist.destroy_process_group()
+        return dict(c_counts=c_counts, rec=rec, e_rec=e_rec, e_a=e_a, e_b=e_b, e_xyz=e_xyz, e_rmse=np.array([h["rmse"] for h in e_hist]),
+                    e_residual=np.array([h["residual"] for h in e_hist]), e_shift_err=np.array([h["shift_err_px"] for h in e_hist]),
+                    e_uploaded_rows=e_uploaded_rows, e_true=te, e_spread=e_spread, **extra, err=err, crec=crec, cerr=cerr, n_allreduce_sirt=n_allreduce_sirt, cor=cor,
+                    n_slab_sirt=n_slab_sirt, pipelined=pipelined, n_rs=n_rs, n_ag=n_ag, n_wg=n_wg, slab_sizes=slab_sizes, rec_a=rec_a, err_a=err_a,
+                    n_slab_allreduce_form=n_slab_allreduce_form, err_gt_sharded=err_gt_sharded, err_gt_allreduce=err_gt_allreduce, rank_spread=rank_spread, n_fwd_whole=n_fwd_whole, rec_d=rec_d, err_d=err_d,
+                    declined_pipelined=declined["pipelined"], declined_n_vol=declined["n_vol"], declined_n_slab=declined["n_slab"],
+                    rec_g=rec_g, err_g=err_g, rec_p=rec_p, err_p=err_p, rec_r=rec_r, err_r=err_r,
+                    align_x=ares["x"], align_fun=ares["fun"], align_true=true, align_nfev=ares["nfev"])
+    return None
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body)

@@ -4,14 +4,9 @@ outer iteration of examples/align_rigid.run(comm=) -- over torch.distributed (gl
 (VERDICT r5 next 6): a slab plan of 8 slabs cut into 8 pieces each with left-over voxels on some slabs, angle blocks of unequal size
 (20 angles: 3 3 3 3 2 2 2 2; 10 projections: 2 2 1 1 1 1 1 1), collective counts identical on every rank, one pose table on every rank.
 Rank 0 writes the results."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+from gloo_world import rank_main
 
 
 def counts(comm):
@@ -19,17 +14,14 @@ def counts(comm):
                      comm.n_wait, getattr(comm, "n_wait_gather", 0)], np.int64)
 
 
-def main(out_path):
-    import torch.distributed as dist
-    dist.init_process_group("gloo", init_method="env://")
-    from backends import OracleBackend, GlooComm
+def body(comm, ctx):
+    from backends import OracleBackend
     from oracle import oracle as orc
     from tomography_alignment_amd.comm import SingleComm
     from tomography_alignment_amd.examples import align_rigid
     from tomography_alignment_amd.recon import sirt_mpi, cgls_mpi
     from tomography_alignment_amd.utilities.geometry import Geometry
 
-    comm = GlooComm()
     comm.force_pipeline = True                        # world 1 takes the slab pipeline too: same code path as the 8 ranks
     out = {}
     # ---- SIRT / CGLS: 123 x 15 x 17 voxels = 8 tile columns of 16 -> 8 slabs of 15, 16 x 6, 12 planes of 255 voxels: 3825 = 8 x 478 + 1,
@@ -124,11 +116,8 @@ def main(out_path):
     # also shows it in the record), taken over the whole program
     total = counts(comm)
     out["counts_spread"] = np.array([comm.allreduce_max(float(v)) + comm.allreduce_max(-float(v)) for v in total])
-    if comm.rank == 0:
-        np.savez(out_path, **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out if comm.rank == 0 else None
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    rank_main(body)

@@ -1,7 +1,7 @@
 """CPU stand-ins used ONLY by the tests: an oracle-backed object with the method set of
-tomography_alignment_amd.backend.HipBackend (so the solvers' control flow can run without a GPU) and a
-torch.distributed (gloo) communicator with the method set of tomography_alignment_amd.comm.RcclComm.
-Nothing in the product imports this module."""
+tomography_alignment_amd.backend.HipBackend (so the solvers' control flow can run without a GPU) and two
+torch.distributed (gloo) communicators with the method set of tomography_alignment_amd.comm.RcclComm: GlooComm on
+the host buffers, HostStagedComm on the real device buffers.  Nothing in the product imports this module."""
 import numpy as np
 
 from oracle import oracle as orc
@@ -292,6 +292,97 @@ class GlooComm(object):
 
     def wait_next_gather(self):
         self.n_wait_gather = getattr(self, "n_wait_gather", 0) + 1
+
+    def join(self):
+        pass
+
+    def allreduce_scalar(self, v):
+        import torch
+        t = torch.tensor([float(v)], dtype=torch.float64)
+        self.dist.all_reduce(t)
+        return float(t[0])
+
+    def allreduce_max(self, v):
+        import torch
+        t = torch.tensor([float(v)], dtype=torch.float64)
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
+        return float(t[0])
+
+    def allreduce_array(self, a):
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(a, np.float64))
+        self.dist.all_reduce(t)
+        a[...] = t.numpy()
+        return a
+
+    def barrier(self):
+        self.dist.barrier()
+
+
+# Why gloo and not RCCL where a test runs world 2 with the REAL HIP backend: two RCCL ranks cannot share one GPU, and a machine with
+# one GPU cannot run RCCL with more than one rank.  Every rank opens its own context on GPU 0 and the collectives go through the host.
+class HostStagedComm(object):
+    """RcclComm's method set over gloo: device buffers are all-reduced through the host.  The asynchronous forms complete at once."""
+
+    def __init__(self, ctx):
+        import torch.distributed as dist
+        self.dist = dist
+        self.rank, self.size = dist.get_rank(), dist.get_world_size()
+        self.ctx = ctx
+        self.n_vol_allreduce = self.n_slab_allreduce = self.n_wait = 0
+
+    def _ar(self, buf):
+        import torch
+        if buf.size:
+            h = buf.download()
+            t = torch.from_numpy(h)
+            self.dist.all_reduce(t)
+            buf.upload(h)
+        return buf
+
+    def allreduce_sum_(self, buf):
+        self.n_vol_allreduce += 1
+        return self._ar(buf)
+
+    def allreduce_sum_async(self, buf):
+        self.n_slab_allreduce += 1
+        return self._ar(buf)
+
+    def wait_next(self):
+        self.n_wait += 1
+
+    # round 4: reduce-scatter (the pieces this rank does not own are left as NaN, as undefined as RCCL leaves them) and all-gather
+    def reduce_scatter_sum_async(self, buf, n_per_rank):
+        import torch
+        n = int(n_per_rank)
+        if n:
+            seg = buf.view(0, n * self.size)
+            h = seg.download()
+            self.dist.all_reduce(torch.from_numpy(h))
+            mine = h[self.rank * n:(self.rank + 1) * n].copy()
+            if self.size > 1:
+                h[:] = np.nan
+            h[self.rank * n:(self.rank + 1) * n] = mine
+            seg.upload(h)
+        self.n_rs = getattr(self, "n_rs", 0) + 1
+        return buf
+
+    def allgather_async(self, buf, n_per_rank):
+        import torch
+        n = int(n_per_rank)
+        if n:
+            seg = buf.view(0, n * self.size)
+            h = seg.download()
+            parts = [torch.empty(n, dtype=torch.float32) for _ in range(self.size)]
+            self.dist.all_gather(parts, torch.from_numpy(h[self.rank * n:(self.rank + 1) * n].copy()))
+            for q, part in enumerate(parts):
+                h[q * n:(q + 1) * n] = part.numpy()
+            seg.upload(h)
+        self.n_ag = getattr(self, "n_ag", 0) + 1
+        return buf
+
+    def wait_next_gather(self):
+        pass
 
     def join(self):
         pass

@@ -9,41 +9,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_max
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _run(world, out, worker="_gloo_worker.py"):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r),
-                   OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=600)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()                      # exactly the processes started here
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return np.load(out)
+from gloo_world import free_port, run_world
 
 
 @pytest.mark.timeout(900)
 def test_sharded_solvers_match_unsharded(tmp_path):
-    one = _run(1, str(tmp_path / "w1.npz"))
-    two = _run(2, str(tmp_path / "w2.npz"))
+    one = run_world("_gloo_worker.py", 1, str(tmp_path / "w1.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
+    two = run_world("_gloo_worker.py", 2, str(tmp_path / "w2.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
     assert rel_max(two["rec"], one["rec"]) < 1e-5           # float32 sums in a different order, nothing else
     assert np.allclose(two["err"], one["err"], rtol=1e-5)
     assert rel_max(two["crec"], one["crec"]) < 1e-5
@@ -78,7 +50,7 @@ def test_sharded_solvers_match_unsharded(tmp_path):
     for w in (one, two):
         assert float(w["rank_spread"]) < 1e-12 and np.allclose(w["err_gt_sharded"], one["err_gt_sharded"], rtol=1e-5) and np.allclose(w["err_gt_allreduce"], one["err_gt_sharded"], rtol=1e-5)
     # world 3: slabs that do not split evenly -- pieces by reduce-scatter, the < 3 left-over voxels of a slab by a small all-reduce
-    three = _run(3, str(tmp_path / "w3.npz"))
+    three = run_world("_gloo_worker.py", 3, str(tmp_path / "w3.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
     assert bool(three["pipelined"]) and int(three["n_rs"]) == 3 * n_it and 0 < int(three["n_slab_sirt"]) <= 3 * n_it
     assert int(three["slab_sizes"].sum()) == 32 ** 3 and int(three["slab_sizes"].min()) < 3
     assert rel_max(three["rec"], one["rec"]) < 1e-5 and np.allclose(three["err"], one["err"], rtol=1e-5)
@@ -108,9 +80,9 @@ def test_align_rigid_outer_loop_sharded_matches_unsharded(tmp_path):
     aligning its own projections against the replicated reconstruction, twice.  Each HALF of each outer iteration equals the unsharded
     loop's on the same inputs (SIRT: 1e-5, float32 sums in another order; alignment pass: exactly -- same evaluations, same optimiser);
     every rank ends with the same pose table; a rank uploads only its own measured rows; the loop recovers the injected shifts."""
-    one = _run(1, str(tmp_path / "e1.npz"))
-    two = _run(2, str(tmp_path / "e2.npz"))
-    three = _run(3, str(tmp_path / "e3.npz"))
+    one = run_world("_gloo_worker.py", 1, str(tmp_path / "e1.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
+    two = run_world("_gloo_worker.py", 2, str(tmp_path / "e2.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
+    three = run_world("_gloo_worker.py", 3, str(tmp_path / "e3.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
     for w in (one, two, three):
         for stage in (0, 1):
             assert float(w["st_sirt%d_rec" % stage]) < 1e-5 and float(w["st_sirt%d_err" % stage]) < 1e-5, (stage, float(w["st_sirt%d_rec" % stage]))
@@ -136,8 +108,8 @@ def test_world_8_sirt_cgls_and_outer_loop(tmp_path):
       * SIRT and CGLS, pipelined, equal to the one-rank run at 1e-5; the collective counts per iteration; the same counts on every rank;
       * one outer iteration of examples/align_rigid.run(comm=): every rank ends with the same pose table, each half equals the unsharded loop's,
         a rank uploads only its own measured rows."""
-    one = _run(1, str(tmp_path / "h1.npz"), "_gloo_worker8.py")
-    eight = _run(8, str(tmp_path / "h8.npz"), "_gloo_worker8.py")
+    one = run_world("_gloo_worker8.py", 1, str(tmp_path / "h1.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
+    eight = run_world("_gloo_worker8.py", 8, str(tmp_path / "h8.npz"), timeout=600, env={"OMP_NUM_THREADS": "1"})
     assert list(eight["block_sizes"]) == [3, 3, 3, 3, 2, 2, 2, 2] and list(one["block_sizes"]) == [20]
     assert [np.array_split(np.arange(720), 8)[r].size for r in range(8)] == [90] * 8 and [np.array_split(np.arange(1024), 8)[r].size for r in range(8)] == [128] * 8
     # the slab plan: 8 slabs of 15, 16 x 6 and 12 x planes, together the volume
@@ -187,7 +159,7 @@ def test_id_rendezvous_between_processes():
     bytes -- and a listener left behind by an EARLIER launch (another key) on the first candidate port, which must be told
     apart and skipped (a stale id must never be read)."""
     from tomography_alignment_amd import comm as tcomm
-    base = _free_port()
+    base = free_port()
     stale = socket.socket()
     try:
         stale.bind(("127.0.0.1", tcomm.candidate_ports(base)[0]))

@@ -1,17 +1,13 @@
 """FBP on the GPU: the HIP ramp filter of libtomo_fbp.so against the float64 model (tests/fbp_model.py), recon/fbp.py's FBP against the
 model through the CPU oracle's adjoint, its accuracy on a blob phantom, the warm start of SIRT and of examples/align_rigid, and the
 angle-sharded FBP at world 2 on one GPU."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import fbp_model as fm
-from conftest import ROOT, rel_max
+from conftest import rel_max
 from fbp_model import pair_err, pair_errs
+from gloo_world import run_world
 from oracle import oracle as orc
 
 from tomography_alignment_amd import _fbp_lib, _lib
@@ -385,32 +381,9 @@ def test_align_rigid_init_fbp():
         align_rigid.run(dict(d), n_outer=1, sirt_iters=1, verbose=False, init="ones")
 
 
-def _run_world(world, out):
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_gpu_fbp_worker.py"), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=300)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return [np.load(out + ".rank%d.npz" % r) for r in range(world)]
-
-
 def test_sharded_fbp_world_2_on_one_gpu(tmp_path):
-    one = _run_world(1, str(tmp_path / "w1"))[0]
-    two = _run_world(2, str(tmp_path / "w2"))
+    one = run_world("_gloo_gpu_fbp_worker.py", 1, str(tmp_path / "w1"), timeout=300, per_rank=True)[0]
+    two = run_world("_gloo_gpu_fbp_worker.py", 2, str(tmp_path / "w2"), timeout=300, per_rank=True)
     assert two[0]["ramp_rows"].size + two[1]["ramp_rows"].size == one["ramp_rows"].size
     for filt in ("ramp", "hann"):
         for r in range(2):

@@ -2,17 +2,12 @@
 numpy model bit for bit on exactly summable data, the prolongation is within float32 rounding of the float64 model, device residency with
 no leaked buffers, the consistency of a level with the full-size problem, levels=1 against `run`, the capture range beyond the bounds of
 the plain loop, and world 2 on one GPU.  Every test prints the figure it asserts on."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import pyr_model as pm
-from conftest import ROOT
 from fbp_model import blob_phantom
+from gloo_world import run_world
 
 from tomography_alignment_amd import _lib, _pyr_lib, multires
 from tomography_alignment_amd.backend import HipBackend
@@ -245,35 +240,12 @@ def test_capture_range_beyond_the_bounds_of_the_plain_loop():
     assert e_pyr <= 1.5 * CAPTURE_SHIFT_ERR_PX and tilt_pyr <= 1.5 * CAPTURE_TILT_ERR_DEG
 
 
-def _run_world(world, out):
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_gpu_multires_worker.py"), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=300)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return [np.load(out + ".rank%d.npz" % r) for r in range(world)]
-
-
 def test_sharded_run_multires_world_2_on_one_gpu(tmp_path):
     """What tests/test_gpu_dist.py allows the composed sharded align_rigid run: every rank ends with the same pose table, the first SIRT's
     RMSE is the unsharded one at 1e-5, and the loop reduces the shift error well below what was injected.  (The composition amplifies the
     last bits of the reconstruction, so the poses of the two worlds are printed, not held to float32 accuracy.)"""
-    one = _run_world(1, str(tmp_path / "w1"))[0]
-    two = _run_world(2, str(tmp_path / "w2"))
+    one = run_world("_gloo_gpu_multires_worker.py", 1, str(tmp_path / "w1"), timeout=300, per_rank=True)[0]
+    two = run_world("_gloo_gpu_multires_worker.py", 2, str(tmp_path / "w2"), timeout=300, per_rank=True)
     assert list(one["factor"]) == [4, 4, 2, 2, 1, 1] and list(one["ranks"]) == [1] * 6
     for r, w in enumerate(two):
         assert list(w["factor"]) == [4, 4, 2, 2, 1, 1] and list(w["ranks"]) == [2] * 6 and float(w["spread"]) == 0.0

@@ -2,14 +2,12 @@
 HipBackend, the fused passes of csrc/tomo_reg.hip against numpy (sizes, alignments, bit-reproducible sums), tomo_tv_prox_det against
 tomo_tv_denoise_fista, world 2 on one GPU, a 1-rank RCCL run, examples/mpi_reconstruct.py and a 256^3 x 256 TV-FISTA run."""
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, golden, rel_max
+from conftest import golden, rel_max
+from gloo_world import run_world
 from reg_standin import G14_CASES, SHARD_CASES, g14_options, g14_problem, shard_problem
 
 pytestmark = pytest.mark.gpu
@@ -137,32 +135,9 @@ def test_tv_prox_det_equals_tv_denoise_fista_on_g9():
     ctx.close()
 
 
-def _run_world(world, out):
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_gpu_reg_worker.py"), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=300)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return [np.load(out + ".rank%d.npz" % r) for r in range(world)]
-
-
 def test_sharded_world_2_on_one_gpu(tmp_path):
-    one = _run_world(1, str(tmp_path / "w1"))[0]
-    two = _run_world(2, str(tmp_path / "w2"))
+    one = run_world("_gloo_gpu_reg_worker.py", 1, str(tmp_path / "w1"), timeout=300, per_rank=True)[0]
+    two = run_world("_gloo_gpu_reg_worker.py", 2, str(tmp_path / "w2"), timeout=300, per_rank=True)
     for tag, _, _ in SHARD_CASES:
         for gt in (0, 1):
             key = "%s_%d" % (tag, gt)

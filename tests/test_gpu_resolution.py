@@ -1,16 +1,11 @@
 """GPU tests of the Fourier shell correlation (tomography_alignment_amd/resolution.py, libtomo_fsc.so) against the numpy model
 tests/fsc_model.py: exact shell counts, the curve at the scale float32 transforms allow, bit-identical repeats, device residency, the
 batched 2-D form, the half-set FSC of an alignment problem (one GPU and world 2 over gloo) and the driver's --fsc."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import fsc_model as fm
-from conftest import ROOT
+from gloo_world import run_world
 
 from tomography_alignment_amd import _fsc_lib, _lib, resolution
 from tomography_alignment_amd.examples import align_rigid, generate_data
@@ -278,34 +273,11 @@ def test_half_set_fsc_tells_true_poses_from_uncorrected_ones():
     ctx.close()
 
 
-def _run_world(world, out):
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_gpu_fsc_worker.py"), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=300)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return [np.load(out + ".rank%d.npz" % r) for r in range(world)]
-
-
 def test_half_set_fsc_world_2_on_one_gpu(tmp_path):
     """World 2 sums each half's volume over the ranks in float32 (tests/test_gpu_fbp.py: 1e-6 rel_max against world 1), so the curves
     agree at the scale of those roundings averaged over a shell (_refbp_tol)."""
-    one = _run_world(1, str(tmp_path / "w1"))[0]
-    two = _run_world(2, str(tmp_path / "w2"))
+    one = run_world("_gloo_gpu_fsc_worker.py", 1, str(tmp_path / "w1"), timeout=300, per_rank=True)[0]
+    two = run_world("_gloo_gpu_fsc_worker.py", 2, str(tmp_path / "w2"), timeout=300, per_rank=True)
     assert np.array_equal(two[0]["table"], two[1]["table"])            # both ranks hold the same all-reduced volumes: the same bits
     for key in ("host", "device"):
         for r in range(2):

@@ -2,18 +2,12 @@
 stand-in backend (tests/reg_standin.py) against the reference's own class (golden G14, tests/golden/make_golden_g14.py), the Armijo
 restatement against scipy's, the decisions on the reference's defects, and the angle-sharded class over gloo at worlds 1, 2, 3 and one
 world larger than the number of angles."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from conftest import golden, rel_max
+from gloo_world import run_world
 from reg_standin import (G14_CASES, RegOracleBackend, SHARD_CASES, SHARD_NPROJ, g14_options, g14_problem, shard_problem)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _serial(geo, b, angles, xyz, opts):
@@ -120,39 +114,10 @@ def test_tikh_f_fp_on_any_operator():
     assert np.allclose(regularized.my_tikh_fp(x, A, b, 0.7), A.T.dot(r) + 0.7 * x)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _run_world(world, out):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r),
-                   OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_reg_worker.py"), out], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
-    try:
-        for p in procs:
-            logs.append(p.communicate(timeout=600)[0].decode())
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, log in zip(procs, logs):
-        assert p.returncode == 0, log
-    return [np.load(out + ".rank%d.npz" % r) for r in range(world)]
-
-
 @pytest.mark.parametrize("world", [1, 2, 3, SHARD_NPROJ + 1])
 def test_sharded_regularized_matches_unsharded_gloo(tmp_path, world):
     geo, b, angles, xyz, x = shard_problem()
-    ranks = _run_world(world, str(tmp_path / "reg"))
+    ranks = run_world("_gloo_reg_worker.py", world, str(tmp_path / "reg"), timeout=600, per_rank=True, env={"OMP_NUM_THREADS": "1"})
     for tag, meth, kw in SHARD_CASES:
         for gt in (False, True):
             key = "%s_%d" % (tag, int(gt))
