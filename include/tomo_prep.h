@@ -18,6 +18,30 @@
  *               at the angles they came from.  n_proj <= TOMO_PREP_MAX_NPROJ, 3 <= size <= min(ndx, 63), size odd.  z is processed in
  *               chunks whose scratch (10 bytes per sinogram value of the chunk) fits max_scratch_bytes (0: no limit); the result does not
  *               depend on the chunking.  d_out may alias d_in; partial overlap is not allowed.
+ *   detector    the stripe detector the next two share, one z row at a time, in float64: the float32 factors f[x] (NaN and +inf read as
+ *               FLT_MAX, -inf as -FLT_MAX) are sorted descending into d; nd = ndx / 4; a least-squares line through (i, d[i]),
+ *               nd <= i < ndx - nd - 1, by the closed form with centred abscissae (xm the mean index, ym = sum d / count, slope
+ *               m = sum (i - xm)(d[i] - ym) / sum (i - xm)^2, each sum in ascending i, intercept c = ym - m xm); t1 = c + m (ndx - 1),
+ *               noise = max(|t1 - c|, 1e-6), v1 = |d[0] - c| / noise, v2 = |d[ndx - 1] - t1| / noise.  v1 >= snr masks every x with
+ *               f[x] > c + (0.5 snr) noise; v2 >= snr masks every x with f[x] <= t1 - (0.5 snr) noise; the mask is then dilated by one
+ *               column on each side.  8 <= ndx <= 8192 (one row of factors is sorted in LDS).
+ *   large       large-stripe removal (Vo algorithm 5): the columns are sorted along the angles and the sorted rows median-filtered
+ *               along x (window `size`) exactly as in `stripe`; nd = int(0.5 clip(drop_ratio, 0, 0.8) n_proj); over the ranks
+ *               nd <= r < n_proj - nd, l1[x] and l2[x] are the float64 sums, in rank order, of the sorted and of the smoothed values,
+ *               each divided by the count, and f[x] = l2 != 0 ? float32(l1 / l2) : 1.  The detector masks columns.  If norm, every
+ *               value becomes s[a][x] / f[x] (IEEE float32 division); in a masked column it becomes the smoothed value at the rank the
+ *               angle had in the sort (the paper re-sorts the normalised column; the ranks are the same whenever f > 0 and the division
+ *               merges no two distinct values).
+ *   dead        dead-stripe removal (Vo algorithm 6), n_proj >= 10: u[a][x] = float32(sum_{k = a-5 .. a+4} double(s[k][x]) / 10) with
+ *               half-sample-symmetric reflection at the ends, diff[x] = float32(sum_a double(|s[a][x] - u[a][x]|)) in angle order, bck
+ *               the reflected median of diff along x (window `size`), f = bck != 0 ? diff / bck : 1.  The detector masks columns; the
+ *               first two and the last two columns are then cleared.  A masked column is interpolated along x at the same angle
+ *               between the nearest unmasked columns xl < x < xr: s[xl] + (s[xr] - s[xl]) * (float(x - xl) / float(xr - xl)) in float32
+ *               without contraction.  If norm, `large` (same snr and size, drop_ratio 0.1, norm) runs on the result.
+ *   all         `dead` (la_size, norm) followed by `stripe` (sm_size), chunk by chunk on one scratch.
+ *               large, dead and all share stripe's limits, chunk z with 10 bytes per value plus 13 bytes per (x, z) of scratch
+ *               (tomo_prep_stripe_all_chunk), do not depend on the chunking, run on the caller's stream without a host round trip, and
+ *               accept d_out == d_in.  A mask pointer is NULL or ndx * ndz bytes [x][z] that receive the detector's (dilated) mask.
  *
  * A handle owns one device, the stripe scratch and the last error; one handle is used by one thread at a time.  Every entry point returns
  * a tomo_prep_status and checks its arguments before it launches anything; on failure tomo_prep_last_error(h) says why (h may be NULL
@@ -42,13 +66,16 @@ extern "C" {
 #define TOMO_PREP_MAX_NPROJ 8192         /* one 64-bit sort key per angle in LDS */
 #define TOMO_PREP_MAX_MEDIAN_FRAMES 64   /* reference frames by median */
 #define TOMO_PREP_MAX_STRIPE_SIZE 63
+#define TOMO_PREP_MIN_STRIPE_NDX 8       /* large / dead / all: the detector's line fit needs a middle half */
+#define TOMO_PREP_MAX_STRIPE_NDX 8192    /* large / dead / all: one row of factors is sorted in LDS */
+#define TOMO_PREP_MIN_DEAD_NPROJ 10      /* dead / all: the 10-angle window */
 
 typedef enum {
     TOMO_PREP_OK = 0,
     TOMO_PREP_ERR_ARG = 1,          /* bad argument (shape, dtype, NULL pointer, window) */
     TOMO_PREP_ERR_HIP = 2,          /* a HIP runtime call failed */
     TOMO_PREP_ERR_NODEV = 3,        /* no HIP device */
-    TOMO_PREP_ERR_UNSUPPORTED = 4   /* n_proj > TOMO_PREP_MAX_NPROJ, or a median over more than 64 frames */
+    TOMO_PREP_ERR_UNSUPPORTED = 4   /* n_proj > TOMO_PREP_MAX_NPROJ, ndx > TOMO_PREP_MAX_STRIPE_NDX, or a median over more than 64 frames */
 } tomo_prep_status;
 
 typedef enum { TOMO_PREP_U16 = 0, TOMO_PREP_F32 = 1 } tomo_prep_dtype;
@@ -74,6 +101,17 @@ TOMO_API int tomo_prep_stripe_chunk(int n_proj, int ndx, int ndz, size_t max_scr
  * and the scatter passes summed over the chunks -- the call then synchronises the stream (benchmarks only). */
 TOMO_API int tomo_prep_stripe_sorting(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, int size,
                                       size_t max_scratch_bytes, float *pass_ms);
+/* The z rows per chunk of tomo_prep_stripe_large / _dead / _all (their scratch per z row is larger than the sorting pass's). */
+TOMO_API int tomo_prep_stripe_all_chunk(int n_proj, int ndx, int ndz, size_t max_scratch_bytes, int *chunk_z);
+/* Large-stripe removal.  snr > 0; size as in tomo_prep_stripe_sorting; d_mask: NULL or ndx * ndz bytes. */
+TOMO_API int tomo_prep_stripe_large(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                    int size, float drop_ratio, int norm, size_t max_scratch_bytes, uint8_t *d_mask);
+/* Dead-stripe removal.  d_mask_large (NULL or ndx * ndz bytes) receives the mask of the closing large-stripe pass when norm is set. */
+TOMO_API int tomo_prep_stripe_dead(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                   int size, int norm, size_t max_scratch_bytes, uint8_t *d_mask, uint8_t *d_mask_large);
+/* dead (la_size, norm) then sorting (sm_size). */
+TOMO_API int tomo_prep_stripe_all(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                  int la_size, int sm_size, size_t max_scratch_bytes, uint8_t *d_mask_dead, uint8_t *d_mask_large);
 
 #ifdef __cplusplus
 }

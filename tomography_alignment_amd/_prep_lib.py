@@ -23,6 +23,8 @@ MEAN, MEDIAN = 0, 1       # TOMO_PREP_MEAN, TOMO_PREP_MEDIAN
 MAX_NPROJ = 8192          # TOMO_PREP_MAX_NPROJ
 MAX_MEDIAN_FRAMES = 64
 MAX_STRIPE_SIZE = 63
+MIN_STRIPE_NDX, MAX_STRIPE_NDX = 8, 8192      # TOMO_PREP_MIN_STRIPE_NDX, TOMO_PREP_MAX_STRIPE_NDX (large / dead / all)
+MIN_DEAD_NPROJ = 10       # TOMO_PREP_MIN_DEAD_NPROJ
 
 # every symbol include/tomo_prep.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -35,11 +37,19 @@ SIGNATURES = {
                                      _c_int, _c_float, _c_int, _c_float, _c_vp]),
     "tomo_prep_stripe_chunk": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_size_t, ctypes.POINTER(_c_int)]),
     "tomo_prep_stripe_sorting": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, ctypes.c_size_t, _c_fp]),
+    "tomo_prep_stripe_all_chunk": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_size_t, ctypes.POINTER(_c_int)]),
+    "tomo_prep_stripe_large": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_int,
+                                        ctypes.c_size_t, _c_vp]),
+    "tomo_prep_stripe_dead": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int, ctypes.c_size_t,
+                                       _c_vp, _c_vp]),
+    "tomo_prep_stripe_all": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int, ctypes.c_size_t,
+                                      _c_vp, _c_vp]),
 }
 
 
 class PrepUnsupported(TomoError):
-    """A shape the kernels do not support: more than 8192 angles for the stripe removal, or a median over more than 64 frames."""
+    """A shape the kernels do not support: more than 8192 angles for the stripe removal (or, for the large- and dead-stripe passes, more
+    than 8192 columns), or a median over more than 64 frames."""
 
 
 def load():
@@ -52,6 +62,14 @@ def stripe_chunk(n_proj, ndx, ndz, max_scratch_bytes=0):
     lib = load()
     zc = _c_int(0)
     _binding.check(lib, "prep", lib.tomo_prep_stripe_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)))
+    return zc.value
+
+
+def stripe_all_chunk(n_proj, ndx, ndz, max_scratch_bytes=0):
+    """The z rows per chunk tomo_prep_stripe_large / _dead / _all use for this shape and scratch budget (0: no limit)."""
+    lib = load()
+    zc = _c_int(0)
+    _binding.check(lib, "prep", lib.tomo_prep_stripe_all_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)))
     return zc.value
 
 
@@ -80,3 +98,22 @@ class PrepHandle(Handle):
         self._check(self.lib.tomo_prep_stripe_sorting(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
                                                       int(size), int(max_scratch_bytes), ms))
         return tuple(ms) if timed else None
+
+    def stripe_large(self, stream, d_in, d_out, n_proj, ndx, ndz, snr, size, drop_ratio, norm, max_scratch_bytes=0, d_mask=None):
+        """Enqueue the large-stripe removal; d_mask: None or ndx * ndz bytes for the detector's mask."""
+        self._check(self.lib.tomo_prep_stripe_large(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
+                                                    float(snr), int(size), float(drop_ratio), 1 if norm else 0, int(max_scratch_bytes),
+                                                    _ptr(d_mask)))
+
+    def stripe_dead(self, stream, d_in, d_out, n_proj, ndx, ndz, snr, size, norm, max_scratch_bytes=0, d_mask=None, d_mask_large=None):
+        """Enqueue the dead-stripe removal (with norm: followed by the large-stripe pass, whose mask goes to d_mask_large)."""
+        self._check(self.lib.tomo_prep_stripe_dead(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
+                                                   float(snr), int(size), 1 if norm else 0, int(max_scratch_bytes), _ptr(d_mask),
+                                                   _ptr(d_mask_large)))
+
+    def stripe_all(self, stream, d_in, d_out, n_proj, ndx, ndz, snr, la_size, sm_size, max_scratch_bytes=0, d_mask_dead=None,
+                   d_mask_large=None):
+        """Enqueue dead (la_size, norm) then sorting (sm_size)."""
+        self._check(self.lib.tomo_prep_stripe_all(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
+                                                  float(snr), int(la_size), int(sm_size), int(max_scratch_bytes), _ptr(d_mask_dead),
+                                                  _ptr(d_mask_large)))

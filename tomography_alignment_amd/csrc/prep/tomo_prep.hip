@@ -14,6 +14,13 @@
 //                      16 x, the window of `size` keys in registers, exact selection by counting.
 //   k_stripe_scatter   (K3) the inverse of K1: the filtered values are scattered to their angles in LDS and written coalesced.
 // Every key is unique (the angle is part of it), so the sort is the stable order numpy's argsort(kind='stable') gives.
+// large and dead stripes (Vo algorithms 5 and 6), per chunk, on top of K1-K3 (a further 13 bytes of scratch per (x, z): three factor
+// lists and the mask):
+//   k_large_factor     (K4) per (x, z) the float64 means of the sorted and of the smoothed values over the kept ranks, and their ratio.
+//   k_dead_diff        (K5) per (x, z) the summed distance of a column from its 10-angle running mean, the window in registers.
+//   k_stripe_detect    (K6) per z: the factors sorted in LDS, a float64 line fit through the middle half, two thresholds, dilation.
+//   k_large_correct    (K7) K3 with a choice per column: the smoothed value at the angle's rank (masked), or in / factor, or a copy.
+//   k_dead_interp      (K8) masked columns interpolated along x between the nearest unmasked ones.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +43,10 @@ constexpr int SCATTER_T = 256;
 constexpr int MED_TZ = 64, MED_TX = 64, MED_T = 256;      // K2 tile: 64 z x 64 x, 4 threads along x each doing 16
 constexpr int NORM_TILE = 64, NORM_T = 256, NORM_FR = 16;     // k_normalize: 64 x 64 tile, 16 frames per work-group
 constexpr int REF_T = 256;
+constexpr int DET_T = 256;             // the stripe detector: one work-group per z row, ndx <= SORT_KEYS 32-bit keys in LDS
+constexpr int COL_T = 256;             // the per-(x, z) kernels of the large- and dead-stripe passes
+constexpr int DEAD_TAPS = 10;          // the angle window of the dead-stripe statistic
+constexpr int INTERP_AY = 32;          // angle groups of k_dead_interp
 constexpr int MAX_LDS = (SORT_KEYS + MAX_ZC) * 8;         // the largest dynamic LDS any kernel here asks for
 
 // orderable bits: unsigned order = float order; -0 is canonicalised to +0 first, every NaN maps to one key above +inf
@@ -246,6 +257,182 @@ __global__ __launch_bounds__(SCATTER_T) void k_stripe_scatter(const float *__res
     }
 }
 
+// ---- large and dead stripes (Vo algorithms 5 and 6).  Per chunk the factor lists and the mask are [x][zl] (zl fastest, cols = ndx zw
+// values).  Every kernel below fixes the order of its float64 sums, so a numpy model repeats it.  The library is built with
+// -ffp-contract=fast, under which the backend fuses a multiply with a following add whatever a pragma says: a product that must be
+// rounded on its own goes through f_mul / d_mul, whose empty asm hides it from that fusion.
+__device__ __forceinline__ float f_mul(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
+__device__ __forceinline__ double d_mul(double a, double b) { double p = a * b; asm volatile("" : "+v"(p)); return p; }
+
+// K4.  One thread per (x, zl): the float64 means over the ranks r0 <= r < r1 of the sorted and of the smoothed values, and their ratio.
+__global__ __launch_bounds__(COL_T) void k_large_factor(const float *__restrict__ S, const float *__restrict__ M, float *__restrict__ f,
+                                                         int r0, int r1, size_t cols) {
+    const size_t t = (size_t)blockIdx.x * COL_T + threadIdx.x;
+    if (t >= cols) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int r = r0; r < r1; ++r) {
+        s1 += (double)S[(size_t)r * cols + t];
+        s2 += (double)M[(size_t)r * cols + t];
+    }
+    const double cnt = (double)(r1 - r0), l1 = s1 / cnt, l2 = s2 / cnt;
+    f[t] = l2 != 0.0 ? (float)(l1 / l2) : 1.f;
+}
+
+// K5.  One thread per (x, zl) walks the angles with the 10 values of the window a - 5 ... a + 4 (reflected) in registers:
+// u = float32(sum of the window in float64, in angle order, / 10), diff = float32(sum_a double(|s - u|)).
+__global__ __launch_bounds__(COL_T) void k_dead_diff(const float *__restrict__ p, float *__restrict__ diff, int n, int ndx, int ndz, int zb,
+                                                      int zw) {
+    const size_t t = (size_t)blockIdx.x * COL_T + threadIdx.x;
+    if (t >= (size_t)ndx * zw) return;
+    const int x = (int)(t / zw), zl = (int)(t % zw);
+    const float *col = p + (size_t)x * ndz + zb + zl;
+    const size_t stride = (size_t)ndx * ndz;
+    float w[DEAD_TAPS];
+#pragma unroll
+    for (int j = 0; j < DEAD_TAPS; ++j) w[j] = col[(size_t)reflect(j - DEAD_TAPS / 2, n) * stride];
+    double acc = 0.0;
+    for (int a = 0; a < n; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < DEAD_TAPS; ++j) s += (double)w[j];
+        const float u = (float)(s / (double)DEAD_TAPS);
+        acc += (double)fabsf(w[DEAD_TAPS / 2] - u);
+#pragma unroll
+        for (int j = 0; j + 1 < DEAD_TAPS; ++j) w[j] = w[j + 1];
+        w[DEAD_TAPS - 1] = col[(size_t)reflect(a + DEAD_TAPS / 2, n) * stride];
+    }
+    diff[t] = (float)acc;
+}
+
+__global__ __launch_bounds__(COL_T) void k_dead_factor(const float *__restrict__ diff, const float *__restrict__ bck, float *__restrict__ f,
+                                                        size_t cols) {
+    const size_t t = (size_t)blockIdx.x * COL_T + threadIdx.x;
+    if (t < cols) f[t] = bck[t] != 0.f ? diff[t] / bck[t] : 1.f;
+}
+
+// the detector reads a factor as a finite float32: NaN and +inf count as the largest value, -inf as the smallest
+__device__ __forceinline__ float finite_factor(float v) {
+    if (v != v) return 3.402823466e+38f;
+    return fminf(fmaxf(v, -3.402823466e+38f), 3.402823466e+38f);
+}
+
+// K6, the stripe detector.  One work-group per zl: the ndx factors as orderable keys in LDS (padded with 0, below every finite key, to
+// a power of two Np), sorted ascending by a bitonic network and read from the top; thread 0 fits the line through the middle half
+// in float64 in one fixed order; every thread thresholds its columns, the mask is dilated by one column in LDS.
+__global__ __launch_bounds__(DET_T) void k_stripe_detect(const float *__restrict__ f, uint8_t *__restrict__ mk, uint8_t *__restrict__ d_mask,
+                                                          int ndx, int ndz, int zb, int zw, int logNp, float snr_f, int clear_edges) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint32_t *keys = reinterpret_cast<uint32_t *>(smem);
+    __shared__ double thr[2];
+    __shared__ int fire[2];
+    const int Np = 1 << logNp, zl = blockIdx.x;
+    for (int x = threadIdx.x; x < Np; x += DET_T) keys[x] = x < ndx ? ord_bits(finite_factor(f[(size_t)x * zw + zl])) : 0u;
+    __syncthreads();
+    for (int k = 2; k <= Np; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < Np / 2; t += DET_T) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+                const bool asc = (i & k) == 0;
+                const uint32_t u = keys[i], v = keys[l];
+                if ((u > v) == asc) {
+                    keys[i] = v;
+                    keys[l] = u;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) {              // d[i], descending, is keys[Np - 1 - i]
+        const double snr = (double)snr_f;
+        const int nd = ndx / 4, i0 = nd, i1 = ndx - nd - 1, cnt = i1 - i0;
+        const double xm = 0.5 * (double)(i0 + i1 - 1);
+        double sy = 0.0;
+        for (int i = i0; i < i1; ++i) sy += (double)from_ord(keys[Np - 1 - i]);
+        const double ym = sy / (double)cnt;
+        double sxy = 0.0, sxx = 0.0;
+        for (int i = i0; i < i1; ++i) {
+            const double dx = (double)i - xm;
+            sxy += d_mul(dx, (double)from_ord(keys[Np - 1 - i]) - ym);
+            sxx += d_mul(dx, dx);
+        }
+        const double m = sxy / sxx, c = ym - d_mul(m, xm), t1 = c + d_mul(m, (double)(ndx - 1));
+        const double noise = fmax(fabs(t1 - c), 1e-6);
+        const double v1 = fabs((double)from_ord(keys[Np - 1]) - c) / noise, v2 = fabs((double)from_ord(keys[Np - ndx]) - t1) / noise;
+        fire[0] = v1 >= snr;
+        fire[1] = v2 >= snr;
+        thr[0] = c + d_mul(0.5 * snr, noise);
+        thr[1] = t1 - d_mul(0.5 * snr, noise);
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < ndx; x += DET_T) {
+        const double g = (double)finite_factor(f[(size_t)x * zw + zl]);
+        keys[x] = ((fire[0] && g > thr[0]) || (fire[1] && g <= thr[1])) ? 1u : 0u;
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < ndx; x += DET_T) {
+        uint32_t r = keys[x] | (x > 0 ? keys[x - 1] : 0u) | (x + 1 < ndx ? keys[x + 1] : 0u);
+        if (clear_edges && (x < 2 || x >= ndx - 2)) r = 0u;
+        mk[(size_t)x * zw + zl] = (uint8_t)r;
+        if (d_mask) d_mask[(size_t)x * ndz + zb + zl] = (uint8_t)r;
+    }
+}
+
+// K7, K3 with a choice per column.  A masked column takes the smoothed value at the rank its angle had in K1's sort (scattered through
+// LDS as in K3); every other column is divided by its factor (norm) or copied.  `in` may be `out`: a thread reads what it writes.
+__global__ __launch_bounds__(SCATTER_T) void k_large_correct(const float *in, const float *__restrict__ M, const uint16_t *__restrict__ P,
+                                                              const float *__restrict__ f, const uint8_t *__restrict__ mk, float *out, int n,
+                                                              int ndx, int ndz, int zb, int zw, int ZC, int norm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *vals = reinterpret_cast<float *>(smem);
+    const int x = blockIdx.x, zg = blockIdx.y * ZC;
+    for (int e = threadIdx.x; e < ZC * n; e += SCATTER_T) {
+        const int c = e % ZC, r = e / ZC, zl = zg + c;
+        if (zl < zw && mk[(size_t)x * zw + zl]) {
+            const size_t o = ((size_t)r * ndx + x) * zw + zl;
+            vals[c * (n + 1) + P[o]] = M[o];
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < ZC * n; e += SCATTER_T) {
+        const int c = e % ZC, a = e / ZC, zl = zg + c;
+        if (zl >= zw) continue;
+        const size_t i = ((size_t)a * ndx + x) * ndz + zb + zl, q = (size_t)x * zw + zl;
+        float v;
+        if (mk[q]) v = vals[c * (n + 1) + a];
+        else v = norm ? in[i] / f[q] : in[i];
+        out[i] = v;
+    }
+}
+
+// K8.  One thread per (x, zl), angles strided over blockIdx.y.  A masked column is interpolated in float32, the product rounded on its own, between
+// the nearest unmasked columns xl < x < xr of the same angle (they exist: the mask's first and last two columns are clear); an
+// unmasked column is copied, or left alone when `in` is `out` -- so the columns read here are never written.
+__global__ __launch_bounds__(COL_T) void k_dead_interp(const float *in, const uint8_t *__restrict__ mk, float *out, int n, int ndx, int ndz,
+                                                        int zb, int zw) {
+    const size_t t = (size_t)blockIdx.x * COL_T + threadIdx.x;
+    if (t >= (size_t)ndx * zw) return;
+    const int x = (int)(t / zw), zl = (int)(t % zw);
+    const bool m = mk[t] != 0;
+    if (!m && in == out) return;
+    int xl = x, xr = x;
+    if (m) {
+        while (xl > 0 && mk[(size_t)xl * zw + zl]) --xl;
+        while (xr < ndx - 1 && mk[(size_t)xr * zw + zl]) ++xr;
+    }
+    const float w = m ? (float)(x - xl) / (float)(xr - xl) : 0.f;
+    for (int a = blockIdx.y; a < n; a += gridDim.y) {
+        const size_t base = (size_t)a * ndx * ndz + zb + zl;
+        float v;
+        if (m) {
+            const float l = in[base + (size_t)xl * ndz], r = in[base + (size_t)xr * ndz];
+            v = l + f_mul(r - l, w);
+        } else {
+            v = in[base + (size_t)x * ndz];
+        }
+        out[base + (size_t)x * ndz] = v;
+    }
+}
+
 }  // namespace
 
 struct tomo_prep {
@@ -332,6 +519,143 @@ int reference_t(tomo_prep *h, hipStream_t st, const T *in, int n, size_t npix, i
     HIPCHK(h, hipGetLastError());
     return TOMO_PREP_OK;
 }
+
+// ---- large and dead stripes: the scratch of one chunk and the passes over it (all enqueued, no host round trip)
+struct Chunk {
+    float *S, *M, *f, *diff, *bck;     // S, M: [rank][x][zl]; f, diff, bck: [x][zl]
+    uint16_t *P;
+    uint8_t *mk;
+};
+
+constexpr size_t VAL_BYTES = 10, COL_BYTES = 13;      // scratch per sinogram value, and per (x, z) on top of it
+
+int chunk_for_all(int n_proj, int ndx, int ndz, size_t budget) {
+    if (budget == 0) return ndz;
+    const size_t per_z = (VAL_BYTES * (size_t)n_proj + COL_BYTES) * (size_t)ndx;
+    size_t zc = budget / per_z;
+    if (zc >= (size_t)ndz) return ndz;
+    if (zc >= 64) zc -= zc % 64;
+    return zc < 1 ? 1 : (int)zc;
+}
+
+// what every pass of the large / dead / all family checks before anything is launched
+int check_stripe(tomo_prep *h, const char *who, const void *d_in, const void *d_out, int n_proj, int ndx, int ndz, float snr, int size,
+                 int min_nproj) {
+    const std::string w(who);
+    if (!h) return fail(h, TOMO_PREP_ERR_ARG, w + ": NULL handle");
+    if (n_proj > TOMO_PREP_MAX_NPROJ)
+        return fail(h, TOMO_PREP_ERR_UNSUPPORTED, w + ": n_proj " + std::to_string(n_proj) + " > " + std::to_string(TOMO_PREP_MAX_NPROJ) +
+                                                      " (one 64-bit key per angle in LDS); nothing was written");
+    if (ndx > SORT_KEYS)
+        return fail(h, TOMO_PREP_ERR_UNSUPPORTED, w + ": ndx " + std::to_string(ndx) + " > " + std::to_string(SORT_KEYS) +
+                                                      " (the detector sorts one row of factors in LDS); nothing was written");
+    if (n_proj < min_nproj || ndx < TOMO_PREP_MIN_STRIPE_NDX || ndz < 1)
+        return fail(h, TOMO_PREP_ERR_ARG, w + ": bad shape (n_proj >= " + std::to_string(min_nproj) + ", ndx >= 8, ndz >= 1)");
+    if (size < 3 || size % 2 == 0 || size > TOMO_PREP_MAX_STRIPE_SIZE || size > ndx)
+        return fail(h, TOMO_PREP_ERR_ARG, w + ": size must be odd with 3 <= size <= min(ndx, 63)");
+    if (!(snr > 0.f) || !(snr <= 3.402823466e+38f)) return fail(h, TOMO_PREP_ERR_ARG, w + ": snr must be finite and > 0");
+    if (!d_in || !d_out) return fail(h, TOMO_PREP_ERR_ARG, w + ": NULL pointer");
+    if ((long long)n_proj * ndx >= (1LL << 31) / 10 || ndz > 65535)
+        return fail(h, TOMO_PREP_ERR_ARG, w + ": shape too large (n_proj * ndx < 2^31 / 10, ndz <= 65535)");
+    return TOMO_PREP_OK;
+}
+
+// the handle's scratch for chunks of zc rows, safe to write on stream st
+int chunk_scratch(tomo_prep *h, hipStream_t st, int n_proj, int ndx, int zc, Chunk &c) {
+    const size_t nchunk = (size_t)n_proj * ndx * zc, cols = (size_t)ndx * zc;
+    const size_t need = nchunk * VAL_BYTES + cols * COL_BYTES;
+    if (h->pending && (need > h->scratch.n || st != h->last_stream)) CHK(drain(h));
+    CHK(grow(h, h->scratch, need));
+    static bool attr = false;
+    if (!attr) {
+        CHK(allow_lds(h, k_stripe_sort));
+        CHK(allow_lds(h, k_stripe_scatter));
+        CHK(allow_lds(h, k_large_correct));
+        attr = true;
+    }
+    c.S = static_cast<float *>(h->scratch.p);
+    c.M = c.S + nchunk;
+    c.f = c.M + nchunk;
+    c.diff = c.f + cols;
+    c.bck = c.diff + cols;
+    c.P = reinterpret_cast<uint16_t *>(c.bck + cols);
+    c.mk = reinterpret_cast<uint8_t *>(c.P + nchunk);
+    return TOMO_PREP_OK;
+}
+
+int scratch_used(tomo_prep *h, hipStream_t st) {
+    HIPCHK(h, hipEventRecord(h->ev_done, st));
+    h->pending = true;
+    h->last_stream = st;
+    return TOMO_PREP_OK;
+}
+
+int sort_pass(tomo_prep *h, hipStream_t st, const float *in, const Chunk &c, int n, int ndx, int ndz, int zb, int zw) {
+    const int logNp = ilog2_ceil(n), Np = 1 << logNp;
+    const int zc1 = std::min(MAX_ZC, std::max(1, SORT_KEYS / Np));
+    hipLaunchKernelGGL(k_stripe_sort, dim3((unsigned)ndx, (unsigned)((zw + zc1 - 1) / zc1)), dim3(SORT_T),
+                       (size_t)zc1 * (Np + 1) * sizeof(uint64_t), st, in, c.S, c.P, n, ndx, ndz, zb, zw, logNp, zc1);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+int detect_pass(tomo_prep *h, hipStream_t st, const Chunk &c, int ndx, int ndz, int zb, int zw, float snr, int clear_edges, uint8_t *d_mask) {
+    const int logNp = ilog2_ceil(ndx);
+    hipLaunchKernelGGL(k_stripe_detect, dim3((unsigned)zw), dim3(DET_T), (size_t)(1 << logNp) * sizeof(uint32_t), st, c.f, c.mk, d_mask, ndx,
+                       ndz, zb, zw, logNp, snr, clear_edges);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+unsigned col_blocks(int ndx, int zw) { return (unsigned)(((size_t)ndx * zw + COL_T - 1) / COL_T); }
+
+// algorithm 5 on the rows zb ... zb + zw of `in` into `out` (which may be `in`)
+int large_chunk(tomo_prep *h, hipStream_t st, const float *in, float *out, int n, int ndx, int ndz, int zb, int zw, float snr, int size,
+                int nd, int norm, uint8_t *d_mask, const Chunk &c) {
+    CHK(sort_pass(h, st, in, c, n, ndx, ndz, zb, zw));
+    CHK(median(h, st, c.S, c.M, n, ndx, zw, size));
+    hipLaunchKernelGGL(k_large_factor, dim3(col_blocks(ndx, zw)), dim3(COL_T), 0, st, c.S, c.M, c.f, nd, n - nd, (size_t)ndx * zw);
+    HIPCHK(h, hipGetLastError());
+    CHK(detect_pass(h, st, c, ndx, ndz, zb, zw, snr, 0, d_mask));
+    const int zc3 = std::min(MAX_ZC, std::max(1, SCATTER_VALS / n));
+    hipLaunchKernelGGL(k_large_correct, dim3((unsigned)ndx, (unsigned)((zw + zc3 - 1) / zc3)), dim3(SCATTER_T),
+                       (size_t)zc3 * (n + 1) * sizeof(float), st, in, c.M, c.P, c.f, c.mk, out, n, ndx, ndz, zb, zw, zc3, norm);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+// algorithm 6 (without its closing large-stripe pass) on the rows zb ... zb + zw
+int dead_chunk(tomo_prep *h, hipStream_t st, const float *in, float *out, int n, int ndx, int ndz, int zb, int zw, float snr, int size,
+               uint8_t *d_mask, const Chunk &c) {
+    const unsigned blocks = col_blocks(ndx, zw);
+    hipLaunchKernelGGL(k_dead_diff, dim3(blocks), dim3(COL_T), 0, st, in, c.diff, n, ndx, ndz, zb, zw);
+    HIPCHK(h, hipGetLastError());
+    CHK(median(h, st, c.diff, c.bck, 1, ndx, zw, size));
+    hipLaunchKernelGGL(k_dead_factor, dim3(blocks), dim3(COL_T), 0, st, c.diff, c.bck, c.f, (size_t)ndx * zw);
+    HIPCHK(h, hipGetLastError());
+    CHK(detect_pass(h, st, c, ndx, ndz, zb, zw, snr, 1, d_mask));
+    hipLaunchKernelGGL(k_dead_interp, dim3(blocks, (unsigned)std::min(n, INTERP_AY)), dim3(COL_T), 0, st, in, c.mk, out, n, ndx, ndz, zb, zw);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+// algorithm 3 in place on the rows zb ... zb + zw of `out`
+int sorting_chunk(tomo_prep *h, hipStream_t st, float *out, int n, int ndx, int ndz, int zb, int zw, int size, const Chunk &c) {
+    CHK(sort_pass(h, st, out, c, n, ndx, ndz, zb, zw));
+    CHK(median(h, st, c.S, c.M, n, ndx, zw, size));
+    const int zc3 = std::min(MAX_ZC, std::max(1, SCATTER_VALS / n));
+    hipLaunchKernelGGL(k_stripe_scatter, dim3((unsigned)ndx, (unsigned)((zw + zc3 - 1) / zc3)), dim3(SCATTER_T),
+                       (size_t)zc3 * (n + 1) * sizeof(float), st, c.M, c.P, out, n, ndx, ndz, zb, zw, zc3);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+int drop_ranks(float drop_ratio, int n_proj) {
+    const double dr = std::min(std::max((double)drop_ratio, 0.0), 0.8);
+    return (int)(0.5 * dr * (double)n_proj);
+}
+
+constexpr float DEAD_DROP_RATIO = 0.1f;      // the large-stripe pass that closes the dead-stripe pass keeps Vo's default
 
 }  // namespace
 
@@ -482,6 +806,60 @@ TOMO_API int tomo_prep_stripe_sorting(tomo_prep *h, void *stream, const float *d
     h->pending = true;
     h->last_stream = st;
     return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_stripe_all_chunk(int n_proj, int ndx, int ndz, size_t max_scratch_bytes, int *chunk_z) {
+    if (!chunk_z || n_proj < 1 || ndx < 1 || ndz < 1) return fail(nullptr, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_all_chunk: bad args");
+    *chunk_z = chunk_for_all(n_proj, ndx, ndz, max_scratch_bytes);
+    return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_stripe_large(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                    int size, float drop_ratio, int norm, size_t max_scratch_bytes, uint8_t *d_mask) {
+    CHK(check_stripe(h, "tomo_prep_stripe_large", d_in, d_out, n_proj, ndx, ndz, snr, size, 1));
+    if (!(drop_ratio == drop_ratio)) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_stripe_large: drop_ratio is NaN");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int zc = chunk_for_all(n_proj, ndx, ndz, max_scratch_bytes), nd = drop_ranks(drop_ratio, n_proj);
+    Chunk c;
+    CHK(chunk_scratch(h, st, n_proj, ndx, zc, c));
+    for (int zb = 0; zb < ndz; zb += zc)
+        CHK(large_chunk(h, st, d_in, d_out, n_proj, ndx, ndz, zb, std::min(zc, ndz - zb), snr, size, nd, norm, d_mask, c));
+    return scratch_used(h, st);
+}
+
+TOMO_API int tomo_prep_stripe_dead(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                   int size, int norm, size_t max_scratch_bytes, uint8_t *d_mask, uint8_t *d_mask_large) {
+    CHK(check_stripe(h, "tomo_prep_stripe_dead", d_in, d_out, n_proj, ndx, ndz, snr, size, TOMO_PREP_MIN_DEAD_NPROJ));
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int zc = chunk_for_all(n_proj, ndx, ndz, max_scratch_bytes), nd = drop_ranks(DEAD_DROP_RATIO, n_proj);
+    Chunk c;
+    CHK(chunk_scratch(h, st, n_proj, ndx, zc, c));
+    for (int zb = 0; zb < ndz; zb += zc) {
+        const int zw = std::min(zc, ndz - zb);
+        CHK(dead_chunk(h, st, d_in, d_out, n_proj, ndx, ndz, zb, zw, snr, size, d_mask, c));
+        if (norm) CHK(large_chunk(h, st, d_out, d_out, n_proj, ndx, ndz, zb, zw, snr, size, nd, 1, d_mask_large, c));
+    }
+    return scratch_used(h, st);
+}
+
+TOMO_API int tomo_prep_stripe_all(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
+                                  int la_size, int sm_size, size_t max_scratch_bytes, uint8_t *d_mask_dead, uint8_t *d_mask_large) {
+    CHK(check_stripe(h, "tomo_prep_stripe_all", d_in, d_out, n_proj, ndx, ndz, snr, la_size, TOMO_PREP_MIN_DEAD_NPROJ));
+    CHK(check_stripe(h, "tomo_prep_stripe_all", d_in, d_out, n_proj, ndx, ndz, snr, sm_size, TOMO_PREP_MIN_DEAD_NPROJ));
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int zc = chunk_for_all(n_proj, ndx, ndz, max_scratch_bytes), nd = drop_ranks(DEAD_DROP_RATIO, n_proj);
+    Chunk c;
+    CHK(chunk_scratch(h, st, n_proj, ndx, zc, c));
+    for (int zb = 0; zb < ndz; zb += zc) {
+        const int zw = std::min(zc, ndz - zb);
+        CHK(dead_chunk(h, st, d_in, d_out, n_proj, ndx, ndz, zb, zw, snr, la_size, d_mask_dead, c));
+        CHK(large_chunk(h, st, d_out, d_out, n_proj, ndx, ndz, zb, zw, snr, la_size, nd, 1, d_mask_large, c));
+        CHK(sorting_chunk(h, st, d_out, n_proj, ndx, ndz, zb, zw, sm_size, c));
+    }
+    return scratch_used(h, st);
 }
 
 }  // extern "C"

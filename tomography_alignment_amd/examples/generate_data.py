@@ -10,6 +10,10 @@ With raw=True (--raw) the file also holds what a detector gives for the same pro
 (uint16 [n_proj][z][x]), `flats` and `darks` (uint16 stacks of frames) and `mu`, the attenuation per unit of `projections` (the line
 integral the counts encode is mu * projections).  counts = Poisson(I0 * gain * exp(-mu p)) + dark, with a per-pixel gain shared by flats
 and projections, and a few detector columns whose gain in the projections differs from the flats' by a few percent: the stripes.
+dead_columns=K (--dead-columns K) and gain_columns=K (--gain-columns K) add the defects the sorting-based removal leaves and
+preprocess.remove_all_stripe handles: K columns stuck at a count of their own in every projection, and K columns whose gain in the
+projections is 25 % above the flats'.  They are drawn from a generator of their own, so with both at 0 the frames are those of earlier
+versions for the same seed.
 With propagate=A (--propagate A) the noiseless transmission exp(-mu p) is first carried over a propagation distance: the forward model
 of preprocess.retrieve_phase with strength A (pixels^2), which puts a bright/dark fringe pair on every edge.
 
@@ -40,10 +44,27 @@ def tie_propagate(T, strength):
     return r[..., ox:ox + nx, oz:oz + nz]
 
 
-def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03, propagate=None):
+DEFECT_GAIN = 1.25        # the gain of a gain column in the projections, relative to the flats
+
+
+def defect_columns(nx, dead_columns, gain_columns, seed=None):
+    """(dead, gain): distinct column indices at least 4 columns from the detector's edges and 3 columns from each other."""
+    k = int(dead_columns) + int(gain_columns)
+    if dead_columns < 0 or gain_columns < 0 or 3 * k > nx - 8:
+        raise ValueError("dead_columns + gain_columns must be >= 0 and fit 3 columns apart into %d - 8 columns, got %d + %d"
+                         % (nx, dead_columns, gain_columns))
+    rng = np.random.default_rng(None if seed is None else [int(seed), 0xdead])
+    slots = rng.permutation((nx - 8) // 3)[:k] * 3 + 4
+    return np.sort(slots[:int(dead_columns)]), np.sort(slots[int(dead_columns):])
+
+
+def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03, propagate=None,
+             dead_columns=0, gain_columns=0):
     """Detector frames of the projections proj [n_proj][nx][nz]: dict(counts, flats, darks, mu) (module docstring).  mu defaults to
     4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor.  propagate: the strength of the propagation
-    applied to the noiseless transmission (None or 0: none, and the frames are those of earlier versions for the same seed)."""
+    applied to the noiseless transmission (None or 0: none, and the frames are those of earlier versions for the same seed).
+    dead_columns, gain_columns: how many stuck and how many mis-gained columns to add (module docstring); with any, the dict also holds
+    their indices as dead_cols and gain_cols."""
     if propagate is not None and not (np.isfinite(propagate) and propagate >= 0):
         raise ValueError("propagate must be a finite strength >= 0 or None, got %r" % (propagate,))
     rng = np.random.default_rng(seed)
@@ -63,13 +84,22 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
     if propagate:
         att = np.clip(tie_propagate(att, float(propagate)), 0.0, None)
     att = att.transpose(0, 2, 1)                                          # [n][z][x]
+    dead, gained = defect_columns(nx, dead_columns, gain_columns, seed) if (dead_columns or gain_columns) else ((), ())
+    if len(gained):
+        drift = drift.copy()
+        drift[gained] *= DEFECT_GAIN
     counts = frames(i0 * gain * drift * att)
     flats = frames(np.broadcast_to(i0 * gain, (n_flat, nz, nx)))
     darks = np.clip(rng.poisson(np.broadcast_to(np.maximum(dark_mean, 0), (n_dark, nz, nx))), 0, 65535).astype(np.uint16)
-    return dict(counts=counts, flats=flats, darks=darks, mu=np.float64(mu))
+    out = dict(counts=counts, flats=flats, darks=darks, mu=np.float64(mu))
+    if len(dead) or len(gained):
+        for j, c in enumerate(dead):                                     # stuck: one count per column, between dark and half the flat
+            counts[:, :, c] = np.uint16(round(dark_level + i0 * (0.2 + 0.3 * (j + 1) / (len(dead) + 1))))
+        out.update(dead_cols=np.asarray(dead, np.int64), gain_cols=np.asarray(gained, np.int64))
+    return out
 
 
-def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None):
+def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0):
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
     shepp = generate_phantom.shepp3d(nx)
@@ -87,7 +117,8 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, pr
     proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
     d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
     if raw:
-        d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate))   # a generator of its own: the other keys do not change
+        d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate, dead_columns=dead_columns,
+                          gain_columns=gain_columns))                  # a generator of its own: the other keys do not change
     return d
 
 
@@ -100,10 +131,15 @@ def main():
     ap.add_argument("--raw", action="store_true", help="also write detector counts, flats and darks (examples/preprocess.py)")
     ap.add_argument("--propagate", type=float, default=None, metavar="A",
                     help="with --raw: propagate the transmission with strength A pixels^2 before the counts are drawn (phase-contrast fringes)")
+    ap.add_argument("--dead-columns", type=int, default=0, metavar="K", help="with --raw: K detector columns stuck at a count")
+    ap.add_argument("--gain-columns", type=int, default=0, metavar="K",
+                    help="with --raw: K columns whose gain in the projections is 25 %% above the flats'")
     a = ap.parse_args()
     if a.propagate is not None and not a.raw:
         ap.error("--propagate needs --raw")
-    d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate)
+    if (a.dead_columns or a.gain_columns) and not a.raw:
+        ap.error("--dead-columns and --gain-columns need --raw")
+    d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

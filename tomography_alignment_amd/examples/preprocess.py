@@ -10,6 +10,10 @@ For data recorded with a propagation distance, `phase` (--phase-strength A, or -
 Paganin's single-distance phase retrieval between the flat-field division and the -log: normalize(minus_log=False) -> retrieve_phase
 -> stripe removal.  Without it the calls and the result are what they were before the option existed.
 
+`--stripe all` replaces the sorting-based removal by preprocess.remove_all_stripe -- dead stripes, large stripes, then the sorting pass
+with --stripe-size as its window -- for detectors with stuck or mis-gained columns (generate_data --dead-columns / --gain-columns);
+`--stripe none` skips the removal.  The default, `--stripe sorting`, is the sorting pass alone.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -26,14 +30,30 @@ import numpy as np
 
 from .. import _lib, preprocess
 
-RAW_KEYS = ("counts", "flats", "darks", "mu")
+RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols")
+STRIPE_MODES = ("sorting", "all", "none")
+LA_SIZE = 61              # the window of the dead- and large-stripe passes of --stripe all, where the detector is wide enough
 PHASE_KEYS = ("strength", "pixel_size", "dist", "energy", "wavelength", "delta_beta", "pad", "min_ratio", "max_scratch_bytes")
 
 
-def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None):
+def la_size_for(nx, la_size=None):
+    """The window of the dead- and large-stripe passes: la_size if given, else 61 or the largest odd number the detector allows."""
+    if la_size is not None:
+        return int(la_size)
+    return min(LA_SIZE, nx if nx % 2 else nx - 1)
+
+
+def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
+        la_size=None):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
-    energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log."""
+    energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
+    sorting pass alone), 'all' (remove_all_stripe with snr stripe_snr, la_size -- default la_size_for(nx) -- and sm_size = stripe_size)
+    or 'none'."""
+    if stripe not in STRIPE_MODES:
+        raise ValueError("preprocess: stripe must be one of %s, got %r" % (", ".join(STRIPE_MODES), stripe))
+    if stripe == "all" and not stripe_size:
+        raise ValueError("preprocess: stripe='all' needs a stripe_size (the window of its sorting pass)")
     if phase is not None:
         unknown = sorted(set(phase) - set(PHASE_KEYS))
         if unknown:
@@ -55,7 +75,9 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         d_frames.free()
         if phase is not None:
             p.retrieve_phase(sino, out=sino, **phase)                                                     # in place; applies the -log
-        if stripe_size:
+        if stripe == "all":
+            p.remove_all_stripe(sino, snr=stripe_snr, la_size=la_size_for(sino.shape[1], la_size), sm_size=stripe_size, out=sino)
+        elif stripe == "sorting" and stripe_size:
             p.remove_stripe_sorting(sino, size=stripe_size, out=sino)                                    # in place, on the device
         proj = sino.download()
     finally:
@@ -70,8 +92,9 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     out = {k: v for k, v in data.items() if k not in RAW_KEYS}
     out["projections"] = proj
     if verbose:
-        print("preprocess: %s counts -> projections %s (stripe window %s, phase retrieval %s)"
-              % (counts.shape, proj.shape, stripe_size or "off", phase if phase is not None else "off"))
+        print("preprocess: %s counts -> projections %s (stripe removal %s, window %s, phase retrieval %s)"
+              % (counts.shape, proj.shape, stripe, (stripe_size or "off") if stripe != "none" else "off",
+                 phase if phase is not None else "off"))
     return out
 
 
@@ -80,6 +103,11 @@ def parse_args(argv=None):
     ap.add_argument("data", help=".npz with counts, flats, darks (generate_data --raw)")
     ap.add_argument("--out", default="data.npz")
     ap.add_argument("--stripe-size", type=int, default=21, help="odd window of the stripe removal; 0 skips it")
+    ap.add_argument("--stripe", choices=STRIPE_MODES, default="sorting",
+                    help="sorting: the sorting pass alone; all: dead, large and sorting passes (remove_all_stripe); none: skip")
+    ap.add_argument("--stripe-snr", type=float, default=3.0, help="with --stripe all: the detector's threshold")
+    ap.add_argument("--stripe-la-size", type=int, default=None,
+                    help="with --stripe all: odd window of the dead- and large-stripe passes (default 61, or what the detector allows)")
     ap.add_argument("--method", choices=("mean", "median"), default="mean", help="how flats and darks are reduced")
     ap.add_argument("--cutoff", type=float, default=None, help="upper bound of the flat-field ratio before the log")
     ap.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Z0", "Z1", "X0", "X1"), help="detector window")
@@ -104,6 +132,12 @@ def parse_args(argv=None):
         a.phase = physical
     if a.stripe_size and (a.stripe_size < 3 or a.stripe_size % 2 == 0):
         ap.error("--stripe-size must be 0 or an odd number >= 3")
+    if not (a.stripe_snr > 0 and a.stripe_snr < float("inf")):
+        ap.error("--stripe-snr must be finite and > 0")
+    if a.stripe == "all" and not a.stripe_size:
+        ap.error("--stripe all needs a --stripe-size (the window of its sorting pass)")
+    if a.stripe_la_size is not None and (a.stripe_la_size < 3 or a.stripe_la_size % 2 == 0):
+        ap.error("--stripe-la-size must be an odd number >= 3")
     if a.crop is not None:
         a.crop = ((a.crop[0], a.crop[1]), (a.crop[2], a.crop[3]))
     return a
@@ -111,7 +145,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase)
+    d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
+            stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 

@@ -1,8 +1,9 @@
 """
 Preprocessing of raw projections on the GPU (libtomo_prep.so, include/tomo_prep.h): reference frames, flat-field normalisation with the
-transpose into the package's sinogram layout, and sorting-based stripe removal.  The first step of the pipeline
+transpose into the package's sinogram layout, and stripe removal (sorting-based, large stripes, dead stripes, and the three combined).
+The first step of the pipeline
 
-    raw counts --normalize--> sinogram --remove_stripe_sorting--> align.align_cc / recon.fbp / examples.align_rigid
+    raw counts --normalize--> sinogram --remove_stripe_sorting / remove_all_stripe--> align.align_cc / recon.fbp / examples.align_rigid
 
 Layouts.  Raw frames, flats and darks are [n][rows = z][cols = x] (x fastest), uint16 or float32, uploaded in their own dtype.  The
 sinogram is float32 p[n_proj][nx][nz] with z, the rotation axis, fastest -- what FBP, SIRT and OuterLoop read (OuterLoop takes the
@@ -35,6 +36,29 @@ Limits: n_proj <= 8192 (one 64-bit key per angle in LDS; more raises PrepUnsuppo
 3 <= size <= min(nx, 63).  z is processed in chunks whose scratch (10 bytes per sinogram value: sorted values, filtered values, uint16
 permutation) fits max_scratch_bytes (default 2 GiB); the result does not depend on the chunking.  The removal needs every angle of a
 column, so it runs on the full stack on one GPU; ranks that each hold a block of angles can still call normalize on their own frames.
+
+Large, dead and all stripes (remove_large_stripe, remove_dead_stripe, remove_all_stripe): algorithms 5 and 6 of the same paper and their
+combination, for what the sorting pass leaves: columns whose gain is wrong over the whole scan, and columns that are stuck or fluctuate.
+Both build a float32 factor per column (x, z) and share one detector, which works on one z row at a time in float64:
+    detector   factors f[x] (NaN and +inf read as FLT_MAX, -inf as -FLT_MAX) sorted descending into d; nd = nx // 4; a least-squares line
+               through (i, d[i]), nd <= i < nx - nd - 1 (closed form, centred abscissae, sums in ascending i): intercept c, slope m;
+               t1 = c + m (nx - 1), noise = max(|t1 - c|, 1e-6), v1 = |d[0] - c| / noise, v2 = |d[nx-1] - t1| / noise.  If v1 >= snr every
+               x with f[x] > c + 0.5 snr noise is masked; if v2 >= snr every x with f[x] <= t1 - 0.5 snr noise; the mask is dilated by
+               one column on each side.  snr is used as a float32.
+    large      sort and median-filter (window `size`) as in the sorting pass; nd = int(0.5 clip(drop_ratio, 0, 0.8) n_proj); l1, l2 =
+               float64 means, in rank order, of the sorted and of the smoothed values over the ranks nd <= r < n_proj - nd;
+               f = l2 != 0 ? float32(l1 / l2) : 1.  With norm every value is divided by its column's f (IEEE float32); a masked column
+               takes the smoothed value at the rank its angle had in the sort.  (The paper sorts the normalised column again; the ranks
+               are the same whenever f > 0 and the division merges no two distinct values.)
+    dead       n_proj >= 10.  u[a] = float32(sum_{k=a-5..a+4} double(s[k]) / 10) (reflected at the ends), diff[x] = float32(sum_a
+               double(|s[a] - u[a]|)), bck = reflected median of diff along x (window `size`), f = bck != 0 ? diff / bck : 1.  After
+               the detector the first and last two columns are unmasked; a masked column is interpolated along x, at the same angle,
+               between the nearest unmasked columns xl < x < xr: s[xl] + (s[xr] - s[xl]) * (float(x - xl) / float(xr - xl)) in float32,
+               every operation rounded on its own.  With norm the large pass (same snr and size, drop_ratio 0.1, norm) follows.
+    all        dead (la_size, norm) then the sorting pass (sm_size).
+Limits: those of the sorting pass, and 8 <= nx <= 8192 (the detector sorts one row of factors in LDS; more raises PrepUnsupported before
+anything is uploaded).  The scratch is 10 bytes per value plus 13 per column (x, z) of a chunk; the result does not depend on the chunking.
+return_mask=True also returns the detector's dilated mask(s) as boolean (nx, nz) arrays.
 
 Phase retrieval (retrieve_phase; libtomo_phase.so, include/tomo_phase.h): Paganin's single-distance filter, the step between the
 flat-field division and the -log for data recorded with a propagation distance:
@@ -163,6 +187,46 @@ def _float32_stack(proj):
     if dtype != np.float32:
         raise ValueError("proj must be float32, got %s" % dtype)
     return shape
+
+
+def _check_window(size, nx, name="size"):
+    if isinstance(size, (bool, np.bool_)) or int(size) != size:
+        raise ValueError("%s must be an odd integer, got %r" % (name, size))
+    size = int(size)
+    if size % 2 == 0 or size < 3 or size > min(nx, _prep_lib.MAX_STRIPE_SIZE):
+        raise ValueError("%s must be odd with 3 <= %s <= min(nx, 63) = %d, got %d" % (name, name, min(nx, _prep_lib.MAX_STRIPE_SIZE), size))
+    return size
+
+
+def _check_stripe_args(proj, snr, out, max_scratch_bytes, min_nproj, what):
+    """(shape, float32 snr, budget) of a large / dead / all call, or ValueError / PrepUnsupported: nothing is uploaded before this."""
+    shape = _float32_stack(proj)
+    n, nx, nz = shape
+    if n < min_nproj:
+        raise ValueError("%s needs n_proj >= %d, got %d" % (what, min_nproj, n))
+    if nx < _prep_lib.MIN_STRIPE_NDX:
+        raise ValueError("%s needs nx >= %d, got %d" % (what, _prep_lib.MIN_STRIPE_NDX, nx))
+    if n > _prep_lib.MAX_NPROJ or nx > _prep_lib.MAX_STRIPE_NDX:
+        raise PrepUnsupported("%s: n_proj %d, nx %d exceed the %d angles / %d columns one work-group sorts in LDS; nothing was written"
+                              % (what, n, nx, _prep_lib.MAX_NPROJ, _prep_lib.MAX_STRIPE_NDX))
+    try:
+        snr32 = np.float32(snr)
+        ok = not isinstance(snr, (bool, np.bool_)) and bool(np.isfinite(snr32) and snr32 > 0)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("snr must be finite and > 0 (in float32), got %r" % (snr,))
+    budget = DEFAULT_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+    if budget < 0:
+        raise ValueError("max_scratch_bytes must be >= 0 (0: no limit)")
+    if out is not None:
+        if not (_is_dev(out) and out.dtype == np.float32 and out.size == n * nx * nz):
+            raise ValueError("out must be a float32 DeviceArray of %d values" % (n * nx * nz))
+        if _is_dev(proj) and out.ptr.value != proj.ptr.value:
+            a0, b0 = proj.ptr.value, out.ptr.value
+            if a0 < b0 + out.nbytes and b0 < a0 + proj.nbytes:
+                raise ValueError("out must be proj itself or not overlap it")
+    return shape, float(snr32), budget
 
 
 class Preprocessor(HandleOwner):
@@ -316,6 +380,77 @@ class Preprocessor(HandleOwner):
             self._free(temps)
         return (result, ms) if timed else result
 
+    def _run_stripe(self, proj, shape, out, n_masks, call):
+        """Upload / allocate as remove_stripe_sorting does, run call(d_in, d_out, masks) with n_masks zeroed uint8 (nx, nz) device
+        buffers, and return (result, mask, ...) with the masks as boolean ndarrays."""
+        self._ready(proj)
+        temps = []
+        try:
+            d_in = self._upload(proj, temps)
+            res = out
+            if res is None:
+                res = self.ctx.empty(shape, np.float32)
+                if not _is_dev(proj):
+                    temps.append(res)
+            try:
+                masks = []
+                for _ in range(n_masks):
+                    masks.append(self.ctx.zeros(shape[1:], np.uint8))
+                    temps.append(masks[-1])
+                call(d_in, res, [m.ptr for m in masks])
+                host_masks = tuple(m.download().astype(bool) for m in masks)
+            except Exception:
+                if out is None and _is_dev(proj):
+                    res.free()
+                raise
+            result = res if _is_dev(proj) else res.download()
+        finally:
+            self._free(temps)
+        return (result,) + host_masks if n_masks else result
+
+    def remove_large_stripe(self, proj, snr=3.0, size=51, drop_ratio=0.1, norm=True, out=None, max_scratch_bytes=None, return_mask=False):
+        """Large-stripe removal (Vo algorithm 5; module docstring) of the sinogram proj [n_proj][nx][nz] (float32).  Host in: an ndarray
+        out.  Device in: the result goes to `out` (`out=proj` works in place) or a new DeviceArray.  return_mask=True: (result, mask)."""
+        shape, snr, budget = _check_stripe_args(proj, snr, out, max_scratch_bytes, 1, "remove_large_stripe")
+        n, nx, nz = shape
+        size = _check_window(size, nx)
+        try:
+            drop_ratio = float(drop_ratio)
+        except (TypeError, ValueError):
+            drop_ratio = float("nan")
+        if not math.isfinite(drop_ratio):
+            raise ValueError("drop_ratio must be a finite number (it is clipped to 0 ... 0.8)")
+
+        def call(d_in, d_out, masks):
+            self.handle.stripe_large(self.ctx.stream(), d_in.ptr, d_out.ptr, n, nx, nz, snr, size, drop_ratio, norm, budget,
+                                     masks[0] if masks else None)
+
+        return self._run_stripe(proj, shape, out, 1 if return_mask else 0, call)
+
+    def remove_dead_stripe(self, proj, snr=3.0, size=51, norm=True, out=None, max_scratch_bytes=None, return_mask=False):
+        """Dead-stripe removal (Vo algorithm 6; module docstring), n_proj >= 10.  Conventions as remove_large_stripe; the mask is that
+        of the dead-stripe detector."""
+        shape, snr, budget = _check_stripe_args(proj, snr, out, max_scratch_bytes, _prep_lib.MIN_DEAD_NPROJ, "remove_dead_stripe")
+        n, nx, nz = shape
+        size = _check_window(size, nx)
+
+        def call(d_in, d_out, masks):
+            self.handle.stripe_dead(self.ctx.stream(), d_in.ptr, d_out.ptr, n, nx, nz, snr, size, norm, budget, masks[0] if masks else None)
+
+        return self._run_stripe(proj, shape, out, 1 if return_mask else 0, call)
+
+    def remove_all_stripe(self, proj, snr=3.0, la_size=61, sm_size=21, out=None, max_scratch_bytes=None, return_mask=False):
+        """Dead stripes, large stripes (window la_size) and the sorting pass (window sm_size) in one call, chunk by chunk on one scratch.
+        Conventions as remove_large_stripe; return_mask=True: (result, dead mask, large mask)."""
+        shape, snr, budget = _check_stripe_args(proj, snr, out, max_scratch_bytes, _prep_lib.MIN_DEAD_NPROJ, "remove_all_stripe")
+        n, nx, nz = shape
+        la_size, sm_size = _check_window(la_size, nx, "la_size"), _check_window(sm_size, nx, "sm_size")
+
+        def call(d_in, d_out, masks):
+            self.handle.stripe_all(self.ctx.stream(), d_in.ptr, d_out.ptr, n, nx, nz, snr, la_size, sm_size, budget, *masks)
+
+        return self._run_stripe(proj, shape, out, 2 if return_mask else 0, call)
+
     def _ready_phase(self, like):
         self._ready_ctx(like)
         if self._phase is None:
@@ -424,6 +559,36 @@ def remove_stripe_sorting(proj, size=21, ctx=None, out=None, max_scratch_bytes=N
     p = Preprocessor(ctx)
     try:
         return p.remove_stripe_sorting(proj, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
+    finally:
+        p.close()
+
+
+def remove_large_stripe(proj, snr=3.0, size=51, drop_ratio=0.1, norm=True, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
+    """Large-stripe removal: Preprocessor.remove_large_stripe on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.remove_large_stripe(proj, snr=snr, size=size, drop_ratio=drop_ratio, norm=norm, out=out,
+                                     max_scratch_bytes=max_scratch_bytes, return_mask=return_mask)
+    finally:
+        p.close()
+
+
+def remove_dead_stripe(proj, snr=3.0, size=51, norm=True, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
+    """Dead-stripe removal: Preprocessor.remove_dead_stripe on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.remove_dead_stripe(proj, snr=snr, size=size, norm=norm, out=out, max_scratch_bytes=max_scratch_bytes,
+                                    return_mask=return_mask)
+    finally:
+        p.close()
+
+
+def remove_all_stripe(proj, snr=3.0, la_size=61, sm_size=21, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
+    """Dead, large and sorting-based stripe removal: Preprocessor.remove_all_stripe on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.remove_all_stripe(proj, snr=snr, la_size=la_size, sm_size=sm_size, out=out, max_scratch_bytes=max_scratch_bytes,
+                                   return_mask=return_mask)
     finally:
         p.close()
 

@@ -10,7 +10,9 @@ flat and dark tiles are read once per 16 frames); the rate is also given as a fr
 timed in the same process (a copy moves 2 x its bytes).  Stripe removal (size 21): per sinogram value the sort pass reads 4 B and writes
 6 B (value + uint16 rank), the median pass reads 4 B (plus the halo) and writes 4 B, the scatter pass reads 6 B and writes 4 B; the sort
 does Np log2(Np) (log2(Np) + 1) / 4 compare-exchanges per column (Np: n_proj rounded up to a power of two), each two 8-byte LDS reads and
-up to two 8-byte LDS writes."""
+up to two 8-byte LDS writes.  The large-, dead- and all-stripe passes (cases `large`, `dead`, `all`; snr 3, windows 51, 51 and 61 / --size)
+are timed whole, in place, on the same sinogram: each adds its statistics, the detector and a correction to the sort and median passes
+above (dead with norm and all run the large pass too)."""
 import argparse
 import json
 import math
@@ -27,7 +29,7 @@ def _emit(**kw):
     print(json.dumps(kw), flush=True)
 
 
-def case(n, rows, cols, reps, size):
+def case(n, rows, cols, reps, size, passes_wanted=("large", "dead", "all")):
     from tomography_alignment_amd import _lib, preprocess
 
     ctx = _lib.Context()
@@ -37,6 +39,7 @@ def case(n, rows, cols, reps, size):
     darks = np.full((1, rows, cols), 100, np.uint16)
     d_flats, d_darks = ctx.to_device(flats, np.uint16), ctx.to_device(darks, np.uint16)
     sino = ctx.empty((n, cols, rows), np.float32)
+    la = cols if cols % 2 else cols - 1                            # the widest odd window the detector allows
     copy_dst = ctx.empty((n, cols, rows), np.float32)
 
     def timed(fn):
@@ -64,6 +67,16 @@ def case(n, rows, cols, reps, size):
         passes.append(ms)
     passes = np.median(np.asarray(passes), axis=0)
     whole_ms, _ = timed(lambda: pre.remove_stripe_sorting(sino, size=size, out=sino))
+    extra = {}
+    runs = {"large": lambda: pre.remove_large_stripe(sino, size=min(51, la), out=sino),
+            "dead": lambda: pre.remove_dead_stripe(sino, size=min(51, la), out=sino),
+            "all": lambda: pre.remove_all_stripe(sino, la_size=min(61, la), sm_size=size, out=sino)}
+    for name in passes_wanted:
+        ms, ms_min = timed(runs[name])
+        extra[name + "_ms"] = round(ms, 2)
+        extra[name + "_min_ms"] = round(ms_min, 2)
+    if passes_wanted:
+        extra["stripe_all_chunk_z"] = preprocess._prep_lib.stripe_all_chunk(n, cols, rows, preprocess.DEFAULT_SCRATCH_BYTES)
     np2 = 1 << max(0, math.ceil(math.log2(n)))
     lg = int(math.log2(np2))
     cols_z = cols * rows                                         # sinogram columns (x, z)
@@ -77,7 +90,7 @@ def case(n, rows, cols, reps, size):
           sort_ms=round(float(passes[0]), 2), sort_GBps=round(moved["sort"] / (passes[0] * 1e-3) / 1e9, 1),
           sort_compare_exchanges=cex, sort_lds_GBps=round(32.0 * cex / (passes[0] * 1e-3) / 1e9, 1),
           median_ms=round(float(passes[1]), 2), median_GBps=round(moved["median"] / (passes[1] * 1e-3) / 1e9, 1),
-          scatter_ms=round(float(passes[2]), 2), scatter_GBps=round(moved["scatter"] / (passes[2] * 1e-3) / 1e9, 1))
+          scatter_ms=round(float(passes[2]), 2), scatter_GBps=round(moved["scatter"] / (passes[2] * 1e-3) / 1e9, 1), **extra)
     pre.close()
     ctx.close()
 
@@ -87,10 +100,12 @@ def main():
     ap.add_argument("--cases", nargs="*", default=["1024x1024x1024", "1800x2048x2048"], help="n_proj x rows x cols")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--size", type=int, default=21)
+    ap.add_argument("--passes", nargs="*", default=["large", "dead", "all"], choices=["large", "dead", "all"],
+                    help="the large- / dead- / all-stripe passes to time after the sorting pass (none: --passes with no value)")
     a = ap.parse_args()
     for c in a.cases:
         n, rows, cols = (int(v) for v in c.split("x"))
-        case(n, rows, cols, a.reps, a.size)
+        case(n, rows, cols, a.reps, a.size, tuple(a.passes))
 
 
 if __name__ == "__main__":
