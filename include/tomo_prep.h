@@ -42,10 +42,27 @@
  *               large, dead and all share stripe's limits, chunk z with 10 bytes per value plus 13 bytes per (x, z) of scratch
  *               (tomo_prep_stripe_all_chunk), do not depend on the chunking, run on the caller's stream without a host round trip, and
  *               accept d_out == d_in.  A mask pointer is NULL or ndx * ndz bytes [x][z] that receive the detector's (dilated) mask.
+ *   outlier     zinger removal and the 2-D median filter of a stack in[n][rows][cols] (cols fastest), uint16 or float32: raw frames
+ *               [n][z][x] and the float32 sinogram (n, nx, nz) alike.  size is 3, 5 or 7; rows >= size and cols >= size.  Per pixel v:
+ *               the window is the size x size values around it inside its own frame, with half-sample-symmetric reflection at the
+ *               edges (d c b a | a b c d, as in `stripe`; one reflection suffices).  uint16 is ordered by value, float32 by the
+ *               stripe sort's key (orderable bits, -0 read as +0, every NaN above +inf); med is the element of rank
+ *               (size * size - 1) / 2 decoded from its key, so a median of -0 is written as +0 and a NaN median as 0x7fc00000.
+ *               mode OUTLIER: d = float(v) - float(med), one IEEE float32 subtraction (exact for uint16); two_sided: d = fabsf(d);
+ *               the pixel becomes med if d >= dif or if v is not finite (float32 only), else it keeps its bits.  dif >= 0 and not
+ *               NaN; +inf only repairs non-finite pixels.  mode MEDIAN2D: every pixel becomes med; dif and two_sided are ignored.
+ *               d_count: NULL, or n uint32 that the call clears on the stream and that receive, per frame, the pixels replaced
+ *               (OUTLIER: those the test chose, whether or not med differs from v; MEDIAN2D: those whose bits changed), summed by
+ *               integer atomics, so they are deterministic.  d_out == d_in is allowed: frames then go in batches
+ *               (tomo_prep_outlier_batch) through handle-owned scratch bounded by max_scratch_bytes (0: no limit; never fewer than
+ *               one frame), each batch filtered into the scratch and copied back on the same stream; the result does not depend on
+ *               the batch.  Any other overlap is TOMO_PREP_ERR_ARG.  Everything runs on the caller's stream without a host round
+ *               trip.  TOMO_PREP_ERR_ARG, with nothing launched: a dtype, mode or size other than the above, rows or cols below
+ *               size, n < 1, rows * cols >= 2^31, a negative or NaN dif (OUTLIER), a NULL d_in or d_out.
  *
- * A handle owns one device, the stripe scratch and the last error; one handle is used by one thread at a time.  Every entry point returns
- * a tomo_prep_status and checks its arguments before it launches anything; on failure tomo_prep_last_error(h) says why (h may be NULL
- * for errors raised before a handle exists).
+ * A handle owns one device, the scratch (of the stripe passes and of the in-place outlier call) and the last error; one handle is used by
+ * one thread at a time.  Every entry point returns a tomo_prep_status and checks its arguments before it launches anything; on failure
+ * tomo_prep_last_error(h) says why (h may be NULL for errors raised before a handle exists).
  */
 #ifndef TOMO_PREP_H
 #define TOMO_PREP_H
@@ -69,6 +86,7 @@ extern "C" {
 #define TOMO_PREP_MIN_STRIPE_NDX 8       /* large / dead / all: the detector's line fit needs a middle half */
 #define TOMO_PREP_MAX_STRIPE_NDX 8192    /* large / dead / all: one row of factors is sorted in LDS */
 #define TOMO_PREP_MIN_DEAD_NPROJ 10      /* dead / all: the 10-angle window */
+#define TOMO_PREP_MAX_OUTLIER_SIZE 7     /* outlier: the window is 3, 5 or 7 on a side */
 
 typedef enum {
     TOMO_PREP_OK = 0,
@@ -80,6 +98,7 @@ typedef enum {
 
 typedef enum { TOMO_PREP_U16 = 0, TOMO_PREP_F32 = 1 } tomo_prep_dtype;
 typedef enum { TOMO_PREP_MEAN = 0, TOMO_PREP_MEDIAN = 1 } tomo_prep_method;
+typedef enum { TOMO_PREP_OUTLIER = 0, TOMO_PREP_MEDIAN2D = 1 } tomo_prep_outlier_mode;
 
 typedef struct tomo_prep tomo_prep;
 
@@ -112,6 +131,12 @@ TOMO_API int tomo_prep_stripe_dead(tomo_prep *h, void *stream, const float *d_in
 /* dead (la_size, norm) then sorting (sm_size). */
 TOMO_API int tomo_prep_stripe_all(tomo_prep *h, void *stream, const float *d_in, float *d_out, int n_proj, int ndx, int ndz, float snr,
                                   int la_size, int sm_size, size_t max_scratch_bytes, uint8_t *d_mask_dead, uint8_t *d_mask_large);
+/* The frames per batch the in-place tomo_prep_outlier uses for this shape and budget (how tests and benchmarks see the batching). */
+TOMO_API int tomo_prep_outlier_batch(int rows, int cols, int dtype, int n, size_t max_scratch_bytes, int *frames);
+/* Zinger removal (mode TOMO_PREP_OUTLIER) or the 2-D median filter (TOMO_PREP_MEDIAN2D) of d_in[n][rows][cols] into d_out (`outlier`
+ * above).  d_count: NULL or n uint32. */
+TOMO_API int tomo_prep_outlier(tomo_prep *h, void *stream, const void *d_in, void *d_out, int dtype, int n, int rows, int cols, int size,
+                               int mode, float dif, int two_sided, size_t max_scratch_bytes, uint32_t *d_count);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,9 @@ MAX_MEDIAN_FRAMES = 64
 MAX_STRIPE_SIZE = 63
 MIN_STRIPE_NDX, MAX_STRIPE_NDX = 8, 8192      # TOMO_PREP_MIN_STRIPE_NDX, TOMO_PREP_MAX_STRIPE_NDX (large / dead / all)
 MIN_DEAD_NPROJ = 10       # TOMO_PREP_MIN_DEAD_NPROJ
+OUTLIER, MEDIAN2D = 0, 1  # TOMO_PREP_OUTLIER, TOMO_PREP_MEDIAN2D
+MAX_OUTLIER_SIZE = 7      # TOMO_PREP_MAX_OUTLIER_SIZE
+OUTLIER_SIZES = (3, 5, 7)
 
 # every symbol include/tomo_prep.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -44,6 +47,9 @@ SIGNATURES = {
                                        _c_vp, _c_vp]),
     "tomo_prep_stripe_all": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int, ctypes.c_size_t,
                                       _c_vp, _c_vp]),
+    "tomo_prep_outlier_batch": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.c_size_t, ctypes.POINTER(_c_int)]),
+    "tomo_prep_outlier": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
+                                   ctypes.c_size_t, _c_vp]),
 }
 
 
@@ -71,6 +77,15 @@ def stripe_all_chunk(n_proj, ndx, ndz, max_scratch_bytes=0):
     zc = _c_int(0)
     _binding.check(lib, "prep", lib.tomo_prep_stripe_all_chunk(int(n_proj), int(ndx), int(ndz), int(max_scratch_bytes), ctypes.byref(zc)))
     return zc.value
+
+
+def outlier_batch(rows, cols, dtype, n, max_scratch_bytes=0):
+    """The frames per batch the in-place tomo_prep_outlier uses for this shape, dtype (U16 / F32) and scratch budget (0: no limit)."""
+    lib = load()
+    nb = _c_int(0)
+    _binding.check(lib, "prep", lib.tomo_prep_outlier_batch(int(rows), int(cols), int(dtype), int(n), int(max_scratch_bytes),
+                                                            ctypes.byref(nb)))
+    return nb.value
 
 
 class PrepHandle(Handle):
@@ -117,3 +132,9 @@ class PrepHandle(Handle):
         self._check(self.lib.tomo_prep_stripe_all(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(n_proj), int(ndx), int(ndz),
                                                   float(snr), int(la_size), int(sm_size), int(max_scratch_bytes), _ptr(d_mask_dead),
                                                   _ptr(d_mask_large)))
+
+    def outlier(self, stream, d_in, d_out, dtype, n, rows, cols, size, mode, dif=0.0, two_sided=False, max_scratch_bytes=0, d_count=None):
+        """Enqueue the zinger removal (mode OUTLIER) or the 2-D median filter (MEDIAN2D); d_out may be d_in; d_count: None or n uint32."""
+        self._check(self.lib.tomo_prep_outlier(self.handle, _ptr(stream), _ptr(d_in), _ptr(d_out), int(dtype), int(n), int(rows), int(cols),
+                                               int(size), int(mode), float(dif), 1 if two_sided else 0, int(max_scratch_bytes),
+                                               _ptr(d_count)))

@@ -21,10 +21,20 @@
 //   k_stripe_detect    (K6) per z: the factors sorted in LDS, a float64 line fit through the middle half, two thresholds, dilation.
 //   k_large_correct    (K7) K3 with a choice per column: the smoothed value at the angle's rank (masked), or in / factor, or a copy.
 //   k_dead_interp      (K8) masked columns interpolated along x between the nearest unmasked ones.
+// zinger removal and the 2-D median filter (tomo_prep_outlier):
+//   k_outlier          float32.  One work-group per 64 (cols) x 32 (rows) tile of a frame, frames strided over blockIdx.y: the tile and its
+//                      reflected halo go to LDS once as orderable keys, rows read coalesced; each lane selects the median of its
+//                      size x size window in registers by forgetful selection over min / max exchanges (size a template parameter,
+//                      every index static: no scratch), decides the replacement and writes its pixel; the replaced pixels are counted
+//                      per wave, then per work-group in LDS, with one integer atomic per work-group and frame.
+//   k_outlier_u16x2    uint16.  The same on 128 x 32 tiles with two horizontally adjacent pixels per lane: the tile stays 16 bits wide,
+//                      is read as 32-bit words, and the exchanges are the packed unsigned v_pk_min_u16 / v_pk_max_u16, one instruction
+//                      for both windows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "../../../include/tomo_prep.h"
 
@@ -47,6 +57,9 @@ constexpr int DET_T = 256;             // the stripe detector: one work-group pe
 constexpr int COL_T = 256;             // the per-(x, z) kernels of the large- and dead-stripe passes
 constexpr int DEAD_TAPS = 10;          // the angle window of the dead-stripe statistic
 constexpr int INTERP_AY = 32;          // angle groups of k_dead_interp
+constexpr int OUT_TW = 64, OUT_TH = 32, OUT_T = 256;      // k_outlier tile: 64 cols x 32 rows, a lane per column, 8 rows per lane
+constexpr int OUT2_TW = 128;           // k_outlier_u16x2 tile: 128 cols x 32 rows, two columns per lane
+constexpr int OUT_MAX_FR = 65535;      // frames k_outlier's grid spans in y; a work-group strides over the rest
 constexpr int MAX_LDS = (SORT_KEYS + MAX_ZC) * 8;         // the largest dynamic LDS any kernel here asks for
 
 // orderable bits: unsigned order = float order; -0 is canonicalised to +0 first, every NaN maps to one key above +inf
@@ -433,12 +446,239 @@ __global__ __launch_bounds__(COL_T) void k_dead_interp(const float *in, const ui
     }
 }
 
+// ---- zinger removal and the 2-D median filter
+// The LDS key of a pixel: uint16 by value, float32 by its orderable bits; both compared as unsigned integers.
+template <typename T> struct OutKey;
+template <> struct OutKey<uint16_t> {
+    static __device__ __forceinline__ uint16_t enc(uint16_t v) { return v; }
+    static __device__ __forceinline__ uint32_t bits(uint16_t v) { return v; }
+    static __device__ __forceinline__ bool finite(uint16_t) { return true; }
+};
+template <> struct OutKey<float> {
+    typedef uint32_t lds_t;
+    static __device__ __forceinline__ uint32_t enc(float v) { return ord_bits(v); }
+    static __device__ __forceinline__ float dec(uint32_t k) { return k == 0xffffffffu ? __uint_as_float(0x7fc00000u) : from_ord(k); }
+    static __device__ __forceinline__ uint32_t bits(float v) { return __float_as_uint(v); }
+    static __device__ __forceinline__ bool finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+};
+
+// Two horizontally adjacent uint16 keys in one register: min / max are the packed unsigned v_pk_min_u16 / v_pk_max_u16.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t vmin(uint32_t a, uint32_t b) { return min(a, b); }
+__device__ __forceinline__ uint32_t vmax(uint32_t a, uint32_t b) { return max(a, b); }
+__device__ __forceinline__ u16x2 vmin(u16x2 a, u16x2 b) { return __builtin_elementwise_min(a, b); }
+__device__ __forceinline__ u16x2 vmax(u16x2 a, u16x2 b) { return __builtin_elementwise_max(a, b); }
+
+template <typename V>
+__device__ __forceinline__ void cx(V &a, V &b) {
+    const V lo = vmin(a, b);
+    b = vmax(a, b);
+    a = lo;
+}
+
+// The minimum of v[0 .. K) to v[0] and the maximum to v[K - 1]; the values in between stay a permutation of the rest.
+template <int K, int M, typename V>
+__device__ __forceinline__ void min_max(V (&v)[M]) {
+    constexpr int L = (K + 1) / 2;       // after the first pass v[0 .. L) holds the minimum and v[K - L .. K) the maximum
+#pragma unroll
+    for (int i = 0; i < K / 2; ++i) cx(v[i], v[K - 1 - i]);
+#pragma unroll
+    for (int s = 1; s < L; s <<= 1) {
+#pragma unroll
+        for (int i = 0; i + s < L; i += 2 * s) cx(v[i], v[i + s]);
+    }
+#pragma unroll
+    for (int s = 1; s < L; s <<= 1) {
+#pragma unroll
+        for (int i = 0; i + s < L; i += 2 * s) cx(v[K - 1 - i - s], v[K - 1 - i]);
+    }
+}
+
+// The S x S window of a lane, read a row of S keys at a time.  One pixel per lane: the keys as they lie in the tile (row stride LW).
+template <int S, int LW, typename L>
+struct RowsOfOne {
+    typedef uint32_t V;
+    const L *win;                         // the window's top left key
+    __device__ __forceinline__ void row(int r, V (&b)[S]) const {
+#pragma unroll
+        for (int c = 0; c < S; ++c) b[c] = win[r * LW + c];
+    }
+};
+
+// Two pixels per lane (uint16): the tile is read as aligned 32-bit words of two keys; the lane's pair lies HP = 2 or 4 (even, >= S / 2)
+// keys into its words, and a pair that starts at an odd key is cut out of two neighbouring words.
+template <int S, int LW32>
+struct RowsOfTwo {
+    typedef u16x2 V;
+    static constexpr int H = S / 2, HP = (H + 1) & ~1, C0 = HP - H, NW = (HP + H + 1) / 2 + 1;
+    const uint32_t *win;                  // the word of the window's top row that holds the lane's pair, less HP / 2 words
+    __device__ __forceinline__ void row(int r, V (&b)[S]) const {
+        uint32_t w[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) w[j] = win[r * LW32 + j];
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            const int k = C0 + c;
+            b[c] = __builtin_bit_cast(u16x2, (k & 1) ? (w[k / 2] >> 16) | (w[k / 2 + 1] << 16) : w[k / 2]);
+        }
+    }
+};
+
+// Forgetful selection: of K candidates the smallest and the largest cannot be the median of all S * S values while K > S * S / 2 + 1, so
+// both are dropped and the next value of the window is admitted, until three are left.
+template <int K, int S, int M, typename Src>
+__device__ __forceinline__ void forget(typename Src::V (&v)[M], typename Src::V (&b)[S], const Src &src) {
+    if constexpr (K > 3) {
+        min_max<K>(v);
+        constexpr int e = 2 * M - K;
+        if constexpr (e % S == 0) src.row(e / S, b);
+        v[0] = b[e % S];
+        forget<K - 1, S, M>(v, b, src);
+    }
+}
+
+// The key of rank (S * S - 1) / 2 of the S x S window (of each of the lane's windows, for a packed V).
+template <int S, typename Src>
+__device__ __forceinline__ typename Src::V window_median(const Src &src) {
+    typedef typename Src::V V;
+    constexpr int M = S * S / 2 + 2;
+    V v[M], b[S];
+#pragma unroll
+    for (int e = 0; e < M; ++e) {
+        if (e % S == 0) src.row(e / S, b);
+        v[e] = b[e % S];
+    }
+    forget<M, S, M>(v, b, src);
+    return vmax(vmin(v[0], v[1]), vmin(vmax(v[0], v[1]), v[2]));
+}
+
+// Whether the pixel v is replaced by the median med, and with what.
+template <typename T>
+__device__ __forceinline__ bool outlier_hit(T v, T med, int mode, float dif, int two_sided) {
+    typedef OutKey<T> KT;
+    if (mode == TOMO_PREP_MEDIAN2D) return KT::bits(v) != KT::bits(med);
+    float d = to_f(v) - to_f(med);
+    if (two_sided) d = fabsf(d);
+    return d >= dif || !KT::finite(v);
+}
+
+// The rows y0 - H ... of the frame and the columns x0 - HP ... go to tile[LH][LW] as keys, reflected at the frame's edges: a wave per row.
+template <typename T, typename L, int LH, int LW>
+__device__ __forceinline__ void stage_tile(const T *__restrict__ fin, L *tile, int rows, int cols, int ytop, int xleft) {
+    for (int r = threadIdx.x / 64; r < LH; r += OUT_T / 64) {
+        const T *row = fin + (size_t)reflect(ytop + r, rows) * cols;
+        for (int c = threadIdx.x % 64; c < LW; c += 64) tile[r * LW + c] = OutKey<T>::enc(row[reflect(xleft + c, cols)]);
+    }
+}
+
+// The work-group's count of replaced pixels goes to count[f] with one atomic; `hits` was cleared before the barrier that preceded the
+// waves' work.  Ends with a barrier: the tile and the counter are then free for the next frame.
+__device__ __forceinline__ void count_hits(uint32_t mine, uint32_t *hits, uint32_t *__restrict__ count, int f) {
+    if (count) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(hits, mine);
+    }
+    __syncthreads();
+    if (count && threadIdx.x == 0 && *hits) atomicAdd(count + f, *hits);
+    __syncthreads();
+}
+
+// grid: (tiles of a frame, x fastest; min(n, OUT_MAX_FR)).  `in` and `out` never overlap: the in-place call goes through the scratch.
+template <typename T, int S>
+__global__ __launch_bounds__(OUT_T) void k_outlier(const T *__restrict__ in, T *__restrict__ out, uint32_t *__restrict__ count, int n, int rows,
+                                                   int cols, int tiles_x, int mode, float dif, int two_sided) {
+    typedef OutKey<T> KT;
+    typedef typename KT::lds_t L;
+    constexpr int H = S / 2, LW = OUT_TW + S - 1, LH = OUT_TH + S - 1;
+    __shared__ L tile[LH * LW];
+    __shared__ uint32_t hits;
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * OUT_TW, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * OUT_TH;
+    const int tx = threadIdx.x % OUT_TW, ty = threadIdx.x / OUT_TW;
+    const int x = x0 + tx;
+    const size_t npix = (size_t)rows * cols;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const T *fin = in + (size_t)f * npix;
+        T *fout = out + (size_t)f * npix;
+        if (threadIdx.x == 0) hits = 0u;
+        stage_tile<T, L, LH, LW>(fin, tile, rows, cols, y0 - H, x0 - H);
+        __syncthreads();
+        uint32_t mine = 0u;
+#pragma unroll 1
+        for (int yy = ty; yy < OUT_TH; yy += OUT_T / OUT_TW) {       // a wave shares yy
+            const int y = y0 + yy;
+            if (y >= rows) break;
+            const RowsOfOne<S, LW, L> src = {tile + yy * LW + tx};
+            const T med = KT::dec(window_median<S>(src));
+            if (x < cols) {
+                const size_t o = (size_t)y * cols + x;
+                const T v = fin[o];            // the pixel's own bits: the keys fold -0 and the NaN payloads
+                const bool hit = outlier_hit(v, med, mode, dif, two_sided);
+                fout[o] = hit ? med : v;
+                mine += hit ? 1u : 0u;
+            }
+        }
+        count_hits(mine, &hits, count, f);
+    }
+}
+
+// The same for uint16 with two adjacent pixels per lane: tiles of 128 columns, the selection on packed pairs.  grid as k_outlier.
+template <int S>
+__global__ __launch_bounds__(OUT_T) void k_outlier_u16x2(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, uint32_t *__restrict__ count,
+                                                         int n, int rows, int cols, int tiles_x, int mode, float dif, int two_sided) {
+    constexpr int H = S / 2, HP = (H + 1) & ~1, LW = OUT2_TW + 2 * HP, LH = OUT_TH + S - 1;
+    __shared__ uint32_t tile32[LH * LW / 2];
+    __shared__ uint32_t hits;
+    uint16_t *tile = reinterpret_cast<uint16_t *>(tile32);
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * OUT2_TW, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * OUT_TH;
+    const int tx = threadIdx.x % 64, ty = threadIdx.x / 64;
+    const int x = x0 + 2 * tx;
+    const size_t npix = (size_t)rows * cols;
+    const bool words = (cols & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;       // every pair of the output is an aligned word
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint16_t *fin = in + (size_t)f * npix;
+        uint16_t *fout = out + (size_t)f * npix;
+        if (threadIdx.x == 0) hits = 0u;
+        stage_tile<uint16_t, uint16_t, LH, LW>(fin, tile, rows, cols, y0 - H, x0 - HP);
+        __syncthreads();
+        uint32_t mine = 0u;
+#pragma unroll 1
+        for (int yy = ty; yy < OUT_TH; yy += OUT_T / 64) {
+            const int y = y0 + yy;
+            if (y >= rows) break;
+            const RowsOfTwo<S, LW / 2> src = {tile32 + yy * (LW / 2) + tx};
+            const u16x2 med = window_median<S>(src);
+            const u16x2 v = __builtin_bit_cast(u16x2, tile32[(yy + H) * (LW / 2) + HP / 2 + tx]);
+            const bool hit0 = outlier_hit<uint16_t>(v.x, med.x, mode, dif, two_sided);
+            const bool hit1 = outlier_hit<uint16_t>(v.y, med.y, mode, dif, two_sided);
+            u16x2 res;
+            res.x = hit0 ? med.x : v.x;
+            res.y = hit1 ? med.y : v.y;
+            const size_t o = (size_t)y * cols + x;
+            if (x + 1 < cols) {
+                if (words) {
+                    *reinterpret_cast<uint32_t *>(fout + o) = __builtin_bit_cast(uint32_t, res);
+                } else {
+                    fout[o] = res.x;
+                    fout[o + 1] = res.y;
+                }
+                mine += (hit0 ? 1u : 0u) + (hit1 ? 1u : 0u);
+            } else if (x < cols) {             // the last column of an odd width
+                fout[o] = res.x;
+                mine += hit0 ? 1u : 0u;
+            }
+        }
+        count_hits(mine, &hits, count, f);
+    }
+}
+
 }  // namespace
 
 struct tomo_prep {
     int device = 0;
     std::string err;
-    Buf scratch;                               // stripe scratch: S, M (float32) and P (uint16) of one chunk
+    Buf scratch;                               // stripe scratch (S, M and P of one chunk), or one batch of frames of the in-place outlier call
     hipStream_t last_stream = nullptr;         // the stream the scratch was last used on
     hipEvent_t ev_done = nullptr;              // after the last use of the scratch
     hipEvent_t ev_pass[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -657,6 +897,52 @@ int drop_ranks(float drop_ratio, int n_proj) {
 
 constexpr float DEAD_DROP_RATIO = 0.1f;      // the large-stripe pass that closes the dead-stripe pass keeps Vo's default
 
+// ---- zinger removal and the 2-D median filter
+size_t dtype_bytes(int dtype) { return dtype == TOMO_PREP_U16 ? sizeof(uint16_t) : sizeof(float); }
+
+// frames per batch of the in-place call: what fits the budget, at least one
+int outlier_batch_for(int rows, int cols, int dtype, int n, size_t budget) {
+    if (budget == 0) return n;
+    const size_t b = budget / ((size_t)rows * (size_t)cols * dtype_bytes(dtype));
+    return b >= (size_t)n ? n : (b < 1 ? 1 : (int)b);
+}
+
+template <typename T, int S>
+int launch_outlier_s(tomo_prep *h, hipStream_t st, const T *in, T *out, uint32_t *count, int n, int rows, int cols, int mode, float dif,
+                     int two_sided) {
+    constexpr bool packed = std::is_same<T, uint16_t>::value;      // uint16: two pixels per lane (1.4 - 2.1 x the rate of one, measured)
+    constexpr int tw = packed ? OUT2_TW : OUT_TW;
+    const int tiles_x = (cols + tw - 1) / tw, tiles_y = (rows + OUT_TH - 1) / OUT_TH;
+    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)std::min(n, OUT_MAX_FR));
+    if constexpr (packed)
+        hipLaunchKernelGGL((k_outlier_u16x2<S>), grid, dim3(OUT_T), 0, st, in, out, count, n, rows, cols, tiles_x, mode, dif, two_sided);
+    else
+        hipLaunchKernelGGL((k_outlier<T, S>), grid, dim3(OUT_T), 0, st, in, out, count, n, rows, cols, tiles_x, mode, dif, two_sided);
+    HIPCHK(h, hipGetLastError());
+    return TOMO_PREP_OK;
+}
+
+template <typename T>
+int launch_outlier(tomo_prep *h, hipStream_t st, const void *in, void *out, uint32_t *count, int n, int rows, int cols, int size, int mode,
+                   float dif, int two_sided) {
+    const T *i = static_cast<const T *>(in);
+    T *o = static_cast<T *>(out);
+    if (size == 3) return launch_outlier_s<T, 3>(h, st, i, o, count, n, rows, cols, mode, dif, two_sided);
+    if (size == 5) return launch_outlier_s<T, 5>(h, st, i, o, count, n, rows, cols, mode, dif, two_sided);
+    return launch_outlier_s<T, 7>(h, st, i, o, count, n, rows, cols, mode, dif, two_sided);
+}
+
+// what tomo_prep_outlier and tomo_prep_outlier_batch both check
+int check_outlier_shape(tomo_prep *h, const char *who, int dtype, int n, int rows, int cols, int size) {
+    const std::string w(who);
+    if (dtype != TOMO_PREP_U16 && dtype != TOMO_PREP_F32) return fail(h, TOMO_PREP_ERR_ARG, w + ": dtype must be uint16 or float32");
+    if (size != 3 && size != 5 && size != 7) return fail(h, TOMO_PREP_ERR_ARG, w + ": size must be 3, 5 or 7");
+    if (n < 1 || rows < size || cols < size)
+        return fail(h, TOMO_PREP_ERR_ARG, w + ": bad shape (n >= 1, rows >= size, cols >= size)");
+    if ((long long)rows * cols >= (1LL << 31)) return fail(h, TOMO_PREP_ERR_ARG, w + ": frame too large (rows * cols < 2^31)");
+    return TOMO_PREP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -858,6 +1144,48 @@ TOMO_API int tomo_prep_stripe_all(tomo_prep *h, void *stream, const float *d_in,
         CHK(dead_chunk(h, st, d_in, d_out, n_proj, ndx, ndz, zb, zw, snr, la_size, d_mask_dead, c));
         CHK(large_chunk(h, st, d_out, d_out, n_proj, ndx, ndz, zb, zw, snr, la_size, nd, 1, d_mask_large, c));
         CHK(sorting_chunk(h, st, d_out, n_proj, ndx, ndz, zb, zw, sm_size, c));
+    }
+    return scratch_used(h, st);
+}
+
+TOMO_API int tomo_prep_outlier_batch(int rows, int cols, int dtype, int n, size_t max_scratch_bytes, int *frames) {
+    if (!frames) return fail(nullptr, TOMO_PREP_ERR_ARG, "tomo_prep_outlier_batch: NULL pointer");
+    CHK(check_outlier_shape(nullptr, "tomo_prep_outlier_batch", dtype, n, rows, cols, 3));
+    *frames = outlier_batch_for(rows, cols, dtype, n, max_scratch_bytes);
+    return TOMO_PREP_OK;
+}
+
+TOMO_API int tomo_prep_outlier(tomo_prep *h, void *stream, const void *d_in, void *d_out, int dtype, int n, int rows, int cols, int size,
+                               int mode, float dif, int two_sided, size_t max_scratch_bytes, uint32_t *d_count) {
+    if (!h) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_outlier: NULL handle");
+    CHK(check_outlier_shape(h, "tomo_prep_outlier", dtype, n, rows, cols, size));
+    if (mode != TOMO_PREP_OUTLIER && mode != TOMO_PREP_MEDIAN2D) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_outlier: unknown mode");
+    if (mode == TOMO_PREP_OUTLIER && !(dif >= 0.f)) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_outlier: dif must be >= 0 and not NaN");
+    if (!d_in || !d_out) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_outlier: NULL pointer");
+    const size_t frame_bytes = (size_t)rows * (size_t)cols * dtype_bytes(dtype), total = frame_bytes * (size_t)n;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if (a != b && a < b + total && b < a + total) return fail(h, TOMO_PREP_ERR_ARG, "tomo_prep_outlier: d_out must be d_in itself or not overlap it");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool u16 = dtype == TOMO_PREP_U16;
+    if (a != b) {
+        if (d_count) HIPCHK(h, hipMemsetAsync(d_count, 0, (size_t)n * sizeof(uint32_t), st));
+        return u16 ? launch_outlier<uint16_t>(h, st, d_in, d_out, d_count, n, rows, cols, size, mode, dif, two_sided)
+                   : launch_outlier<float>(h, st, d_in, d_out, d_count, n, rows, cols, size, mode, dif, two_sided);
+    }
+    // in place: batches of frames are filtered into the handle's scratch and copied back, all on the stream
+    const int nb = outlier_batch_for(rows, cols, dtype, n, max_scratch_bytes);
+    const size_t need = frame_bytes * (size_t)nb;
+    if (h->pending && (need > h->scratch.n || st != h->last_stream)) CHK(drain(h));
+    CHK(grow(h, h->scratch, need));
+    if (d_count) HIPCHK(h, hipMemsetAsync(d_count, 0, (size_t)n * sizeof(uint32_t), st));
+    for (int f0 = 0; f0 < n; f0 += nb) {
+        const int nf = std::min(nb, n - f0);
+        char *frames = static_cast<char *>(d_out) + frame_bytes * (size_t)f0;
+        uint32_t *cnt = d_count ? d_count + f0 : nullptr;
+        CHK(u16 ? launch_outlier<uint16_t>(h, st, frames, h->scratch.p, cnt, nf, rows, cols, size, mode, dif, two_sided)
+                : launch_outlier<float>(h, st, frames, h->scratch.p, cnt, nf, rows, cols, size, mode, dif, two_sided));
+        HIPCHK(h, hipMemcpyAsync(frames, h->scratch.p, frame_bytes * (size_t)nf, hipMemcpyDeviceToDevice, st));
     }
     return scratch_used(h, st);
 }

@@ -14,6 +14,9 @@ dead_columns=K (--dead-columns K) and gain_columns=K (--gain-columns K) add the 
 preprocess.remove_all_stripe handles: K columns stuck at a count of their own in every projection, and K columns whose gain in the
 projections is 25 % above the flats'.  They are drawn from a generator of their own, so with both at 0 the frames are those of earlier
 versions for the same seed.
+zingers=K (--zingers K) adds K zingers to every count frame and to every flat frame: distinct pixels that a scattered photon drove
+6 000 ... 30 000 counts above what they recorded (clipped to 65535), what preprocess.remove_outlier is for.  They too come from a
+generator of their own, and `zinger_mask` (bool, shaped like counts) says where those of the counts are.
 With propagate=A (--propagate A) the noiseless transmission exp(-mu p) is first carried over a propagation distance: the forward model
 of preprocess.retrieve_phase with strength A (pixels^2), which puts a bright/dark fringe pair on every edge.
 
@@ -58,13 +61,34 @@ def defect_columns(nx, dead_columns, gain_columns, seed=None):
     return np.sort(slots[:int(dead_columns)]), np.sort(slots[int(dead_columns):])
 
 
+ZINGER_COUNTS = (6000, 30000)      # what a zinger adds to its pixel, uniform
+
+
+def add_zingers(frames, k, rng):
+    """Add k zingers to every frame of the uint16 stack frames [n][z][x], in place: k distinct pixels per frame, each raised by a
+    uniform ZINGER_COUNTS and clipped to 65535.  Returns the bool mask of the pixels hit."""
+    n, nz, nx = frames.shape
+    mask = np.zeros(frames.shape, bool)
+    for i in range(n):
+        pix = rng.choice(nz * nx, size=k, replace=False)
+        extra = rng.integers(ZINGER_COUNTS[0], ZINGER_COUNTS[1], size=k, endpoint=True)
+        flat = frames[i].reshape(-1)
+        flat[pix] = np.minimum(flat[pix].astype(np.int64) + extra, 65535).astype(np.uint16)
+        mask[i].reshape(-1)[pix] = True
+    return mask
+
+
 def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03, propagate=None,
-             dead_columns=0, gain_columns=0):
+             dead_columns=0, gain_columns=0, zingers=0):
     """Detector frames of the projections proj [n_proj][nx][nz]: dict(counts, flats, darks, mu) (module docstring).  mu defaults to
     4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor.  propagate: the strength of the propagation
     applied to the noiseless transmission (None or 0: none, and the frames are those of earlier versions for the same seed).
     dead_columns, gain_columns: how many stuck and how many mis-gained columns to add (module docstring); with any, the dict also holds
-    their indices as dead_cols and gain_cols."""
+    their indices as dead_cols and gain_cols.  zingers: how many zingers every count frame and every flat frame gets (module docstring);
+    with any, the dict also holds zinger_mask, and with 0 every array is that of earlier versions for the same seed."""
+    zingers = int(zingers)
+    if zingers < 0 or zingers > proj.shape[1] * proj.shape[2]:
+        raise ValueError("zingers must be >= 0 and at most the pixels of a frame, got %d" % zingers)
     if propagate is not None and not (np.isfinite(propagate) and propagate >= 0):
         raise ValueError("propagate must be a finite strength >= 0 or None, got %r" % (propagate,))
     rng = np.random.default_rng(seed)
@@ -96,10 +120,15 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
         for j, c in enumerate(dead):                                     # stuck: one count per column, between dark and half the flat
             counts[:, :, c] = np.uint16(round(dark_level + i0 * (0.2 + 0.3 * (j + 1) / (len(dead) + 1))))
         out.update(dead_cols=np.asarray(dead, np.int64), gain_cols=np.asarray(gained, np.int64))
+    if zingers:
+        zrng = np.random.default_rng(None if seed is None else [int(seed), 0x21])
+        out["zinger_mask"] = add_zingers(counts, zingers, zrng)
+        add_zingers(flats, zingers, zrng)
     return out
 
 
-def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0):
+def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0,
+         zingers=0):
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
     shepp = generate_phantom.shepp3d(nx)
@@ -118,11 +147,11 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, pr
     d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
     if raw:
         d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate, dead_columns=dead_columns,
-                          gain_columns=gain_columns))                  # a generator of its own: the other keys do not change
+                          gain_columns=gain_columns, zingers=zingers))  # a generator of its own: the other keys do not change
     return d
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--angles", type=int, default=90)
@@ -134,12 +163,23 @@ def main():
     ap.add_argument("--dead-columns", type=int, default=0, metavar="K", help="with --raw: K detector columns stuck at a count")
     ap.add_argument("--gain-columns", type=int, default=0, metavar="K",
                     help="with --raw: K columns whose gain in the projections is 25 %% above the flats'")
-    a = ap.parse_args()
+    ap.add_argument("--zingers", type=int, default=0, metavar="K", help="with --raw: K zingers in every count frame and every flat frame")
+    a = ap.parse_args(argv)
+    if a.zingers < 0:
+        ap.error("--zingers must be >= 0")
+    if a.zingers and not a.raw:
+        ap.error("--zingers needs --raw")
     if a.propagate is not None and not a.raw:
         ap.error("--propagate needs --raw")
     if (a.dead_columns or a.gain_columns) and not a.raw:
         ap.error("--dead-columns and --gain-columns need --raw")
-    d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns)
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns,
+             zingers=a.zingers)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

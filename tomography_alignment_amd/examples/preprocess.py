@@ -14,6 +14,10 @@ Paganin's single-distance phase retrieval between the flat-field division and th
 with --stripe-size as its window -- for detectors with stuck or mis-gained columns (generate_data --dead-columns / --gain-columns);
 `--stripe none` skips the removal.  The default, `--stripe sorting`, is the sorting pass alone.
 
+`--zinger-dif D` (with `--zinger-size S`, default 3) first removes zingers (preprocess.remove_outlier, one-sided): from the uploaded
+counts, in place on the device, and from the flats before normalize reduces them (generate_data --zingers).  Without it the calls and
+the result are exactly what they were.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -30,7 +34,7 @@ import numpy as np
 
 from .. import _lib, preprocess
 
-RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols")
+RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols", "zinger_mask")
 STRIPE_MODES = ("sorting", "all", "none")
 LA_SIZE = 61              # the window of the dead- and large-stripe passes of --stripe all, where the detector is wide enough
 PHASE_KEYS = ("strength", "pixel_size", "dist", "energy", "wavelength", "delta_beta", "pad", "min_ratio", "max_scratch_bytes")
@@ -44,12 +48,13 @@ def la_size_for(nx, la_size=None):
 
 
 def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
-        la_size=None):
+        la_size=None, zinger_dif=None, zinger_size=3):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
     energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
     sorting pass alone), 'all' (remove_all_stripe with snr stripe_snr, la_size -- default la_size_for(nx) -- and sm_size = stripe_size)
-    or 'none'."""
+    or 'none'.  zinger_dif: None, or the threshold (counts) of preprocess.remove_outlier, window zinger_size, applied to the counts and to
+    the flats before anything else."""
     if stripe not in STRIPE_MODES:
         raise ValueError("preprocess: stripe must be one of %s, got %r" % (", ".join(STRIPE_MODES), stripe))
     if stripe == "all" and not stripe_size:
@@ -68,10 +73,16 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     d_frames = sino = None
     try:
         d_frames = ctx.to_device(counts, counts.dtype if counts.dtype in (np.uint16, np.float32) else np.float32)     # uploaded once
+        flats = data["flats"]
+        if zinger_dif is not None:
+            p.remove_outlier(d_frames, zinger_dif, size=zinger_size, out=d_frames)                       # in place, on the device
+            flats = np.asarray(flats)
+            flats = p.remove_outlier(flats if flats.dtype in (np.uint16, np.float32) else flats.astype(np.float32), zinger_dif,
+                                     size=zinger_size)
         if phase is None:
-            sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop)
+            sino = p.normalize(d_frames, flats, data["darks"], cutoff=cutoff, method=method, crop=crop)
         else:
-            sino = p.normalize(d_frames, data["flats"], data["darks"], cutoff=cutoff, method=method, crop=crop, minus_log=False)
+            sino = p.normalize(d_frames, flats, data["darks"], cutoff=cutoff, method=method, crop=crop, minus_log=False)
         d_frames.free()
         if phase is not None:
             p.retrieve_phase(sino, out=sino, **phase)                                                     # in place; applies the -log
@@ -117,7 +128,14 @@ def parse_args(argv=None):
     ap.add_argument("--dist", type=float, default=None, help="propagation distance, metres")
     ap.add_argument("--energy", type=float, default=None, help="keV")
     ap.add_argument("--delta-beta", type=float, default=None, help="delta / beta of the material (default 1000)")
+    ap.add_argument("--zinger-dif", type=float, default=None, metavar="D",
+                    help="remove zingers first: pixels of the counts and the flats D counts or more above their neighbourhood's median")
+    ap.add_argument("--zinger-size", type=int, default=3, metavar="S", help="with --zinger-dif: the median window, 3, 5 or 7")
     a = ap.parse_args(argv)
+    if a.zinger_dif is not None and not a.zinger_dif >= 0:
+        ap.error("--zinger-dif must be >= 0")
+    if a.zinger_size not in (3, 5, 7):
+        ap.error("--zinger-size must be 3, 5 or 7")
     physical = {k: getattr(a, k) for k in ("pixel_size", "dist", "energy", "delta_beta") if getattr(a, k) is not None}
     a.phase = None
     if a.phase_strength is not None:
@@ -146,7 +164,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
-            stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size)
+            stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 

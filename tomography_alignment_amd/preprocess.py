@@ -3,7 +3,7 @@ Preprocessing of raw projections on the GPU (libtomo_prep.so, include/tomo_prep.
 transpose into the package's sinogram layout, and stripe removal (sorting-based, large stripes, dead stripes, and the three combined).
 The first step of the pipeline
 
-    raw counts --normalize--> sinogram --remove_stripe_sorting / remove_all_stripe--> align.align_cc / recon.fbp / examples.align_rigid
+    raw counts --remove_outlier--> --normalize--> sinogram --remove_stripe_sorting / remove_all_stripe--> align.align_cc / recon.fbp / examples.align_rigid
 
 Layouts.  Raw frames, flats and darks are [n][rows = z][cols = x] (x fastest), uint16 or float32, uploaded in their own dtype.  The
 sinogram is float32 p[n_proj][nx][nz] with z, the rotation axis, fastest -- what FBP, SIRT and OuterLoop read (OuterLoop takes the
@@ -59,6 +59,22 @@ Both build a float32 factor per column (x, z) and share one detector, which work
 Limits: those of the sorting pass, and 8 <= nx <= 8192 (the detector sorts one row of factors in LDS; more raises PrepUnsupported before
 anything is uploaded).  The scratch is 10 bytes per value plus 13 per column (x, z) of a chunk; the result does not depend on the chunking.
 return_mask=True also returns the detector's dilated mask(s) as boolean (nx, nz) arrays.
+
+Zinger removal and the 2-D median filter (remove_outlier, median_filter): the first step of the chain, applied to the raw counts and to
+the flats before anything else sees them (a zinger is a pixel, or a cluster of two or three, that a scattered photon or a cosmic ray
+drives far above its neighbours in one frame).  frames is a stack [n][rows][cols] or one image [rows][cols], uint16 or float32 -- raw
+frames [n][z][x] and the sinogram (n, nx, nz) alike; the output has the input's dtype.  size is 3, 5 or 7 (rows, cols >= size).  Per pixel v:
+    window   the size x size values around it in its own frame, scipy.ndimage's mode='reflect' at the edges;
+    med      the window's value of rank (size^2 - 1) / 2: uint16 ordered by value, float32 by the stripe sort's key (-0 read as +0, every
+             NaN above +inf), decoded from the key -- a median of -0 is +0, a NaN median is the quiet NaN 0x7fc00000;
+    remove_outlier   d = float32(v) - float32(med) (exact for uint16), |d| if two_sided; v becomes med if d >= dif or if v is not finite,
+             else it keeps its bits.  dif >= 0 (as a float32), +inf only repairs non-finite pixels.  This is tomopy's remove_outlier
+             with the exact median; one-sided is the default because zingers are bright.
+    median_filter    every pixel becomes med.
+return_count=True also gives, per frame, the number of pixels the test replaced (whether or not med differs from v), as int64.  `out`
+may be the input: frames then go through the handle's scratch in batches bounded by max_scratch_bytes (default 2 GiB; 0: no limit; never
+fewer than one frame), and the result does not depend on the batch.  The work is per frame: a rank that holds a block of angles filters
+its own block.
 
 Phase retrieval (retrieve_phase; libtomo_phase.so, include/tomo_phase.h): Paganin's single-distance filter, the step between the
 flat-field division and the -log for data recorded with a propagation distance:
@@ -227,6 +243,44 @@ def _check_stripe_args(proj, snr, out, max_scratch_bytes, min_nproj, what):
             if a0 < b0 + out.nbytes and b0 < a0 + proj.nbytes:
                 raise ValueError("out must be proj itself or not overlap it")
     return shape, float(snr32), budget
+
+
+def _check_outlier_args(frames, size, out, max_scratch_bytes):
+    """((n, rows, cols), dtype, size, budget) of a remove_outlier / median_filter call, or ValueError: nothing is uploaded before this."""
+    shape, dtype = _shape_dtype(frames, "frames", (2, 3))
+    n, rows, cols = (1,) + shape if len(shape) == 2 else shape
+    if isinstance(size, (bool, np.bool_)) or not isinstance(size, (int, np.integer)) or int(size) not in _prep_lib.OUTLIER_SIZES:
+        raise ValueError("size must be 3, 5 or 7, got %r" % (size,))
+    size = int(size)
+    if rows < size or cols < size:
+        raise ValueError("frames of %d x %d are smaller than the window: rows and cols must be >= size = %d" % (rows, cols, size))
+    if rows * cols >= 2 ** 31:
+        raise ValueError("frames must have fewer than 2^31 pixels each, got %d x %d" % (rows, cols))
+    budget = DEFAULT_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+    if budget < 0:
+        raise ValueError("max_scratch_bytes must be >= 0 (0: no limit)")
+    if out is not None:
+        if not (_is_dev(out) and out.dtype == dtype and out.size == n * rows * cols):
+            raise ValueError("out must be a %s DeviceArray of %d values" % (dtype, n * rows * cols))
+        if not _is_dev(frames):
+            raise ValueError("out needs a DeviceArray input (a host input gives a host result)")
+        if out.ptr.value != frames.ptr.value:
+            a0, b0 = frames.ptr.value, out.ptr.value
+            if a0 < b0 + out.nbytes and b0 < a0 + frames.nbytes:
+                raise ValueError("out must be frames itself or not overlap it")
+    return (n, rows, cols), dtype, size, budget
+
+
+def _check_dif(dif):
+    """dif as the float32 the kernel compares with, or ValueError."""
+    try:
+        dif32 = np.float32(dif)
+        ok = not isinstance(dif, (bool, np.bool_)) and bool(dif32 >= 0)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("dif must be a number >= 0 (in float32; inf is allowed, NaN is not), got %r" % (dif,))
+    return float(dif32)
 
 
 class Preprocessor(HandleOwner):
@@ -451,6 +505,48 @@ class Preprocessor(HandleOwner):
 
         return self._run_stripe(proj, shape, out, 2 if return_mask else 0, call)
 
+    def _run_outlier(self, frames, out, info, mode, dif, two_sided, return_count):
+        """Upload / allocate as the conventions say (a host input's upload is filtered in place), enqueue, download a host input's result."""
+        (n, rows, cols), dtype, size, budget = info
+        self._ready(frames)
+        temps = []
+        try:
+            d_in = self._upload(frames, temps)
+            res = out
+            if res is None:
+                res = d_in if not _is_dev(frames) else self.ctx.empty(tuple(frames.shape), dtype)
+            try:
+                d_count = None
+                if return_count:
+                    d_count = self.ctx.empty((n,), np.uint32)
+                    temps.append(d_count)
+                self.handle.outlier(self.ctx.stream(), d_in.ptr, res.ptr, _DTYPES[dtype], n, rows, cols, size, mode, dif, two_sided, budget,
+                                    None if d_count is None else d_count.ptr)
+                counts = d_count.download().astype(np.int64) if return_count else None
+            except Exception:
+                if out is None and res is not d_in:
+                    res.free()
+                raise
+            result = res if _is_dev(frames) else res.download().reshape(np.shape(frames))
+        finally:
+            self._free(temps)
+        return (result, counts) if return_count else result
+
+    def remove_outlier(self, frames, dif, size=3, two_sided=False, out=None, max_scratch_bytes=None, return_count=False):
+        """Zinger removal (module docstring) of frames [n][rows][cols] or [rows][cols], uint16 or float32: a pixel that exceeds the
+        size x size median of its neighbourhood by dif or more (two_sided: or falls below it by as much) becomes that median.  Host in:
+        an ndarray out.  Device in: the result goes to `out` (a DeviceArray of the same dtype and size; `out=frames` works in place) or
+        a new DeviceArray.  return_count=True: (result, int64 array of the pixels replaced per frame)."""
+        info = _check_outlier_args(frames, size, out, max_scratch_bytes)
+        dif = _check_dif(dif)
+        return self._run_outlier(frames, out, info, _prep_lib.OUTLIER, dif, bool(two_sided), return_count)
+
+    def median_filter(self, frames, size=3, out=None, max_scratch_bytes=None):
+        """The size x size median filter (module docstring; scipy.ndimage.median_filter(mode='reflect') per frame on finite data) of
+        frames [n][rows][cols] or [rows][cols], uint16 or float32.  Conventions as remove_outlier."""
+        info = _check_outlier_args(frames, size, out, max_scratch_bytes)
+        return self._run_outlier(frames, out, info, _prep_lib.MEDIAN2D, 0.0, False, False)
+
     def _ready_phase(self, like):
         self._ready_ctx(like)
         if self._phase is None:
@@ -550,6 +646,25 @@ def normalize(frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6,
     p = Preprocessor(ctx)
     try:
         return p.normalize(frames, flats, darks, cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, method=method, crop=crop, out=out)
+    finally:
+        p.close()
+
+
+def remove_outlier(frames, dif, size=3, two_sided=False, ctx=None, out=None, max_scratch_bytes=None, return_count=False):
+    """Zinger removal: Preprocessor.remove_outlier on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.remove_outlier(frames, dif, size=size, two_sided=two_sided, out=out, max_scratch_bytes=max_scratch_bytes,
+                                return_count=return_count)
+    finally:
+        p.close()
+
+
+def median_filter(frames, size=3, ctx=None, out=None, max_scratch_bytes=None):
+    """The 2-D median filter: Preprocessor.median_filter on a handle of its own."""
+    p = Preprocessor(ctx)
+    try:
+        return p.median_filter(frames, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
     finally:
         p.close()
 

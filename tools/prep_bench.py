@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development tool (not the benchmark contract; bench.py is): times preprocess.py on the GPU -- the fused normalisation of uint16 frames
-and the three passes of the stripe removal -- with device events on a warmed handle.
+the three passes of the stripe removal, and the zinger removal -- with device events on a warmed handle.
 
     python tools/prep_bench.py                          # 1024 x 1024^2 and 1800 x 2048^2 (n_proj x rows x cols)
     python tools/prep_bench.py --cases 256x512x512 --reps 3
@@ -12,7 +12,12 @@ timed in the same process (a copy moves 2 x its bytes).  Stripe removal (size 21
 does Np log2(Np) (log2(Np) + 1) / 4 compare-exchanges per column (Np: n_proj rounded up to a power of two), each two 8-byte LDS reads and
 up to two 8-byte LDS writes.  The large-, dead- and all-stripe passes (cases `large`, `dead`, `all`; snr 3, windows 51, 51 and 61 / --size)
 are timed whole, in place, on the same sinogram: each adds its statistics, the detector and a correction to the sort and median passes
-above (dead with norm and all run the large pass too)."""
+above (dead with norm and all run the large pass too).
+
+The outlier leg (--legs outlier; one more JSON line per case) times preprocess.remove_outlier (one-sided, dif 3000) on n x rows x cols
+frames of noisy counts, uint16 and float32, windows 3, 5 and 7, out of place and in place (default scratch budget): milliseconds, the
+GB/s of the minimal traffic (each pixel read once and written once) and that rate as a fraction of a device-to-device copy of the same
+buffer timed in the same process -- the yardstick of normalize_vs_copy."""
 import argparse
 import json
 import math
@@ -95,6 +100,53 @@ def case(n, rows, cols, reps, size, passes_wanted=("large", "dead", "all")):
     ctx.close()
 
 
+def outlier_case(n, rows, cols, reps):
+    from tomography_alignment_amd import _lib, preprocess
+
+    ctx = _lib.Context()
+    pre = preprocess.Preprocessor(ctx)
+    rng = np.random.default_rng(0)
+    block = min(n, 16)                                           # noisy counts, not zeros: 16 random frames, repeated
+    base = np.clip(rng.poisson(2e4, (block, rows, cols)) + 100, 0, 65535).astype(np.uint16)
+    base.reshape(-1)[rng.choice(base.size, size=4 * block, replace=False)] += 9000       # a few zingers
+    frames = np.concatenate([base] * ((n + block - 1) // block))[:n]
+    res = dict(case="%dx%dx%d" % (n, rows, cols), leg="outlier", reps=reps, device=ctx.device_name(), dif=3000.0)
+
+    def timed(fn):
+        fn()                                                     # warm-up
+        ctx.sync()
+        out = []
+        for _ in range(reps):
+            ctx.timer_start()
+            fn()
+            out.append(ctx.timer_stop())
+        return float(np.median(out)), float(np.min(out))
+
+    for dtype, name in ((np.uint16, "u16"), (np.float32, "f32")):
+        d_in = ctx.to_device(frames.astype(dtype), dtype)
+        d_out = ctx.empty(frames.shape, dtype)
+        moved = 2.0 * d_in.nbytes                                # read once, written once: what a copy of the buffer moves too
+        copy_ms, _ = timed(lambda: d_out.copy_from(d_in))
+        res["%s_copy_ms" % name] = round(copy_ms, 3)
+        res["%s_copy_GBps" % name] = round(moved / (copy_ms * 1e-3) / 1e9, 1)
+        code = preprocess._prep_lib.U16 if dtype == np.uint16 else preprocess._prep_lib.F32
+        res["%s_in_place_batch" % name] = preprocess._prep_lib.outlier_batch(rows, cols, code, n, preprocess.DEFAULT_SCRATCH_BYTES)
+        for size in (3, 5, 7):
+            for where, out in (("out", d_out), ("in_place", d_in)):
+                ms, ms_min = timed(lambda: pre.remove_outlier(d_in, 3000.0, size=size, out=out))
+                key = "%s_size%d_%s" % (name, size, where)
+                res[key + "_ms"] = round(ms, 3)
+                res[key + "_min_ms"] = round(ms_min, 3)
+                res[key + "_GBps"] = round(moved / (ms * 1e-3) / 1e9, 1)
+                res[key + "_vs_copy"] = round(copy_ms / ms, 3)
+            d_in.upload(frames.astype(dtype))                    # the in-place runs removed the zingers: put them back
+        d_in.free()
+        d_out.free()
+    _emit(**res)
+    pre.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", nargs="*", default=["1024x1024x1024", "1800x2048x2048"], help="n_proj x rows x cols")
@@ -102,10 +154,15 @@ def main():
     ap.add_argument("--size", type=int, default=21)
     ap.add_argument("--passes", nargs="*", default=["large", "dead", "all"], choices=["large", "dead", "all"],
                     help="the large- / dead- / all-stripe passes to time after the sorting pass (none: --passes with no value)")
+    ap.add_argument("--legs", nargs="+", default=["prep", "outlier"], choices=["prep", "outlier"],
+                    help="prep: normalisation and stripe removal; outlier: remove_outlier, both dtypes, windows 3, 5 and 7")
     a = ap.parse_args()
     for c in a.cases:
         n, rows, cols = (int(v) for v in c.split("x"))
-        case(n, rows, cols, a.reps, a.size, tuple(a.passes))
+        if "prep" in a.legs:
+            case(n, rows, cols, a.reps, a.size, tuple(a.passes))
+        if "outlier" in a.legs:
+            outlier_case(n, rows, cols, a.reps)
 
 
 if __name__ == "__main__":
