@@ -17,6 +17,11 @@ Without ground truth (fsc=True, --fsc): after every alignment pass the even and 
 at the current poses and their Fourier shell correlation (resolution.half_set_fsc) gives the half-bit resolution, in full-size pixels --
 the monitor that measured data, which have no phantom, allow.
 
+Rotation axis (cor=, --cor): measured data never have the axis on the detector's centre column, and the alignment searches a few pixels
+only.  cor is the x component of `Geometry(cor_shift=)` in full-size pixels -- a number, or "auto": rotation_axis.find_center on
+AUTO_COR_ROWS detector rows of the measured projections, the median offset turned into a cor_shift by rotation_axis.to_cor_shift.  The
+reconstruction, the alignment pass and the FSC's FBPs all use it; None (the default) leaves every call as it was.
+
 Coarse to fine (run_multires, --levels): the first outer iterations run on data binned by 2^(levels-1), ..., 2 (multires.py: the
 binning and prolongation kernels of libtomo_pyr.so), each level a unit-pitch geometry of its own; the poses (translations times 2, tilts
 as they are) and the prolonged reconstruction are handed up, and only the last iterations run at full size.  The bounds of the optimiser
@@ -25,6 +30,7 @@ are in pixels of the level, so the same +-3 px reach +-12 full-size pixels at a 
     python -m tomography_alignment_amd.examples.align_rigid data.npz --outer 5 --sirt-iters 50
     python -m tomography_alignment_amd.examples.align_rigid data.npz --levels 3 --outer 3 --sirt-iters 50
     python -m tomography_alignment_amd.examples.align_rigid measured.npz --fsc          # no phantom needed: a resolution per outer iteration
+    python -m tomography_alignment_amd.examples.align_rigid measured.npz --cor auto     # find the rotation axis first (rotation_axis.py)
     python -m torch.distributed.run --nproc-per-node 8 -m tomography_alignment_amd.examples.align_rigid data.npz
 """
 import argparse
@@ -32,7 +38,7 @@ import time
 
 import numpy as np
 
-from .. import alignment, multires, resolution
+from .. import alignment, multires, resolution, rotation_axis
 from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
 
@@ -52,9 +58,11 @@ class OuterLoop(object):
              INCREMENT around (from a zero start, inside the bounds); the estimate is base + increment (run_multires: the coarser level's).
     d_rec    None, or a device buffer that is the warm start of the first SIRT (it is updated in place).
     factor   the binning factor of the level `data` belongs to: `xyz` of the true poses is in full-size pixels, and pose_errors reports
-             in full-size pixels."""
+             in full-size pixels.
+    cor      None, or the x component of the geometry's cor_shift in pixels of THIS level (resolve_cor; a level of factor f gets the
+             full-size value / f): the SIRT, the FBPs and the alignment pass all project with it."""
 
-    def __init__(self, data, backend=None, comm=None, kernel_names=None, base=None, d_rec=None, factor=1):
+    def __init__(self, data, backend=None, comm=None, kernel_names=None, base=None, d_rec=None, factor=1, cor=None):
         self.comm = comm
         self.size = 1 if comm is None else (comm.Get_size() if hasattr(comm, "Get_size") else comm.size)
         self.rank = 0 if comm is None else (comm.Get_rank() if hasattr(comm, "Get_rank") else comm.rank)
@@ -71,7 +79,12 @@ class OuterLoop(object):
         ground_truth = data["phantom"] if "phantom" in data else None
         ny = int(data["ny"]) if "ny" in data else (ground_truth.shape[1] if getattr(ground_truth, "ndim", 0) == 3 else nx)
         self.vox_shape = (nx, ny, nz)
-        self.geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2))
+        self.cor = None if cor is None else float(cor)
+        if self.cor is None:
+            self.geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2))
+        else:
+            self.geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2),
+                                          cor_shift=np.array([self.cor, 0.0, 0.0]))
         self.mine = np.array_split(np.arange(n_proj), self.size)[self.rank]           # recon/sirt_mpi.py:40
         if backend is None:
             from ..backend import HipBackend
@@ -135,6 +148,8 @@ class OuterLoop(object):
         kw = dict(letters="xzab", bounds=bounds)
         if self.base is not None:
             kw.update(xyz0=self.base[0], angles0=np.column_stack([self.phi, self.base[1], self.base[2]]))
+        if self.cor is not None:
+            kw.update(cor_shift=np.asarray(self.geom.cor_shift, np.float64))
         kw.update(align_kwargs)
         if self.comm is None:
             res = alignment.align_projections(self.be, self.d_rec, self.d_b, self.phi, indices=self.mine, **kw)
@@ -168,21 +183,58 @@ class OuterLoop(object):
         return self.be.download(self.d_rec).reshape(self.vox_shape)
 
 
+AUTO_COR_ROWS = 9      # cor="auto" searches this many detector rows, spread evenly over the central half of z, and takes the median
+
+
+def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
+    """The x component of cor_shift, full-size pixels, that `cor` stands for: None -> None, a number -> itself, "auto" ->
+    rotation_axis.find_center on the measured projections (`phi` must cover pi uniformly, with or without the endpoint; the search
+    range is the default +-50 half-pixel steps, cut to what the detector holds), its median offset as a cor_shift.
+    With a communicator only a number is taken: a rank holds a block of the angles, the search needs all of them for a detector row,
+    and every rank needs the same value; "auto" raises ValueError there -- find the offset beforehand and pass the number."""
+    if cor is None:
+        return None
+    if not isinstance(cor, str):
+        cor = float(cor)
+        if not np.isfinite(cor):
+            raise ValueError("align_rigid: cor must be finite, got %r" % (cor,))
+        return cor
+    if cor != "auto":
+        raise ValueError("align_rigid: cor must be None, a number or 'auto', not %r" % (cor,))
+    if comm is not None:
+        raise ValueError("align_rigid: cor='auto' needs all angles of a detector row on one GPU; with a communicator pass the number "
+                         "(rotation_axis.find_center beforehand)")
+    proj = data["projections"]
+    shape = tuple(int(v) for v in (data["projections_shape"] if "projections_shape" in data else np.shape(proj)))
+    n, nx, nz = shape
+    smin, smax = rotation_axis.widest_range(nx)
+    rows = rotation_axis.spread_rows(nz, AUTO_COR_ROWS)
+    found = rotation_axis.find_center(proj, angles=np.asarray(data["phi"], np.float64), rows=rows, smin=smin, smax=smax, ctx=ctx, shape=shape)
+    value = float(rotation_axis.to_cor_shift(found.offset, 1)[0, 0])
+    if verbose:
+        print({"cor": value, "offsets": found.offsets.tolist(), "rows": rows.tolist()})
+    return value
+
+
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
-        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False):
+        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
     fsc            True: every history entry gains `fsc_resolution` (pixels) and `fsc_curve` (_fsc_entry); needs no phantom.
+    cor            None, a number or "auto" (resolve_cor; "auto" only without a communicator): the geometry's cor_shift x.  With a
+                   value every history entry carries it as `cor`; with None nothing changes.
     kernel_names   with a HIP context: the history carries the HIP-event kernel time of each half of each outer iteration for these names.
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
-    loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names)
+    cor = resolve_cor(data, cor, comm, getattr(backend, "ctx", None), verbose)
+    loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names, cor=cor)
     history = []
     res = resolution.Resolution(loop.ctx) if fsc else None
     try:
         for it in range(n_outer):
-            history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, fsc_with=res))
+            history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, fsc_with=res,
+                                            extra=None if cor is None else {"cor": cor}))
     finally:
         if res is not None:
             res.close()
@@ -241,20 +293,23 @@ def _per_level(value, levels, name):
 
 
 def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, align_kwargs=None, comm=None,
-                 kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None, fsc=False):
+                 kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None, fsc=False,
+                 cor=None):
     """`run` coarse to fine (module docstring): levels binned by 2^(levels-1), ..., 2, 1, coarsest first.
     n_outer, sirt_iters   one number, or one per level, coarsest first.
     bounds                of the increment every pass searches around the pose carried up from the coarser level (zero at the coarsest),
                           in pixels of the level.
     init                  the start of the coarsest level's first SIRT; every finer level starts from the prolonged coarser reconstruction.
     fsc                   as in `run`; `fsc_resolution` is in full-size pixels at every level.
+    cor                   as in `run`, in full-size pixels (found on the full-size data); a level binned by f projects with cor / f.
     ctx                   the _lib.Context all levels share (default: the communicator's, or a new one).
     backend_factory, pyramid   test seams: geometry -> backend (default a HipBackend on ctx per level), and the object with multires.Pyramid's
                           three methods (default a Pyramid on ctx).
     Per level: the data are bin_projections of this rank's FULL-SIZE rows and bin_volume of the full-size ground truth (never of the previous
     level's); the level's OuterLoop runs on the unit-pitch geometry of the binned sizes (multires.level_geometry); its base pose is the
-    coarser level's estimate with the translations times 2 and the tilts as they are.  The loop carries no centre-of-rotation offset, so
-    there is none to rescale.  A finished level's buffers are freed before the next level allocates its own.
+    coarser level's estimate with the translations times 2 and the tilts as they are.  The centre-of-rotation offset `cor`, where one is
+    given, is a length like the translations: the level's geometry gets cor / f.  A finished level's buffers are freed before the next
+    level allocates its own.
     Returns what `run` returns; every history entry also carries `level` (0: the coarsest) and `factor`, and its shift error is in
     full-size pixels.  levels=1 IS `run`."""
     levels = int(levels)
@@ -263,7 +318,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
     n_outer, sirt_iters = _per_level(n_outer, levels, "n_outer"), _per_level(sirt_iters, levels, "sirt_iters")
     if levels == 1:
         out = run(data, n_outer[0], sirt_iters[0], bounds=bounds, verbose=verbose, align_kwargs=align_kwargs, comm=comm,
-                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init, fsc=fsc)
+                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init, fsc=fsc, cor=cor)
         for entry in out[4]:
             entry.update(level=0, factor=1)
         return out
@@ -291,6 +346,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
         if ctx is None:
             ctx = _lib.Context()
         backend_factory = lambda g: HipBackend(g, ctx=ctx)      # noqa: E731
+    cor = resolve_cor(data, cor, comm, ctx, verbose)
     own_pyramid = pyramid is None
     if own_pyramid:
         pyramid = multires.Pyramid(ctx)
@@ -317,12 +373,14 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
             ldata = dict(poses, projections=d_b_l, projections_shape=(n_proj,) + shape[::2], phi=phi, ny=shape[1])
             if d_gt_l is not None:
                 ldata["phantom"] = d_gt_l
-            loop = OuterLoop(ldata, backend=be_l, comm=comm, kernel_names=kernel_names, base=carried, d_rec=d_rec, factor=f)
+            loop = OuterLoop(ldata, backend=be_l, comm=comm, kernel_names=kernel_names, base=carried, d_rec=d_rec, factor=f,
+                             cor=None if cor is None else cor / f)
             if fsc and res is None:
                 res = resolution.Resolution(loop.ctx)
             for _ in range(n_outer[level]):
                 history.append(_outer_iteration(loop, len(history), sirt_iters[level], bounds, init if level == 0 else "zero", align_kwargs,
-                                                kernel_names, verbose, extra={"level": level, "factor": f}, fsc_with=res))
+                                                kernel_names, verbose, fsc_with=res,
+                                                extra={"level": level, "factor": f} if cor is None else {"level": level, "factor": f, "cor": cor}))
             if f == 1:
                 break
             # hand up, and free what this level held before the finer one allocates: the solver's buffers, the binned data, then -- once it is
@@ -367,16 +425,19 @@ def main():
                     "then count per level.  1: the plain loop")
     ap.add_argument("--fsc", action="store_true", help="report the half-bit resolution of the half-set Fourier shell correlation per outer "
                     "iteration (needs no phantom)")
+    ap.add_argument("--cor", default=None, metavar="D|auto", help="the rotation axis as Geometry's cor_shift x in pixels, or 'auto' to find it "
+                    "from the sinograms first (rotation_axis.find_center; one GPU)")
     a = ap.parse_args()
+    cor = a.cor if a.cor in (None, "auto") else float(a.cor)
     import os
     comm = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:       # launched one process per GPU: python -m torch.distributed.run --nproc-per-node N -m ...
         from ..comm import RcclComm
         comm = RcclComm.from_env()
     if a.levels == 1:
-        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc)
+        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor)
     else:
-        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc)
+        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor)
     if comm is not None:
         comm.close()
 

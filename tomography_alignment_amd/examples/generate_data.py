@@ -19,6 +19,9 @@ zingers=K (--zingers K) adds K zingers to every count frame and to every flat fr
 generator of their own, and `zinger_mask` (bool, shaped like counts) says where those of the counts are.
 With propagate=A (--propagate A) the noiseless transmission exp(-mu p) is first carried over a propagation distance: the forward model
 of preprocess.retrieve_phase with strength A (pixels^2), which puts a bright/dark fringe pair on every edge.
+With cor_offset=D (--cor-offset D) the data are projected with Geometry(cor_shift=[D, 0, 0]): the rotation axis is off the detector's
+centre column, as in every measured scan, and the file holds D as `cor_offset` -- what rotation_axis.find_center and align_rigid's
+cor= are for.  With D = 0 every other key is that of earlier versions for the same seed.
 
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --out data.npz
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --out raw.npz
@@ -128,11 +131,15 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
 
 
 def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0,
-         zingers=0):
+         zingers=0, cor_offset=0.0):
+    cor_offset = float(cor_offset)
+    if not np.isfinite(cor_offset):
+        raise ValueError("cor_offset must be finite, got %r" % (cor_offset,))
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
     shepp = generate_phantom.shepp3d(nx)
-    geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2))
+    geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2),
+                             cor_shift=np.array([cor_offset, 0.0, 0.0]) if cor_offset else None)
     phi = np.linspace(0.0, np.pi, n_proj)
     a100, s100 = int(round(100 * ang_deg)), int(round(100 * shift_px))
     jitter = lambda m: rng.randint(-m, m, n_proj) / 100 if m > 0 else np.zeros(n_proj)      # noqa: E731 (m = 0: nominal poses)
@@ -144,7 +151,7 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, pr
     proj_obj = projection_operators.ProjectionMatrix(geom, precision=np.float32)
     pmat = proj_obj.projection_matrix(alpha=alpha, beta=beta, phi=phi, xyz_shift=xyz)
     proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
-    d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp)
+    d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp, cor_offset=np.float64(cor_offset))
     if raw:
         d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate, dead_columns=dead_columns,
                           gain_columns=gain_columns, zingers=zingers))  # a generator of its own: the other keys do not change
@@ -163,6 +170,8 @@ def parse_args(argv=None):
     ap.add_argument("--dead-columns", type=int, default=0, metavar="K", help="with --raw: K detector columns stuck at a count")
     ap.add_argument("--gain-columns", type=int, default=0, metavar="K",
                     help="with --raw: K columns whose gain in the projections is 25 %% above the flats'")
+    ap.add_argument("--cor-offset", type=float, default=0.0, metavar="D", help="project with the rotation axis off centre: "
+                    "Geometry(cor_shift=[D, 0, 0])")
     ap.add_argument("--zingers", type=int, default=0, metavar="K", help="with --raw: K zingers in every count frame and every flat frame")
     a = ap.parse_args(argv)
     if a.zingers < 0:
@@ -179,7 +188,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     d = make(a.size, a.angles, a.seed, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns,
-             zingers=a.zingers)
+             zingers=a.zingers, cor_offset=a.cor_offset)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

@@ -18,6 +18,10 @@ with --stripe-size as its window -- for detectors with stuck or mis-gained colum
 counts, in place on the device, and from the flats before normalize reduces them (generate_data --zingers).  Without it the calls and
 the result are exactly what they were.
 
+`--find-center` (with `--center-rows K`, default 9) finds the rotation axis on the finished sinogram, where it lies on the device
+(rotation_axis.find_center on K detector rows spread over the central half of z, the median offset), and stores it as `cor_offset`: the
+x component of Geometry's cor_shift, the number align_rigid's --cor takes.  The data need `phi`, covering pi uniformly.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -32,7 +36,7 @@ import argparse
 
 import numpy as np
 
-from .. import _lib, preprocess
+from .. import _lib, preprocess, rotation_axis
 
 RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols", "zinger_mask")
 STRIPE_MODES = ("sorting", "all", "none")
@@ -48,13 +52,16 @@ def la_size_for(nx, la_size=None):
 
 
 def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
-        la_size=None, zinger_dif=None, zinger_size=3):
+        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
     energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
     sorting pass alone), 'all' (remove_all_stripe with snr stripe_snr, la_size -- default la_size_for(nx) -- and sm_size = stripe_size)
     or 'none'.  zinger_dif: None, or the threshold (counts) of preprocess.remove_outlier, window zinger_size, applied to the counts and to
-    the flats before anything else."""
+    the flats before anything else.  find_center: True stores the rotation axis found on the finished sinogram as `cor_offset` (module
+    docstring), searched on center_rows detector rows."""
+    if find_center and "phi" not in data:
+        raise ValueError("preprocess: find_center needs the angles `phi`")
     if stripe not in STRIPE_MODES:
         raise ValueError("preprocess: stripe must be one of %s, got %r" % (", ".join(STRIPE_MODES), stripe))
     if stripe == "all" and not stripe_size:
@@ -90,6 +97,14 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
             p.remove_all_stripe(sino, snr=stripe_snr, la_size=la_size_for(sino.shape[1], la_size), sm_size=stripe_size, out=sino)
         elif stripe == "sorting" and stripe_size:
             p.remove_stripe_sorting(sino, size=stripe_size, out=sino)                                    # in place, on the device
+        cor = None
+        if find_center:
+            _, nx, nz = sino.shape
+            smin, smax = rotation_axis.widest_range(nx)
+            with rotation_axis.RotationAxis(ctx) as axis:
+                found = axis.find_center(sino, angles=np.asarray(data["phi"], np.float64), rows=rotation_axis.spread_rows(nz, center_rows),
+                                         smin=smin, smax=smax)
+            cor = float(rotation_axis.to_cor_shift(found.offset, 1)[0, 0])
         proj = sino.download()
     finally:
         for d in (d_frames, sino):
@@ -102,10 +117,14 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         proj = (proj / np.float32(data["mu"])).astype(np.float32)
     out = {k: v for k, v in data.items() if k not in RAW_KEYS}
     out["projections"] = proj
+    if cor is not None:
+        out["cor_offset"] = np.float64(cor)
     if verbose:
         print("preprocess: %s counts -> projections %s (stripe removal %s, window %s, phase retrieval %s)"
               % (counts.shape, proj.shape, stripe, (stripe_size or "off") if stripe != "none" else "off",
                  phase if phase is not None else "off"))
+        if cor is not None:
+            print("preprocess: rotation axis at cor_offset %+.3f px (offsets per row %s)" % (cor, found.offsets.tolist()))
     return out
 
 
@@ -131,7 +150,11 @@ def parse_args(argv=None):
     ap.add_argument("--zinger-dif", type=float, default=None, metavar="D",
                     help="remove zingers first: pixels of the counts and the flats D counts or more above their neighbourhood's median")
     ap.add_argument("--zinger-size", type=int, default=3, metavar="S", help="with --zinger-dif: the median window, 3, 5 or 7")
+    ap.add_argument("--find-center", action="store_true", help="find the rotation axis on the finished sinogram and store it as cor_offset")
+    ap.add_argument("--center-rows", type=int, default=9, metavar="K", help="with --find-center: the detector rows searched")
     a = ap.parse_args(argv)
+    if a.center_rows < 1:
+        ap.error("--center-rows must be >= 1")
     if a.zinger_dif is not None and not a.zinger_dif >= 0:
         ap.error("--zinger-dif must be >= 0")
     if a.zinger_size not in (3, 5, 7):
@@ -164,7 +187,8 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
-            stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size)
+            stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size,
+            find_center=a.find_center, center_rows=a.center_rows)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 
