@@ -167,6 +167,15 @@ TOMO_API int tomo_forward(tomo_ctx *ctx, const double *h_poses, int n_proj, cons
 TOMO_API int tomo_adjoint(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_proj, float *d_vol,
                  int accumulate);
 
+/* tomo_adjoint_update: one SIRT step on the volume in one pass, rec += V * A^T res; clamp at 0 if positivity; ||gt - rec||^2 if d_gt
+ *   (recon/sirt.py:61,63-67,73) -- tomo_adjoint followed by tomo_vec_update, bit for bit, without the back-projection volume between
+ *   them: the gather adjoint writes every voxel once from a register and stores the updated voxel instead.
+ *   *fused = 1 when done.  *fused = 0: nothing was launched and d_rec is untouched -- some projection of the call does not take the
+ *   gather adjoint (a tilted pose, a lattice that is not a unit lattice, adj_variant 1), d_V is NULL, or option "fused_update" is 0
+ *   (default 1); the caller then makes the two calls.  h_sumsq_err is written only when d_gt is given and *fused = 1. */
+TOMO_API int tomo_adjoint_update(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_res, float *d_rec, const float *d_V,
+                 int positivity, const float *d_gt, double *h_sumsq_err, int *fused);
+
 /* x-slab form of tomo_adjoint for pipelining the all-reduce of recon/sirt_mpi.py:103 with the back-projection:
  *   the volume is x-major, so the tile columns [xt0, xt1) (width *tile_width voxels, *n_xtiles of them) finalise the
  *   CONTIGUOUS voxel range x in [tile_width*xt0 - 1, tile_width*xt1 - 1) (clipped to [0, nx); the last column runs to nx)
@@ -239,6 +248,12 @@ TOMO_API int tomo_vec_recip_guard(tomo_ctx *ctx, float *d_v, int64_t n, float th
 TOMO_API int tomo_vec_fill(tomo_ctx *ctx, float *d_v, int64_t n, float value);
 TOMO_API int tomo_vec_residual_scale(tomo_ctx *ctx, const float *d_b, const float *d_ax, const float *d_w,
                             float *d_out, int64_t n, double *h_sumsq); /* out = w*(b-ax); sumsq = ||b-ax||^2  sirt.py:60-61,69 */
+/* the same pass for a sinogram of n_proj projections of the context's geometry (n = n_proj*ndx*ndz) that is back-projected next
+ * (sirt.py:60-61): it also notes which detector-z planes of d_out hold a non-zero value, so that the tomo_adjoint / tomo_adjoint_update
+ * that follows skips its own pass over d_out for them.  The note is dropped by any call in between that launches, copies or reduces;
+ * where it cannot be taken (no geometry, another n, poses the tile kernels decline) this is tomo_vec_residual_scale. */
+TOMO_API int tomo_vec_residual_scale_flags(tomo_ctx *ctx, const float *d_b, const float *d_ax, const float *d_w,
+                            float *d_out, int64_t n, int n_proj, double *h_sumsq);
 TOMO_API int tomo_vec_update(tomo_ctx *ctx, float *d_rec, const float *d_bp, const float *d_v, int64_t n,
                     int positivity, const float *d_gt, double *h_sumsq_err); /* rec += v*bp; clamp; ||gt-rec||^2  sirt.py:63-67,73 */
 /* the same update on one x slab of a pipelined iteration: no host synchronisation; ||gt-rec||^2 accumulates over the slabs on the

@@ -65,6 +65,7 @@ SIGNATURES = {
     "tomo_set_geometry": (ctypes.c_int, [_c_vp, ctypes.POINTER(TomoGeom)]),
     "tomo_forward": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, _c_vp]),
     "tomo_adjoint": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, _c_vp, ctypes.c_int]),
+    "tomo_adjoint_update": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp, _c_dp, ctypes.POINTER(ctypes.c_int)]),
     "tomo_adjoint_xslab_info": (ctypes.c_int, [_c_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tomo_adjoint_xslab": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int]),
     "tomo_forward_xslab": (ctypes.c_int, [_c_vp, _c_dp, ctypes.c_int, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int]),
@@ -80,6 +81,7 @@ SIGNATURES = {
     "tomo_vec_recip_guard": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, ctypes.c_int]),
     "tomo_vec_fill": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float]),
     "tomo_vec_residual_scale": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_dp]),
+    "tomo_vec_residual_scale_flags": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_dp]),
     "tomo_vec_update": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp, _c_dp]),
     "tomo_vec_update_acc": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp, ctypes.c_int]),
     "tomo_vec_update_acc_fetch": (ctypes.c_int, [_c_vp, _c_dp]),

@@ -20,6 +20,7 @@ _c_vp = ctypes.c_void_p
 
 class HipBackend(object):
     name = "hip"
+    notes_sinogram_planes = True      # residual_scale(..., n_proj=) exists
 
     def __init__(self, geometry, ctx=None):
         self.ctx = ctx if ctx is not None else _lib.Context()
@@ -68,6 +69,19 @@ class HipBackend(object):
             raise ValueError("adjoint: buffer sizes do not match geometry")
         self.ctx.check(self.lib.tomo_adjoint(self.ctx.handle, _lib.dptr(poses), n, proj.ptr, out.ptr, 1 if accumulate else 0))
         return out
+
+    def adjoint_update(self, poses, res, rec, v, positivity=False, gt=None):
+        """One SIRT step on the volume in one pass of the gather adjoint: rec += v * A^T res, clamp, ||gt - rec||^2 -- the bits of
+        adjoint() + update().  -> (fused, err): fused False means nothing was done (a pose of the call does not take the gather adjoint,
+        or option "fused_update" is 0) and the caller makes the two calls; err is None without gt."""
+        self._geom()
+        n = poses.shape[0]
+        if rec.size != self.n_vox or res.size != n * self.n_det or v.size != self.n_vox or (gt is not None and gt.size != self.n_vox):
+            raise ValueError("adjoint_update: buffer sizes do not match geometry")
+        s, fused = ctypes.c_double(0), ctypes.c_int(0)
+        self.ctx.check(self.lib.tomo_adjoint_update(self.ctx.handle, _lib.dptr(poses), n, res.ptr, rec.ptr, v.ptr, 1 if positivity else 0,
+                                                    gt.ptr if gt is not None else None, ctypes.byref(s), ctypes.byref(fused)))
+        return bool(fused.value), (s.value if (gt is not None and fused.value) else None)
 
     def xslab_info(self):
         """(number of x tile columns, their width in voxels) of the tile adjoint."""
@@ -209,10 +223,17 @@ class HipBackend(object):
         strict = thresh is None
         self.ctx.check(self.lib.tomo_vec_recip_guard(self.ctx.handle, buf.ptr, buf.size, 0.0 if strict else float(thresh), 1 if strict else 0))
 
-    def residual_scale(self, b, ax, w, out):
+    def residual_scale(self, b, ax, w, out, n_proj=None):
+        """out = w * (b - ax) -> ||b - ax||^2.  n_proj: `out` is a sinogram of n_proj projections of this geometry that is back-projected
+        next -- the pass then also notes its non-empty detector planes for that back-projection (tomo_vec_residual_scale_flags)."""
         s = ctypes.c_double(0)
-        self.ctx.check(self.lib.tomo_vec_residual_scale(self.ctx.handle, b.ptr, ax.ptr, w.ptr if w is not None else None, out.ptr,
-                                                        b.size, ctypes.byref(s)))
+        if n_proj is not None and b.size == int(n_proj) * self.n_det:
+            self._geom()
+            self.ctx.check(self.lib.tomo_vec_residual_scale_flags(self.ctx.handle, b.ptr, ax.ptr, w.ptr if w is not None else None, out.ptr,
+                                                                  b.size, int(n_proj), ctypes.byref(s)))
+        else:
+            self.ctx.check(self.lib.tomo_vec_residual_scale(self.ctx.handle, b.ptr, ax.ptr, w.ptr if w is not None else None, out.ptr,
+                                                            b.size, ctypes.byref(s)))
         return s.value
 
     def update(self, rec, bp, v, positivity=False, gt=None):

@@ -15,8 +15,10 @@
 // Row set-up shared by the flat kernels: for detector row `rix` of an untilted projection, the sample range [jlo, jhi) whose x, y
 // cells can fall into the tile's 16 x 16 footprint -- the row's line (tile-relative, sample 0 at (cbx, cby), direction (fdx, fdy))
 // clipped against the footprint widened by 2e-2 (conservative float32; exact ownership is decided per sample from the
-// fixed-point position).  One row per LANE; the callers broadcast the results with v_readlane.
-__device__ __forceinline__ void flat_row_range(float cbx, float cby, float fdx, float fdy, int n, bool row_ok, int &jlo, int &jhi, float xext = (float)ATX)
+// fixed-point position).  One row per LANE; the callers broadcast the results with v_readlane.  xext, yext: the footprint's extent in cells
+// (k_fwd_flat_tab clips it to the cells that have a node inside the volume).
+__device__ __forceinline__ void flat_row_range(float cbx, float cby, float fdx, float fdy, int n, bool row_ok, int &jlo, int &jhi, float xext = (float)ATX,
+                                               float yext = (float)ATY)
 {
     float t0 = 0.f, t1 = (float)(n - 1);
     if (fdx != 0.f) {
@@ -24,9 +26,9 @@ __device__ __forceinline__ void flat_row_range(float cbx, float cby, float fdx, 
         t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb));
     } else if (cbx < -2e-2f || cbx >= xext + 2e-2f) { t0 = 1.f; t1 = 0.f; }
     if (fdy != 0.f) {
-        const float inv = 1.f / fdy, ta = (-2e-2f - cby) * inv, tb = ((float)ATY + 2e-2f - cby) * inv;
+        const float inv = 1.f / fdy, ta = (-2e-2f - cby) * inv, tb = (yext + 2e-2f - cby) * inv;
         t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb));
-    } else if (cby < -2e-2f || cby >= (float)ATY + 2e-2f) { t0 = 1.f; t1 = 0.f; }
+    } else if (cby < -2e-2f || cby >= yext + 2e-2f) { t0 = 1.f; t1 = 0.f; }
     jlo = jhi = 0;
     if (row_ok && t0 <= t1) {
         jlo = max(0, (int)ceilf(t0));
@@ -486,12 +488,21 @@ __global__ __launch_bounds__(256) void k_fwd_live(const float *__restrict__ vol,
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool in0 = z0 + lane < g.nz, in1 = z0 + FLZ + lane < g.nz;
     bool nz0 = false, nz1 = false;
-    for (int c = wv; c < ALX * ALY; c += 4) {                        // a wave reads a column's 2 x 64 planes: 2 x 256 B, coalesced
-        const int gx = x0 + c / ALY, gy = y0 + c % ALY;
-        if (gx < 0 || gx >= g.nx || gy < 0 || gy >= g.ny) continue;
-        const float *col = vol + ((size_t)gx * g.ny + gy) * g.nz + z0 + lane;
-        if (in0) nz0 |= col[0] != 0.f;
-        if (in1) nz1 |= col[FLZ] != 0.f;
+    // a wave reads a column's 2 x 64 planes: 2 x 256 B, coalesced -- FOUR columns per trip (eight independent loads in flight), then one
+    // wave-uniform test: with one column per trip an all-zero block walked its columns as that many serial round trips to memory
+    for (int c0 = wv; c0 < ALX * ALY; c0 += 16) {
+        float a0[4], a1[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + 4 * k;
+            const int gx = x0 + c / ALY, gy = y0 + c % ALY;
+            const bool ok = c < ALX * ALY && gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
+            const float *col = vol + ((size_t)(ok ? gx : 0) * g.ny + (ok ? gy : 0)) * g.nz + z0 + lane;
+            a0[k] = (ok && in0) ? col[0] : 0.f;
+            a1[k] = (ok && in1) ? col[FLZ] : 0.f;
+        }
+        nz0 |= a0[0] != 0.f || a0[1] != 0.f || a0[2] != 0.f || a0[3] != 0.f;
+        nz1 |= a1[0] != 0.f || a1[1] != 0.f || a1[2] != 0.f || a1[3] != 0.f;
         if (__builtin_amdgcn_ballot_w64(nz0) && __builtin_amdgcn_ballot_w64(nz1)) break;      // wave-uniform: both images known to be live
     }
     const int l0 = __syncthreads_or(nz0), l1 = __syncthreads_or(nz1);
@@ -551,7 +562,12 @@ __global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_tab(const AdjC *__re
         img[e] = v;
     }
     __syncthreads();
-    const float bcx = (float)x0 + 0.5f * ATX, bcy = (float)y0 + 0.5f * ATY;
+    // The footprint CLIPPED to the volume: cell lx has the nodes x0 + lx and x0 + lx + 1, so the cells lx >= nx - x0 (the last tile column
+    // of a volume whose nx is a multiple of ATX keeps ONE of its ATX cells) hold zeros only, likewise in y.  The row range and the detector
+    // rows enumerated below shrink with it; only samples that read zeros go, the row sums keep their bits.  (x0, y0 >= -1 and the tile
+    // grid ends at the volume: the extents are >= 1.)
+    const float xext = (float)min(ATX, g.nx - x0), yext = (float)min(ATY, g.ny - y0);
+    const float bcx = (float)x0 + 0.5f * xext, bcy = (float)y0 + 0.5f * yext;
     const int64_t orgx = (int64_t)x0 << 32, orgy = (int64_t)y0 << 32;
     const size_t n_det = (size_t)g.ndx * g.ndz;
     const float two_m32 = 2.3283064365386963e-10f;
@@ -583,7 +599,7 @@ __global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_tab(const AdjC *__re
         const float qx = bcx - (float)c.p0[0], qy = bcy - (float)c.p0[1];
         const float m00 = (float)c.minv[0][0], m01 = (float)c.minv[0][1];
         const float ixc = m00 * qx + m01 * qy;
-        const float ixr = fabsf(m00) * (0.5f * ATX) + fabsf(m01) * (0.5f * ATY) + 2e-2f;
+        const float ixr = fabsf(m00) * (0.5f * xext) + fabsf(m01) * (0.5f * yext) + 2e-2f;
         const int ix_lo = max(0, (int)ceilf(fmaxf(ixc - ixr, -1.f)));
         const int ix_hi = min(g.ndx - 1, (int)floorf(fminf(ixc + ixr, (float)g.ndx)));
         if (ix_lo > ix_hi) continue;
@@ -600,7 +616,7 @@ __global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_tab(const AdjC *__re
             int v_jlo, v_jhi;
             {
                 const int rix = ix_lo + r0 + lane;
-                flat_row_range(fp0x + (float)rix * fux, fp0y + (float)rix * fuy, fdx, fdy, c.n, rix <= ix_hi, v_jlo, v_jhi);
+                flat_row_range(fp0x + (float)rix * fux, fp0y + (float)rix * fuy, fdx, fdy, c.n, rix <= ix_hi, v_jlo, v_jhi, xext, yext);
             }
             const int r_end = min(64, n_rows_w - r0);
             int64_t rbx = c.fp0[0] + (int64_t)(ix_lo + r0) * k_fux - orgx, rby = c.fp0[1] + (int64_t)(ix_lo + r0) * k_fuy - orgy;

@@ -99,10 +99,60 @@ __global__ __launch_bounds__(64) void k_zchunk_shift(const unsigned char *__rest
     if (threadIdx.x == 0) *shift = first >= n_chunk ? 0 : (GWAVES - first % GWAVES) % GWAVES;
 }
 
-template <int NJ>      // samples per row that can reach a column: 3 for step >= 0.95 voxel, 6 for step >= 0.475
+// The SIRT update as the kernel's store (UPD = 1): a lane holds the 64 back-projected values of its column in registers and every voxel is
+// written exactly once, so rec = rec + V * acc (a product and a sum, each rounded, as k_update in tomo_ctx.hip: both pin that, the
+// build contracts by default), the clamp at 0 and the error sum
+// (gt - rec)^2 go where the store is -- no back-projection volume is filled, written, read back and passed over once more by k_update.
+// ZERO: a wave whose planes receive nothing (acc = 0) but whose voxels k_update would still clamp and count.
+template <bool ZERO>
+__device__ __forceinline__ void gather_update_store(float *__restrict__ dst, const float *__restrict__ vv, const float *__restrict__ gt, const f32x2 (&acc2)[32],
+                                                    int z0, int nz, int positivity, double *__restrict__ err_out)
+{
+    double err = 0.0;
+#define G_UPD1(R, A, V, G)                                  \
+    {                                                       \
+        float pr_ = (A) * (V);                              \
+        asm volatile("" : "+v"(pr_));       /* the product is rounded on its own: never contracted into an fma with the sum */ \
+        R = R + pr_;                                        \
+        if (positivity && R < 0.f) R = 0.f;                 \
+        if (gt) { const float e_ = (G) - R; err += (double)e_ * (double)e_; } \
+    }
+    if (z0 + 64 <= nz && (nz & 3) == 0) {
+#pragma unroll
+        for (int p = 0; p < 64; p += 4) {
+            float4 r = *(float4 *)(dst + p);
+            const float4 v = *(const float4 *)(vv + p);
+            float4 t = {0.f, 0.f, 0.f, 0.f};
+            if (gt) t = *(const float4 *)(gt + p);
+            G_UPD1(r.x, ZERO ? 0.f : acc2[p / 2].x, v.x, t.x)
+            G_UPD1(r.y, ZERO ? 0.f : acc2[p / 2].y, v.y, t.y)
+            G_UPD1(r.z, ZERO ? 0.f : acc2[p / 2 + 1].x, v.z, t.z)
+            G_UPD1(r.w, ZERO ? 0.f : acc2[p / 2 + 1].y, v.w, t.w)
+            *(float4 *)(dst + p) = r;
+            __builtin_amdgcn_sched_barrier(0);      // one quad's loads in flight beside the 64 accumulators, not all sixteen (spills)
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 64; ++p)
+            if (z0 + p < nz) {
+                float r = dst[p];
+                G_UPD1(r, ZERO ? 0.f : ((p & 1) ? acc2[p / 2].y : acc2[p / 2].x), vv[p], gt[p])
+                dst[p] = r;
+            }
+    }
+#undef G_UPD1
+    if (gt) {                                                           // wave-uniform
+        err = wave_sum_d(err);
+        if ((threadIdx.x & 63) == 0) atomicAdd(err_out, err);           // one double atomic per wave (waves of a work-group end at different times)
+    }
+}
+
+template <int NJ, int UPD>      // NJ: samples per row that can reach a column: 3 for step >= 0.95 voxel, 6 for step >= 0.475; UPD: the store is the SIRT update
 __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(const GfC *__restrict__ cs, int n_proj, const float *__restrict__ proj,
                                                                  float *__restrict__ vol, TomoGeomC g, int xs, int xe, int patched,
-                                                                 const unsigned char *__restrict__ zflags, int zc_lo, int zc_hi, const int *__restrict__ zshift)
+                                                                 const unsigned char *__restrict__ zflags, int zc_lo, int zc_hi, const int *__restrict__ zshift,
+                                                                 const float *__restrict__ upd_v, const float *__restrict__ upd_gt, int positivity,
+                                                                 double *__restrict__ upd_err)
 {
     __shared__ __attribute__((aligned(16))) float rows[GWAVES][GROWS * GPITCH];
     __shared__ float4 wtab[3][GWAVES][64];          // [group mod 3][projection of the group][column] = (i0, W0, W1, W2)
@@ -155,6 +205,15 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
 #if !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__) && defined(__HIP_DEVICE_COMPILE__)
 #error "k_adj_gather_flat: divergent exit before barriers is only known to be safe on gfx9-family targets (s_barrier ignores ended waves)"
 #endif
+    if (UPD && !zlive && z0 >= 0 && z0 < g.nz && (positivity || upd_gt)) {
+        // its voxels receive nothing, rec + V * 0 = rec: nothing to store -- unless the update clamps or sums the error, which k_update does for every voxel
+        const int X = x0 + (lane >> 3), Y = y0 + (lane & 7);
+        if (X < xe && Y < g.ny) {
+            const size_t o = ((size_t)X * g.ny + Y) * g.nz + z0;
+            f32x2 none[32];
+            gather_update_store<true>(vol + o, upd_v + o, upd_gt ? upd_gt + o : nullptr, none, z0, g.nz, positivity, upd_err);
+        }
+    }
     if (!zlive) return;
     // a lane is a voxel COLUMN (X, Y) with 64 plane accumulators, except while loading sinogram rows, where it is plane Zl
     const int X = x0 + (lane >> 3), Y = y0 + (lane & 7), Zl = z0 + lane;
@@ -313,7 +372,12 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
 #undef G_TABLE
 #undef G_SETUP
     // ---- store: the lane's column is 64 consecutive floats of the volume
-    if (zlive && X < xe && Y < g.ny) {
+    if (UPD) {
+        if (X < xe && Y < g.ny) {
+            const size_t o = ((size_t)X * g.ny + Y) * g.nz + z0;
+            gather_update_store<false>(vol + o, upd_v + o, upd_gt ? upd_gt + o : nullptr, acc2, z0, g.nz, positivity, upd_err);
+        }
+    } else if (zlive && X < xe && Y < g.ny) {
         float *dst = vol + ((size_t)X * g.ny + Y) * g.nz + z0;
         if (z0 + 64 <= g.nz && (g.nz & 3) == 0) {
 #pragma unroll

@@ -73,6 +73,11 @@ struct tomo_ctx {
     int zf_nproj = 0;
     bool zf_has_cum = false, zf_has_shift = false;
     int zf_ndz = 0, zf_ndx = 0, zf_nz = 0, zf_zc_lo = 0, zf_zc_hi = 0;   // ... and the geometry / pose z offsets they were computed for
+    // true: the flags of zf_src were recorded by the pass that WROTE that sinogram (tomo_vec_residual_scale_flags) and nothing has been
+    // launched, copied or reduced on this context since -- the next back-projection of zf_src takes them without the caller's word
+    // (reuse_sino_flags) and without its own scan.  Dropped by every launch (TOMO_LAUNCH) and by the copies, fills, frees and collectives
+    // that can write a caller's buffer (tomo_ctx.hip): recorded flags serve exactly the call that follows their recording.
+    bool zf_recorded = false;
     size_t fwd_blk_flat_ints = 0;       // ints of d_blk the flat forward of the current call uses (the general kernel's tile list follows)
     // general float workspace (grow-only): the TV-FISTA proximal step keeps its 7 fields here across calls
     float *d_ws = nullptr;
@@ -87,6 +92,7 @@ struct tomo_ctx {
     int grad_variant = 4;     // 1 plain, 2 eight dword gathers + packed lerps, 3 four gathers + DPP neighbour shift, 4 (default) 2 or 3 per pose by tilt
     int grad_v1_prec = 0;     // diagnostic for grad_variant 1 (per-ray tomo_proj_grad only): bit 0 float64 sample positions, bit 1 float64 lerps and sums
     int tile_flat = 1;      // 1: untilted projections take the flat tile kernels
+    int fused_update = 1;     // 1: tomo_adjoint_update folds the SIRT update into the gather adjoint's store when all its poses take that kernel; 0: it always declines (the caller's two calls)
     int adj_flat_gather = 1;  // 1: untilted unit lattices take the gather-form adjoint (k_adj_gather_flat) instead of the LDS-atomic flat kernel
     int fwd_flat_tab = 1;     // 1 (default): the flat forward with the sample table in LDS and the two images interleaved per plane (k_fwd_flat_tab); 0: the round-2 kernel (k_fwd_flat_z<2>: entries broadcast with v_readlane)
     int fwd_flat_wide = 0;    // 1: measurement variant of the flat forward -- 32 x 16 x 63 footprint, one image per work-group (k_fwd_flat_z<1, 32>); only in builds with -DTOMO_MEASUREMENT_VARIANTS
@@ -128,6 +134,9 @@ int tomo_ensure_red(tomo_ctx *ctx, size_t n_doubles);
 int tomo_ensure_red_part(tomo_ctx *ctx, size_t n_doubles);
 int tomo_ensure_ws(tomo_ctx *ctx, size_t n_floats);
 int tomo_ensure_blk(tomo_ctx *ctx, size_t n_ints);
+// the passes and the cache key that go with freshly written sinogram plane flags (tomo_project.hip)
+int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, unsigned char *d_zf, int *d_zcum, int *d_zshift,
+                       const char *prof_name, bool recorded);
 void tomo_csr_release(tomo_ctx *ctx);
 void tomo_prof_begin(tomo_ctx *ctx, const char *name);
 void tomo_prof_end(tomo_ctx *ctx);
@@ -154,6 +163,7 @@ void tomo_prof_end_on(tomo_ctx *ctx, hipStream_t stream);
 // launch with optional event bracketing (tomo_profile_enable) and launch-error check
 #define TOMO_LAUNCH(ctx, name, kern, grid, block, shmem, ...)                                   \
     do {                                                                                        \
+        (ctx)->zf_recorded = false;                                                             \
         tomo_prof_begin((ctx), (name));                                                         \
         hipLaunchKernelGGL(kern, (grid), (block), (shmem), (ctx)->stream, __VA_ARGS__);         \
         tomo_prof_end((ctx));                                                                   \

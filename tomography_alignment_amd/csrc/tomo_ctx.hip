@@ -100,6 +100,7 @@ extern "C" int tomo_free(tomo_ctx *ctx, void *d_ptr)
 {
     if (!ctx) return tomo_fail(ctx, TOMO_ERR_ARG, "null ctx");
     if (!d_ptr) return TOMO_OK;
+    ctx->zf_recorded = false;             // the address may come back as another buffer
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     TOMO_HIP(ctx, hipFree(d_ptr));
     return TOMO_OK;
@@ -108,6 +109,7 @@ extern "C" int tomo_free(tomo_ctx *ctx, void *d_ptr)
 extern "C" int tomo_memcpy_h2d(tomo_ctx *ctx, void *d, const void *h, size_t bytes)
 {
     if (!ctx) return tomo_fail(ctx, TOMO_ERR_ARG, "null ctx");
+    ctx->zf_recorded = false;             // d may be the sinogram whose plane flags were recorded
     TOMO_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));   // caller may reuse h immediately
     return TOMO_OK;
@@ -124,6 +126,7 @@ extern "C" int tomo_memcpy_d2h(tomo_ctx *ctx, void *h, const void *d, size_t byt
 extern "C" int tomo_memcpy_d2d(tomo_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
     if (!ctx) return tomo_fail(ctx, TOMO_ERR_ARG, "null ctx");
+    ctx->zf_recorded = false;
     TOMO_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return TOMO_OK;
 }
@@ -131,6 +134,7 @@ extern "C" int tomo_memcpy_d2d(tomo_ctx *ctx, void *dst, const void *src, size_t
 extern "C" int tomo_memset0(tomo_ctx *ctx, void *d, size_t bytes)
 {
     if (!ctx) return tomo_fail(ctx, TOMO_ERR_ARG, "null ctx");
+    ctx->zf_recorded = false;
     TOMO_HIP(ctx, hipMemsetAsync(d, 0, bytes, ctx->stream));
     return TOMO_OK;
 }
@@ -189,6 +193,7 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
     else if (!strcmp(key, "comm_test_copy_eighths")) ctx->comm_test_copy_eighths = value < 0 ? 0 : value;
     else if (!strcmp(key, "comm_test_copy_wgs")) ctx->comm_test_copy_wgs = value < 0 ? 0 : value;
     else if (!strcmp(key, "adj_flat_gather")) ctx->adj_flat_gather = value;
+    else if (!strcmp(key, "fused_update")) ctx->fused_update = value;
     else if (!strcmp(key, "fwd_flat_ztiles")) ctx->fwd_flat_ztiles = value;
     else if (!strcmp(key, "fwd_flat_wide")) {
 #ifdef TOMO_MEASUREMENT_VARIANTS
@@ -583,6 +588,26 @@ __global__ __launch_bounds__(256) void k_residual_scale(const float *__restrict_
     block_atomic_sum(acc, sumsq);
 }
 
+// The same pass, also recording which detector-z planes of `out` hold a non-zero value (what k_sino_zflags finds with a pass of its own
+// before the back-projection).  The grid stride is a multiple of ndz (host), so a thread meets ONE plane, iz = its first index mod ndz:
+// "saw a non-zero" stays in a register, one byte store at the end; flags pre-zeroed, benign races (everybody stores 1).
+__global__ __launch_bounds__(256) void k_residual_scale_flags(const float *__restrict__ b, const float *__restrict__ ax, const float *__restrict__ w,
+                                                              float *__restrict__ out, int64_t n, double *sumsq, int ndz, unsigned char *__restrict__ flags)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double acc = 0.0;
+    bool nz = false;
+    for (int64_t i = i0; i < n; i += stride) {
+        float r = b[i] - ax[i];
+        acc += (double)r * (double)r;
+        const float o = w ? w[i] * r : r;
+        nz |= o != 0.f;
+        out[i] = o;
+    }
+    if (nz) flags[(int)(i0 % ndz)] = 1;
+    block_atomic_sum(acc, sumsq);
+}
+
 // rec += v*bp ; rec = max(rec,0) if positivity ; err += (gt-rec)^2     recon/sirt.py:63-67,73
 __global__ __launch_bounds__(256) void k_update(float *__restrict__ rec, const float *__restrict__ bp, const float *__restrict__ v,
                                                 int64_t n, int positivity, const float *__restrict__ gt, double *sumsq)
@@ -590,7 +615,11 @@ __global__ __launch_bounds__(256) void k_update(float *__restrict__ rec, const f
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float r = rec[i] + (v ? bp[i] * v[i] : bp[i]);
+        float r;
+        {
+#pragma clang fp contract(off)      // product and sum each rounded: the gather adjoint's update epilogue (gather_update_store) gives the same bits
+            r = rec[i] + (v ? bp[i] * v[i] : bp[i]);
+        }
         if (positivity && r < 0.f) r = 0.f;
         rec[i] = r;
         if (gt) { float e = gt[i] - r; acc += (double)e * (double)e; }
@@ -625,6 +654,45 @@ extern "C" int tomo_vec_residual_scale(tomo_ctx *ctx, const float *b, const floa
     if (rc) return rc;
     TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));
     TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale, dim3(vec_grid(n)), dim3(256), 0, b, ax, w, out, n, ctx->d_red);
+    return h_sumsq ? red_fetch(ctx, h_sumsq) : TOMO_OK;
+}
+
+// tomo_vec_residual_scale for a sinogram of the context's geometry (n = n_proj * ndx * ndz): when the poses the projector last staged are
+// n_proj poses the tile kernels take, the pass also records the sinogram's non-empty detector planes under the key the tile adjoint checks
+// and runs the small passes that derive from them (chunk shift, prefix counts) -- the back-projection of `out` that follows then finds
+// them and skips its own scan of the sinogram.  Anything else (no geometry, other sizes, a stride ndz does not divide): the plain pass.
+extern "C" int tomo_vec_residual_scale_flags(tomo_ctx *ctx, const float *b, const float *ax, const float *w, float *out, int64_t n,
+                                             int n_proj, double *h_sumsq)
+{
+    VEC_CHECK(ctx, n);
+    int rc = tomo_ensure_red(ctx, 8);
+    if (rc) return rc;
+    const TomoGeomC &g = ctx->g;
+    const int grid = vec_grid(n);
+    bool record = ctx->has_geom && n_proj > 0 && g.ndz > 0 && n == (int64_t)n_proj * g.ndx * g.ndz && ((int64_t)grid * 256) % g.ndz == 0 &&
+                  ctx->tile_cache_valid && ctx->tile_cache_ok && ctx->tile_cache_poses.size() == (size_t)n_proj * TOMO_POSE_STRIDE &&
+                  ctx->adj_variant != 1;
+    unsigned char *d_zf = nullptr;
+    int *d_zcum = nullptr, *d_zshift = nullptr;
+    if (record) {
+        const size_t zf_ints = ((size_t)g.ndz + 3) / 4;                 // layout of the head of d_blk: as adjoint_tiles (tomo_project.hip)
+        rc = tomo_ensure_blk(ctx, zf_ints + (size_t)g.ndz + 2);
+        if (rc) return rc;
+        d_zf = (unsigned char *)ctx->d_blk;
+        d_zcum = ctx->d_blk + zf_ints;
+        d_zshift = d_zcum + g.ndz + 1;
+    }
+    ctx->zf_src = nullptr;                                              // `out` is rewritten: whatever was cached for it is void
+    TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));
+    if (!record)
+        TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale, dim3(grid), dim3(256), 0, b, ax, w, out, n, ctx->d_red);
+    else {
+        const bool want_cum = n_proj > ctx->tile_cache_nflat, want_shift = ctx->tile_cache_ngather > 0;
+        TOMO_HIP(ctx, hipMemsetAsync(d_zf, 0, (size_t)g.ndz, ctx->stream));
+        TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale_flags, dim3(grid), dim3(256), 0, b, ax, w, out, n, ctx->d_red, g.ndz, d_zf);
+        rc = tomo_record_zflags(ctx, out, n_proj, want_cum, want_shift, d_zf, d_zcum, d_zshift, "k_residual_scale", true);
+        if (rc) return rc;
+    }
     return h_sumsq ? red_fetch(ctx, h_sumsq) : TOMO_OK;
 }
 
@@ -793,6 +861,7 @@ extern "C" int tomo_allreduce_sum_f32(tomo_ctx *ctx, float *d_buf, int64_t n)
     TomoRange roctx_range("tomo_allreduce_sum_f32");
     if (!ctx) return tomo_fail(ctx, TOMO_ERR_ARG, "null ctx");
     if (!ctx->comm) return ctx->n_ranks == 1 ? TOMO_OK : tomo_fail(ctx, TOMO_ERR_STATE, "comm not initialised");
+    ctx->zf_recorded = false;
     tomo_prof_begin(ctx, "allreduce_f32");
     ncclResult_t r = ncclAllReduce(d_buf, d_buf, (size_t)n, ncclFloat32, ncclSum, ctx->comm, ctx->stream);
     tomo_prof_end(ctx);
@@ -835,6 +904,7 @@ static int comm_async(tomo_ctx *ctx, int kind, float *d_buf, int64_t n)
     TomoRange roctx_range(kind == COLL_ALLREDUCE ? "tomo_allreduce_sum_f32_async" : kind == COLL_REDUCE_SCATTER ? "tomo_reduce_scatter_sum_f32_async" : "tomo_allgather_f32_async");
     if (!ctx || n < 0) return tomo_fail(ctx, TOMO_ERR_ARG, "bad args");
     if (!ctx->comm) return ctx->n_ranks == 1 ? TOMO_OK : tomo_fail(ctx, TOMO_ERR_STATE, "comm not initialised");
+    ctx->zf_recorded = false;
     if (!ctx->comm_stream) {
         TOMO_HIP(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
         TOMO_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_compute, hipEventDisableTiming));

@@ -358,9 +358,38 @@ static int adjoint_atomic(tomo_ctx *ctx, const double *h_poses, int n_proj, cons
     return TOMO_OK;
 }
 
+// The passes that derive from freshly written plane flags (d_zf, in d_blk) and the key under which adjoint_tiles finds them: used by
+// adjoint_tiles after its own scan and by tomo_vec_residual_scale_flags (tomo_ctx.hip), whose residual pass wrote the flags itself
+// (recorded = true: see tomo_ctx.h, zf_recorded).  zc range: that of the poses staged last (stage_tile_consts).
+int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, unsigned char *d_zf, int *d_zcum, int *d_zshift,
+                       const char *prof_name, bool recorded)
+{
+    const TomoGeomC &g = ctx->g;
+    if (want_cum) TOMO_LAUNCH(ctx, prof_name, k_zflags_prefix, dim3(1), dim3(1024), 0, (const unsigned char *)d_zf, g.ndz, d_zcum);
+    if (want_shift)
+        TOMO_LAUNCH(ctx, prof_name, k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)d_zf, g.ndz, g.nz, ctx->tile_cache_zc_lo,
+                    ctx->tile_cache_zc_hi, d_zshift);
+    ctx->zf_src = d_proj;
+    ctx->zf_nproj = n_proj;
+    ctx->zf_has_cum = want_cum;
+    ctx->zf_has_shift = want_shift;
+    ctx->zf_ndz = g.ndz; ctx->zf_ndx = g.ndx; ctx->zf_nz = g.nz;
+    ctx->zf_zc_lo = ctx->tile_cache_zc_lo; ctx->zf_zc_hi = ctx->tile_cache_zc_hi;
+    ctx->zf_recorded = recorded;
+    return TOMO_OK;
+}
+
+// What tomo_adjoint_update hands to adjoint_tiles: the gather kernel's store becomes rec = rec + V * acc (kernels_tile_gather.hip.h)
+struct GatherUpd {
+    const float *v, *gt;
+    int positivity;
+};
+
 // tile adjoint restricted to the x tile columns [xt0, xt1): adds into d_vol (the caller zeroes it).  *done = false when the
-// poses do not qualify for the tile kernels (nothing launched).
-static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_proj, float *d_vol, int xt0, int xt1, bool *done)
+// poses do not qualify for the tile kernels (nothing launched).  With `upd`, d_vol is the reconstruction and the call is the whole SIRT
+// step on it: *done = true only when EVERY projection takes the gather kernel (otherwise nothing is launched and nothing changed).
+static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_proj, float *d_vol, int xt0, int xt1, bool *done,
+                         const GatherUpd *upd = nullptr)
 {
     const TomoGeomC &g = ctx->g;
     const size_t n_det = (size_t)g.ndx * g.ndz;
@@ -378,6 +407,7 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     const int n_xt = (int)grid.z;
     xt0 = std::max(xt0, 0);
     xt1 = std::min(xt1, n_xt);
+    if (upd && (n_gather != n_proj || xt0 != 0 || xt1 != n_xt)) return TOMO_OK;
     *done = true;
     if (xt1 <= xt0) return TOMO_OK;
     grid.z = (unsigned)(xt1 - xt0);
@@ -400,7 +430,8 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
         // (option "reuse_sino_flags": the x-slab calls of one back-projection pass scan the sinogram once, not once per slab)
         // The key holds everything the cached words depend on: the sinogram and its shape (layout of d_zf / d_zcum), and the
         // volume height and the poses' integer z offsets the chunk shift was computed from.
-        const bool cached = ctx->reuse_sino_flags && ctx->zf_src == (const void *)d_proj && ctx->zf_nproj == n_proj && (ctx->zf_has_cum || !want_cum) &&
+        // (zf_recorded: the flags were recorded by the residual pass that wrote d_proj and nothing ran since -- no caller's word needed)
+        const bool cached = (ctx->reuse_sino_flags || ctx->zf_recorded) && ctx->zf_src == (const void *)d_proj && ctx->zf_nproj == n_proj && (ctx->zf_has_cum || !want_cum) &&
                             (ctx->zf_has_shift || n_gather == 0) && ctx->zf_ndz == g.ndz && ctx->zf_ndx == g.ndx && ctx->zf_nz == g.nz &&
                             ctx->zf_zc_lo == ctx->tile_cache_zc_lo && ctx->zf_zc_hi == ctx->tile_cache_zc_hi;
         if (!cached) {
@@ -408,16 +439,8 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
             const long long n_rows = (long long)n_proj * g.ndx;
             const unsigned gy = (unsigned)std::min<long long>(n_rows, 4096);
             TOMO_LAUNCH(ctx, "k_sino_zflags", k_sino_zflags, dim3((unsigned)((g.ndz + 255) / 256), gy), dim3(256), 0, d_proj, n_rows, g.ndz, d_zf);
-            if (want_cum) TOMO_LAUNCH(ctx, "k_sino_zflags", k_zflags_prefix, dim3(1), dim3(1024), 0, (const unsigned char *)d_zf, g.ndz, d_zcum);
-            if (n_gather > 0)
-                TOMO_LAUNCH(ctx, "k_sino_zflags", k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)d_zf, g.ndz, g.nz, ctx->tile_cache_zc_lo,
-                            ctx->tile_cache_zc_hi, d_zshift);
-            ctx->zf_src = (const void *)d_proj;
-            ctx->zf_nproj = n_proj;
-            ctx->zf_has_cum = want_cum;
-            ctx->zf_has_shift = n_gather > 0;
-            ctx->zf_ndz = g.ndz; ctx->zf_ndx = g.ndx; ctx->zf_nz = g.nz;
-            ctx->zf_zc_lo = ctx->tile_cache_zc_lo; ctx->zf_zc_hi = ctx->tile_cache_zc_hi;
+            rc = tomo_record_zflags(ctx, d_proj, n_proj, want_cum, n_gather > 0, d_zf, d_zcum, d_zshift, "k_sino_zflags", false);
+            if (rc) return rc;
         }
     }
     if (n_gather > 0) {
@@ -432,12 +455,16 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
             if (n_wg >= ((long long)1 << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather adjoint: grid too large");
             const dim3 ggrid((unsigned)n_wg);
             const int zc_lo = ctx->tile_cache_zc_lo, zc_hi = ctx->tile_cache_zc_hi;
-            if (ctx->tile_cache_eb_max < 1.49)
-                TOMO_LAUNCH(ctx, "k_adj_gather_flat", k_adj_gather_flat<3>, ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, d_vol, g, xs, xe, patched,
-                            (const unsigned char *)d_zf, zc_lo, zc_hi, (const int *)d_zshift);
-            else        // finer sampling along the rays (step down to ~0.475 voxel): six samples per row can reach a column
-                TOMO_LAUNCH(ctx, "k_adj_gather_flat", k_adj_gather_flat<6>, ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, d_vol, g, xs, xe, patched,
-                            (const unsigned char *)d_zf, zc_lo, zc_hi, (const int *)d_zshift);
+            const float *u_v = upd ? upd->v : nullptr, *u_gt = upd ? upd->gt : nullptr;
+            const int u_pos = upd ? upd->positivity : 0;
+            if (upd && upd->gt) TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));      // the slot k_update sums into (tomo_vec_update)
+#define GATHER_LAUNCH(NJ, UPD)                                                                                                                       \
+    TOMO_LAUNCH(ctx, "k_adj_gather_flat", (k_adj_gather_flat<NJ, UPD>), ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, d_vol, g, xs, xe, patched, \
+                (const unsigned char *)d_zf, zc_lo, zc_hi, (const int *)d_zshift, u_v, u_gt, u_pos, ctx->d_red)
+            // NJ = 6: finer sampling along the rays (step down to ~0.475 voxel): six samples per row can reach a column
+            if (ctx->tile_cache_eb_max < 1.49) { if (upd) GATHER_LAUNCH(3, 1); else GATHER_LAUNCH(3, 0); }
+            else { if (upd) GATHER_LAUNCH(6, 1); else GATHER_LAUNCH(6, 0); }
+#undef GATHER_LAUNCH
         }
     }
     if (n_proj == n_gather) return TOMO_OK;
@@ -491,6 +518,34 @@ extern "C" int tomo_adjoint(tomo_ctx *ctx, const double *h_poses, int n_proj, co
     if (rc) return rc;
     if (done) return TOMO_OK;
     return adjoint_atomic(ctx, h_poses, n_proj, d_proj, d_vol, accumulate);
+}
+
+// One SIRT step on the volume, rec += V * A^T res (clamp at 0, ||gt - rec||^2), as ONE pass of the gather adjoint: the kernel holds a voxel's
+// back-projected value in a register when it stores, so it stores the updated reconstruction instead -- no back-projection volume, no
+// fill of it, no k_update.  *fused = 0 (nothing launched, d_rec untouched; the caller runs tomo_adjoint + tomo_vec_update) unless every
+// projection of the call takes the gather kernel; option "fused_update" 0 declines always.  Same bits as the two calls.
+extern "C" int tomo_adjoint_update(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_res, float *d_rec, const float *d_V, int positivity,
+                                   const float *d_gt, double *h_sumsq_err, int *fused)
+{
+    TomoRange roctx_range("tomo_adjoint_update");
+    TOMO_NEED_GEOM(ctx);
+    if (!h_poses || !d_res || !d_rec || n_proj < 0 || !fused) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_adjoint_update: bad args");
+    *fused = 0;
+    if (n_proj == 0 || !d_V || !ctx->fused_update) return TOMO_OK;
+    int rc = tomo_ensure_red(ctx, 8);
+    if (rc) return rc;
+    const GatherUpd upd = {d_V, d_gt, positivity};
+    bool done = false;
+    rc = adjoint_tiles(ctx, h_poses, n_proj, d_res, d_rec, 0, INT_MAX, &done, &upd);
+    if (rc) return rc;
+    if (!done) return TOMO_OK;
+    *fused = 1;
+    if (d_gt && h_sumsq_err) {
+        TOMO_HIP(ctx, hipMemcpyAsync(ctx->h_red, ctx->d_red, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *h_sumsq_err = ctx->h_red[0];
+    }
+    return TOMO_OK;
 }
 
 // x-slab form for pipelining the all-reduce with the back-projection (volume is x-major: the tile columns [xt0, xt1) finalise

@@ -44,6 +44,10 @@ class SIRT(object):
         self._stop_after = 0         # stop test needs k > 0 (sirt.py:75) / k > 1 (sirt_mpi.py:116)
         self._initialize()
 
+    # the back-projection and the update as ONE pass of the gather adjoint (backend.adjoint_update) where the backend offers it and every
+    # pose takes that kernel; the sharded subclass all-reduces the back-projection between the two and keeps them apart
+    _fuse_update = True
+
     # ---- hooks the sharded subclass overrides
     def _my_rows(self):
         return np.arange(self.n_proj)
@@ -136,9 +140,8 @@ class SIRT(object):
         t_start = time.time()
         while k < niter and not stop:
             self._forward()                                                             # sirt.py:59
-            sumsq = be.residual_scale(self.d_b, self.d_ax, self.d_W, self.d_res)        # :60-61 (W * res) and :69
-            self._backproject_scaled()                                                  # :61,63 ; sirt_mpi.py:98-103
-            err = self._update(positivity, last=(k + 1 >= niter))                       # :64-67,73
+            sumsq = self._residual()                                                    # :60-61 (W * res) and :69
+            err = self._backproject_update(positivity, last=(k + 1 >= niter))           # :61,63-67,73 ; sirt_mpi.py:98-103
             convergence[k] = np.sqrt(self._allreduce_scalar(sumsq))                     # :69 ; sirt_mpi.py:110
             rms_error[k] = convergence[k] / norm_factor if self.d_gt is None else np.sqrt(err) / norm_factor
             if k > self._stop_after and rms_error[k] > rms_error[k - 1]:
@@ -156,6 +159,25 @@ class SIRT(object):
     def _forward(self):
         """d_ax = A d_rec."""
         self.proj_mat.apply(self.d_rec, self.d_ax)
+
+    def _residual(self):
+        """d_res = W * (d_b - d_ax) -> ||d_b - d_ax||^2; a backend that can also notes the residual's non-empty detector planes for the
+        back-projection that follows (HipBackend.residual_scale)."""
+        be = self.be
+        if getattr(be, "notes_sinogram_planes", False):
+            return be.residual_scale(self.d_b, self.d_ax, self.d_W, self.d_res, n_proj=np.size(self._rows))
+        return be.residual_scale(self.d_b, self.d_ax, self.d_W, self.d_res)
+
+    def _backproject_update(self, positivity, last=False):
+        """rec += V * A^T d_res, clamp; returns ||gt - rec||^2 when a ground truth is given.  One pass where the backend fuses the two
+        (it declines -- nothing done -- when a pose does not take the gather adjoint), else the back-projection, then the update."""
+        be = self.be
+        if self._fuse_update and hasattr(be, "adjoint_update") and getattr(self.proj_mat, "_mask", None) is None:
+            fused, err = be.adjoint_update(self.proj_mat.poses, self.d_res, self.d_rec, self.d_V, positivity, self.d_gt)
+            if fused:
+                return err
+        self._backproject_scaled()
+        return self._update(positivity, last=last)
 
     def _update(self, positivity, last=False):
         """rec += V * d_bp, clamp; returns ||gt - rec||^2 when a ground truth is given."""

@@ -85,6 +85,7 @@ class SlabPipeline(object):
 
 
 class SIRT(SlabPipeline, _SIRT):
+    _fuse_update = False      # the back-projection is summed over the ranks before the update: the two stay apart
 
     def __init__(self, comm, geometry, projections, angles, xyz_shifts, options={}):
         self.comm = comm
