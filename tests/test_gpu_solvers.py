@@ -180,7 +180,9 @@ def test_vector_kernels_phantom_timer_profile():
     assert np.array_equal(dc.download(), a - b)
     be.axpy(dc, da, 0.5)
     assert np.allclose(dc.download(), (a - b) + np.float32(0.5) * a, rtol=1e-6, atol=1e-6)
+    axpy_out = dc.download()
     be.xpay(dc, db, 2.0)
+    assert np.allclose(dc.download(), b + np.float32(2.0) * axpy_out, rtol=1e-6, atol=1e-6)
     w = a.copy()
     w[::7] = 0.0
     dw = be.upload(w)

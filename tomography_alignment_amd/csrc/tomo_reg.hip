@@ -30,8 +30,17 @@ extern "C" int tomo_vec_soft_threshold(tomo_ctx *ctx, float *d_out, const float 
     return TOMO_OK;
 }
 
+// a float32 product the backend cannot fuse with the add that follows (the build's -ffp-contract=fast reaches the backend, and
+// __fmul_rn is a plain product in this compiler's headers): the empty asm pins the rounded product, as csrc/tomo_f2py.hip does
+__device__ __forceinline__ float reg_mul(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
+
 // ------------------------------------------------------------------------------------------------
 // TV-FISTA.  Volume [nx][ny][nz], z fastest.  Grid: (z chunks of 256, ny, nx).
+// The kernels apply the reference's float32 operations in the reference's order, every product rounded on its own (reg_mul; the
+// adds and subtractions are __fadd_rn / __fsub_rn, which have no product left to fuse with): the only fused float32 operations are the
+// refinement steps inside the IEEE division; the square root is one v_sqrt_f32, good to a unit in the last place.  A float32 numpy
+// model of the iteration (tests/tv_model.py) is therefore met bit for bit wherever the projection on the unit ball divides by 1, and
+// to the last place of the square root elsewhere.
 // ------------------------------------------------------------------------------------------------
 struct TvDims { int nx, ny, nz; int64_t sy, sx; };
 
@@ -57,7 +66,7 @@ __global__ __launch_bounds__(256) void k_tv_error(const float *__restrict__ ax, 
     const int iz = blockIdx.x * 256 + threadIdx.x, iy = blockIdx.y, ix = blockIdx.z;
     if (iz >= d.nz) return;
     const int64_t i = (int64_t)ix * d.sx + (int64_t)iy * d.sy + iz;
-    err[i] = __fsub_rn(__fmul_rn(weight, tv_div_at(ax, ay, az, i, ix, iy, iz, d)), im[i]);
+    err[i] = __fsub_rn(reg_mul(weight, tv_div_at(ax, ay, az, i, ix, iy, iz, d)), im[i]);
 }
 
 // grad_tmp = gradient(err) / (factor * weight); grad_aux += grad_tmp; project on the unit ball; FISTA combination
@@ -73,12 +82,12 @@ __global__ __launch_bounds__(256) void k_tv_update(float *__restrict__ ax, float
     const float gx = ix < d.nx - 1 ? __fsub_rn(err[i + d.sx], e0) : 0.f;      // forward differences, 0 at the last index of an axis
     const float gy = iy < d.ny - 1 ? __fsub_rn(err[i + d.sy], e0) : 0.f;
     const float gz = iz < d.nz - 1 ? __fsub_rn(err[i + 1], e0) : 0.f;
-    const float a0 = __fadd_rn(ax[i], __fmul_rn(gx, c)), a1 = __fadd_rn(ay[i], __fmul_rn(gy, c)), a2 = __fadd_rn(az[i], __fmul_rn(gz, c));
-    const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(a0, a0), __fmul_rn(a1, a1)), __fmul_rn(a2, a2))), 1.f);
+    const float a0 = __fadd_rn(ax[i], reg_mul(gx, c)), a1 = __fadd_rn(ay[i], reg_mul(gy, c)), a2 = __fadd_rn(az[i], reg_mul(gz, c));
+    const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(reg_mul(a0, a0), reg_mul(a1, a1)), reg_mul(a2, a2))), 1.f);
     const float p0 = __fdiv_rn(a0, nrm), p1 = __fdiv_rn(a1, nrm), p2 = __fdiv_rn(a2, nrm);
-    ax[i] = __fsub_rn(__fmul_rn(one_tf, p0), __fmul_rn(tf, px[i]));             // (1 + t_factor) * grad_tmp - t_factor * grad_im   :158
-    ay[i] = __fsub_rn(__fmul_rn(one_tf, p1), __fmul_rn(tf, py[i]));
-    az[i] = __fsub_rn(__fmul_rn(one_tf, p2), __fmul_rn(tf, pz[i]));
+    ax[i] = __fsub_rn(reg_mul(one_tf, p0), reg_mul(tf, px[i]));                // (1 + t_factor) * grad_tmp - t_factor * grad_im   :158
+    ay[i] = __fsub_rn(reg_mul(one_tf, p1), reg_mul(tf, py[i]));
+    az[i] = __fsub_rn(reg_mul(one_tf, p2), reg_mul(tf, pz[i]));
     px[i] = p0; py[i] = p1; pz[i] = p2;                                            // grad_im = grad_tmp                               :159
 }
 
@@ -101,7 +110,7 @@ __global__ __launch_bounds__(256) void k_tv_new(const float *__restrict__ px, co
     double s_gap = 0.0, s_new = 0.0, s_im = 0.0;
     if (iz < d.nz) {
         const int64_t i = (int64_t)ix * d.sx + (int64_t)iy * d.sy + iz;
-        const float gap = __fmul_rn(weight, tv_div_at(px, py, pz, i, ix, iy, iz, d));
+        const float gap = reg_mul(weight, tv_div_at(px, py, pz, i, ix, iy, iz, d));
         const float v = im[i], nw = __fsub_rn(v, gap);
         out[i] = nw;
         s_gap = (double)gap * gap; s_new = (double)nw * nw; s_im = (double)v * v;
@@ -122,7 +131,7 @@ __global__ __launch_bounds__(256) void k_tv_norm(const float *__restrict__ x, Tv
         const int64_t i = (int64_t)ix * d.sx + (int64_t)iy * d.sy + iz;
         const float v = x[i];
         const float gx = ix < d.nx - 1 ? x[i + d.sx] - v : 0.f, gy = iy < d.ny - 1 ? x[i + d.sy] - v : 0.f, gz = iz < d.nz - 1 ? x[i + 1] - v : 0.f;
-        const float q = __fadd_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)), __fmul_rn(gz, gz));
+        const float q = __fadd_rn(__fadd_rn(reg_mul(gx, gx), reg_mul(gy, gy)), reg_mul(gz, gz));
         s = ISO ? (double)__fsqrt_rn(q) : (double)q;
     }
     tv_block_sum(s, red);
@@ -206,8 +215,8 @@ extern "C" int tomo_tv_denoise_fista(tomo_ctx *ctx, const float *d_im, float *d_
 // ------------------------------------------------------------------------------------------------
 // The regularised solvers' per-iteration vector work (recon/regularized.py RegularizedRecon; include/tomo.h lists the reference lines
 // each entry point restates).  Every kernel is ONE streaming pass over float32 volumes that also produces the iteration's scalars:
-//   - elementwise float arithmetic in the reference's operation order, every product rounded on its own (reg_mul), so no contraction
-//     into an FMA changes a bit against numpy float32 (the build has -ffp-contract=fast);
+//   - elementwise float arithmetic in the reference's operation order, every product rounded on its own (reg_mul, above the TV
+//     section), so no contraction into an FMA changes a bit against numpy float32 (the build has -ffp-contract=fast);
 //   - 16-byte loads / stores on the body when every operand has the same offset from a 16-byte boundary (a scalar head and tail take
 //     the rest; operands of mixed offsets take the scalar loop throughout);
 //   - the scalars are summed in float64 DETERMINISTICALLY: a fixed grid (it depends on n only, never on the device) in which every
@@ -219,9 +228,6 @@ extern "C" int tomo_tv_denoise_fista(tomo_ctx *ctx, const float *d_im, float *d_
 #define REG_MAX_GRID 2048
 #define REG_MAX_NS 3
 
-// a float32 product the backend cannot fuse with the add that follows (the build's -ffp-contract=fast reaches the backend, and
-// __fmul_rn is a plain product in this compiler's headers): the empty asm pins the rounded product, as csrc/tomo_f2py.hip does
-__device__ __forceinline__ float reg_mul(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
 __device__ __forceinline__ float reg_soft(float y, float l) { return y > l ? __fsub_rn(y, l) : (y < -l ? __fadd_rn(y, l) : 0.f); }
 __device__ __forceinline__ double reg_sq(float v) { return (double)v * (double)v; }
 
@@ -533,7 +539,7 @@ __global__ __launch_bounds__(REG_BLOCK) void k_tv_gap_det(const float *__restric
     const int64_t n = (int64_t)d.nx * d.sx, stride = (int64_t)gridDim.x * REG_BLOCK;
     for (int64_t i = (int64_t)blockIdx.x * REG_BLOCK + threadIdx.x; i < n; i += stride) {
         const int ix = (int)(i / d.sx), iy = (int)((i - (int64_t)ix * d.sx) / d.sy), iz = (int)(i - (int64_t)ix * d.sx - (int64_t)iy * d.sy);
-        const float gap = __fmul_rn(weight, tv_div_at(px, py, pz, i, ix, iy, iz, d));
+        const float gap = reg_mul(weight, tv_div_at(px, py, pz, i, ix, iy, iz, d));
         const float v = im[i], nw = __fsub_rn(v, gap);
         out[i] = nw;
         s[0] += (double)gap * gap; s[1] += (double)nw * nw; s[2] += (double)v * v;
@@ -549,7 +555,7 @@ __global__ __launch_bounds__(REG_BLOCK) void k_tv_iso_det(const float *__restric
         const int ix = (int)(i / d.sx), iy = (int)((i - (int64_t)ix * d.sx) / d.sy), iz = (int)(i - (int64_t)ix * d.sx - (int64_t)iy * d.sy);
         const float v = x[i];
         const float gx = ix < d.nx - 1 ? x[i + d.sx] - v : 0.f, gy = iy < d.ny - 1 ? x[i + d.sy] - v : 0.f, gz = iz < d.nz - 1 ? x[i + 1] - v : 0.f;
-        s[0] += (double)__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)), __fmul_rn(gz, gz)));
+        s[0] += (double)__fsqrt_rn(__fadd_rn(__fadd_rn(reg_mul(gx, gx), reg_mul(gy, gy)), reg_mul(gz, gz)));
     }
     reg_block_partials<1>(s, part);
 }
