@@ -1,0 +1,375 @@
+"""The consistency pre-alignment without a GPU: the estimator of align/consistency.py against the model of tests/mom_model.py on the same
+marginals, exact recovery of the shifts of analytic series, the CPU oracle's Shepp-Logan data at +-2 and +-10 px of jitter, the sign of
+axis_offset, the argument checks, that the data generator and the driver are what they were without the new options, and the binding of
+libtomo_mom.so (the assertions of tests/test_binding.py, for _mom_lib).  The marginals themselves are the GPU's business
+(tests/test_gpu_consistency.py); here they come from the model."""
+import ctypes
+import inspect
+
+import numpy as np
+import pytest
+
+import mom_model as mm
+
+from tomography_alignment_amd import _binding, _lib, _mom_lib, rotation_axis
+from tomography_alignment_amd.align import consistency
+from tomography_alignment_amd.examples import align_rigid, generate_data, preprocess
+
+NX = NZ = 160          # the analytic series: +-20 px of shift, centres within 8 px of the axis and 9 sigma of tail stay on 160 pixels
+N = 40
+
+
+def _series(seed, shift=20.0, axis_offset=0.0, gauge_free=False):
+    rng = np.random.default_rng(seed)
+    phi = np.arange(N) * np.pi / N
+    xyz = np.zeros((N, 3))
+    xyz[:, 0], xyz[:, 2] = rng.uniform(-shift, shift, N), rng.uniform(-shift, shift, N)
+    if gauge_free:
+        xyz = mm.gauge_fix(xyz, phi)
+    p = mm.ellipsoid_series(NX, NZ, phi, xyz, axis_offset=axis_offset)
+    return phi, xyz, consistency.moments(p.sum(axis=2), p.sum(axis=1))
+
+
+@pytest.fixture(scope="module")
+def oracle_data():
+    """make() on the CPU oracle, once: (48, 60, +-2 px) and (64, 90, +-10 px), seed 3, with the model's marginals."""
+    mp = pytest.MonkeyPatch()
+    mp.setattr(generate_data.projection_operators, "ProjectionMatrix", mm.OracleProjector)
+    try:
+        out = {}
+        for size, n, s in ((48, 60, 2.0), (64, 90, 10.0)):
+            d = generate_data.make(size, n, seed=3, shift_px=s)
+            out[s] = (d, consistency.moments(*mm.marginals(d["projections"])))
+    finally:
+        mp.undo()
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ module against model
+
+@pytest.mark.parametrize("vertical", ["moment", "profile"])
+def test_the_module_is_the_model_on_the_same_marginals(vertical):
+    phi, _, m = _series(1)
+    got = consistency.shifts_from_marginals(m, phi, vertical=vertical)
+    ref = mm.estimate(m.Q, m.Z, phi, vertical=vertical)
+    mass, cx, cz = mm.moments(m.Q, m.Z)
+    worst = max(float(np.max(np.abs(got.xyz0 - ref["xyz0"]))), abs(got.axis_offset - ref["axis_offset"]), float(np.max(np.abs(np.array(got.fit) - ref["fit"]))),
+                abs(got.mass_spread - ref["mass_spread"]), abs(got.residual_rms - ref["residual_rms"]), float(np.max(np.abs(m.cx - cx))),
+                float(np.max(np.abs(m.cz - cz))), float(np.max(np.abs(m.mass / mass - 1))))
+    print("%s: largest difference between module and model %.2e" % (vertical, worst))
+    assert worst <= 1e-12 and got.vertical == vertical and got.marginals is None and not got.xyz0[:, 1].any()
+    s = np.random.default_rng(2).uniform(-5, 5, (N, 3))
+    assert np.max(np.abs(consistency.gauge_fix(s, phi) - mm.gauge_fix(s, phi))) <= 1e-12
+    assert np.max(np.abs(consistency.gauge_fix(s[:, [0, 2]], phi) - mm.gauge_fix(s, phi)[:, [0, 2]])) <= 1e-12
+    assert np.array_equal(consistency.gauge_fix(s, phi)[:, 1], s[:, 1])
+    assert consistency.shifts_from_marginals(m, phi, vertical=vertical, return_marginals=True).marginals is m
+
+
+def test_gauge_fix_removes_exactly_what_the_law_absorbs():
+    phi = np.linspace(0.2, 3.0, N)
+    rng = np.random.default_rng(3)
+    s = rng.uniform(-5, 5, (N, 3))
+    absorbed = np.zeros((N, 3))
+    absorbed[:, 0] = 7.0 - 3.0 * np.cos(phi) + 11.0 * np.sin(phi)
+    absorbed[:, 2] = -4.0
+    a, b = consistency.gauge_fix(s, phi), consistency.gauge_fix(s + absorbed, phi)
+    assert np.max(np.abs(a - b)) <= 1e-12
+    assert np.max(np.abs(consistency.gauge_fix(a, phi) - a)) <= 1e-12                       # a projection
+    assert np.max(np.abs(consistency.design(phi).T.dot(a[:, 0]))) <= 1e-10 and abs(a[:, 2].mean()) <= 1e-13
+    with pytest.raises(ValueError):
+        consistency.gauge_fix(np.zeros((N, 4)), phi)
+
+
+# ------------------------------------------------------------------------------------------------------------------ exact recovery
+
+@pytest.mark.parametrize("seed", [4, 5])
+def test_analytic_series_give_their_shifts_back(seed):
+    phi, xyz, m = _series(seed)
+    spread = m.mass.max() / m.mass.min() - 1
+    truth = mm.gauge_fix(xyz, phi)
+    mom = consistency.shifts_from_marginals(m, phi, vertical="moment")
+    pro = consistency.shifts_from_marginals(m, phi, vertical="profile", upsample=20)
+    ex = float(np.max(np.abs(consistency.gauge_fix(mom.xyz0, phi)[:, 0] - truth[:, 0])))
+    ez = float(np.max(np.abs(consistency.gauge_fix(mom.xyz0, phi)[:, 2] - truth[:, 2])))
+    ep = float(np.max(np.abs(consistency.gauge_fix(pro.xyz0, phi)[:, 2] - truth[:, 2])))
+    print("seed %d, shifts within +-20 px: mass spread %.1e; moment x %.1e z %.1e px; profile z %.4f px (1 / upsample = 0.05)" % (seed, spread, ex, ez, ep))
+    assert np.max(np.abs(xyz)) > 15 and spread < 1e-12
+    assert ex <= 1e-9 and ez <= 1e-9
+    assert ep <= 1.0 / 20
+    assert np.array_equal(pro.xyz0[:, 0], mom.xyz0[:, 0])                                   # the horizontal fit is the same in both modes
+    assert np.max(np.abs(consistency.gauge_fix(mom.xyz0, phi) - mom.xyz0)) <= 1e-9           # the estimate is gauge-fixed as returned
+
+
+def test_the_fit_is_the_closed_form_law_and_axis_offset_has_find_centers_sign():
+    for off in (0.0, 2.5, -6.25):
+        phi, xyz, m = _series(6, axis_offset=off, gauge_free=True)
+        est = consistency.shifts_from_marginals(m, phi)
+        law = mm.ellipsoid_law(NX, axis_offset=off)
+        print("axis %+.2f px from the centre: fit %s, law %s, axis_offset %.12f" % (off, est.fit, law, est.axis_offset))
+        assert np.max(np.abs(np.array(est.fit) - law)) <= 1e-9 and abs(est.axis_offset - off) <= 1e-9
+        assert abs(est.residual_rms - np.sqrt(np.mean(xyz[:, 0] ** 2))) <= 1e-9
+
+
+def test_axis_offset_follows_cor_offset(monkeypatch):
+    """cor_shift = [D, 0, 0] puts the axis at the column (nx - 1) / 2 - D, which find_center reports as offset = -D
+    (rotation_axis, Sign).  No jitter: any constant part of it would go into c0."""
+    monkeypatch.setattr(generate_data.projection_operators, "ProjectionMatrix", mm.OracleProjector)
+    offs = {}
+    for D in (0.0, 3.0, -4.5):
+        d = generate_data.make(32, 24, seed=1, shift_px=0.0, ang_deg=0.0, cor_offset=D)
+        assert not d["xyz"].any()
+        offs[D] = consistency.shifts_from_marginals(consistency.moments(*mm.marginals(d["projections"])), d["phi"]).axis_offset
+    print("axis_offset for cor_offset 0, 3, -4.5: %s" % [round(v, 4) for v in offs.values()])
+    for D in (3.0, -4.5):
+        assert abs((offs[D] - offs[0.0]) - float(rotation_axis.to_cor_shift(D, 1)[0, 0])) <= 0.1
+
+
+# --------------------------------------------------------------------------------------------------------------------- oracle data
+
+def _errors(d, est):
+    g = consistency.gauge_fix(est.xyz0, d["phi"]) - consistency.gauge_fix(d["xyz"], d["phi"])
+    return np.abs(g[:, 0]), np.abs(g[:, 2])
+
+
+def test_oracle_data_with_2_px_of_jitter(oracle_data):
+    d, m = oracle_data[2.0]
+    est = consistency.shifts_from_marginals(m, d["phi"])
+    ex, ez = _errors(d, est)
+    print("48^3 x 60, +-2 px: x error mean %.3f max %.3f px, z error mean %.3f max %.3f px, mass spread %.2f %%"
+          % (ex.mean(), ex.max(), ez.mean(), ez.max(), 100 * est.mass_spread))
+    assert ex.max() < 0.1 and ez.max() < 0.1
+    assert np.max(np.abs(est.xyz0[:, [0, 2]])) > 1.0 and not est.xyz0[:, 1].any()
+
+
+def test_oracle_data_with_10_px_of_jitter_lands_inside_the_fine_alignments_bounds(oracle_data):
+    d, m = oracle_data[10.0]
+    est = consistency.shifts_from_marginals(m, d["phi"])
+    ex, ez = _errors(d, est)
+    print("64^3 x 90, +-10 px: x error mean %.3f max %.3f px, z error mean %.3f max %.3f px, mass spread %.2f %%"
+          % (ex.mean(), ex.max(), ez.mean(), ez.max(), 100 * est.mass_spread))
+    bound = align_rigid.DEFAULT_BOUNDS[0][1]
+    assert bound == 3.0 and ex.max() < bound and ez.max() < bound
+    assert est.mass_spread > 0.01                                     # the phantom leaves the detector, and the order-0 condition says so
+    assert align_rigid.gauge_shift_error(est.xyz0, d["xyz"], d["phi"]) == pytest.approx(0.5 * (ex.mean() + ez.mean()), abs=1e-12)
+
+
+# ----------------------------------------------------------------------------------------------------------------- argument errors
+
+def test_argument_errors_need_no_device():
+    p = np.zeros((8, 16, 12), np.float32)
+    phi = np.linspace(0, np.pi, 8)
+    with pytest.raises(ValueError, match="n >= 4"):
+        consistency.estimate_shifts(p[:3], phi[:3])
+    with pytest.raises(ValueError, match="7 angles for 8"):
+        consistency.estimate_shifts(p, phi[:7])
+    with pytest.raises(ValueError, match="ill-conditioned"):
+        consistency.estimate_shifts(p, np.linspace(0, 1.5, 8))
+    with pytest.raises(ValueError, match="vertical"):
+        consistency.estimate_shifts(p, phi, vertical="centroid")
+    with pytest.raises(ValueError, match="upsample"):
+        consistency.estimate_shifts(p, phi, vertical="profile", upsample=0)
+    with pytest.raises(ValueError, match="max_lag"):
+        consistency.estimate_shifts(p, phi, vertical="profile", max_lag=12)
+    with pytest.raises(ValueError, match=r"\(n, nx, nz\)"):
+        consistency.estimate_shifts(p[0], phi)
+    with pytest.raises(ValueError, match="zrange"):
+        consistency.marginals(p, zrange=3)
+    with pytest.raises(ValueError, match="NaN"):
+        consistency.marginals(p, floor=float("nan"))
+    for zr in ((-1, 5), (5, 5), (0, 13)):
+        with pytest.raises(consistency.MomUnsupported):
+            consistency.marginals(p, zrange=zr)
+    with pytest.raises(consistency.MomUnsupported):
+        consistency.marginals(np.zeros((1, 1, _mom_lib.MAX_NZ + 1), np.float32))
+    # after the pass: non-finite values and empty projections
+    Q, Z = np.ones((8, 16)), np.ones((8, 12)) * 16 / 12
+    bad = np.zeros(8, np.int32)
+    bad[3] = 2
+    with pytest.raises(ValueError, match="non-finite"):
+        consistency.shifts_from_marginals(consistency.moments(Q, Z, bad), phi)
+    assert consistency.shifts_from_marginals(consistency.moments(Q, Z, bad), phi, allow_bad=True).xyz0.shape == (8, 3)
+    Q0 = Q.copy()
+    Q0[5] = 0.0
+    with pytest.raises(ValueError, match="mass <= 0"):
+        consistency.shifts_from_marginals(consistency.moments(Q0, Z), phi)
+    # the drivers
+    data = dict(projections=p, phi=phi)
+    with pytest.raises(ValueError, match="communicator"):
+        align_rigid.resolve_prealign(data, "moment", comm=object())
+    with pytest.raises(ValueError, match="prealign"):
+        align_rigid.resolve_prealign(data, "centroid")
+    with pytest.raises(ValueError, match=r"\(8, 3\)"):
+        align_rigid.resolve_prealign(data, np.zeros((7, 3)))
+    with pytest.raises(ValueError, match="prealign"):
+        align_rigid.resolve_prealign(data, np.full((8, 3), np.nan))
+    xyz0 = np.arange(24.0).reshape(8, 3)
+    assert np.array_equal(align_rigid.resolve_prealign(data, xyz0, comm=object()), xyz0) and align_rigid.resolve_prealign(data, None) is None
+    with pytest.raises(ValueError, match="prealign"):
+        preprocess.run(dict(counts=p, flats=p, darks=p, phi=phi), prealign="centroid")
+    with pytest.raises(ValueError, match="phi"):
+        preprocess.run(dict(counts=p, flats=p, darks=p), prealign="moment")
+    with pytest.raises(ValueError, match="ill-conditioned"):
+        preprocess.run(dict(counts=p, flats=p, darks=p, phi=np.linspace(0, 1, 8)), prealign="moment")
+    assert preprocess.parse_args(["x.npz"]).prealign is None and preprocess.parse_args(["x.npz", "--prealign"]).prealign == "moment"
+    assert preprocess.parse_args(["x.npz", "--prealign", "profile"]).prealign == "profile"
+
+
+# ------------------------------------------------------------------------------------------------------------------ unchanged data
+
+def test_generate_data_with_default_jitter_is_what_it_was(monkeypatch):
+    monkeypatch.setattr(generate_data.projection_operators, "ProjectionMatrix", mm.OracleProjector)
+    sig = inspect.signature(generate_data.make).parameters
+    a = generate_data.parse_args([])
+    assert a.shift_px == sig["shift_px"].default == 2.0 and a.tilt_deg == sig["ang_deg"].default == 1.0
+    b = generate_data.parse_args(["--shift-px", "10", "--tilt-deg", "0.5"])
+    assert b.shift_px == 10.0 and b.tilt_deg == 0.5
+    plain = generate_data.make(16, 12, seed=1)
+    flags = generate_data.make(16, 12, seed=1, ang_deg=a.tilt_deg, shift_px=a.shift_px)          # what main() passes for no flags
+    assert sorted(plain) == sorted(flags)
+    for k in plain:
+        assert np.array_equal(np.asarray(plain[k]), np.asarray(flags[k])), k
+    # the poses are the draws they always were: four randint(-m, m) / 100 from RandomState(seed), in the order alpha, beta, x, z
+    rng = np.random.RandomState(1)
+    draws = [rng.randint(-m, m, 12) / 100 for m in (100, 100, 200, 200)]
+    assert np.array_equal(plain["alpha"], np.deg2rad(draws[0])) and np.array_equal(plain["beta"], np.deg2rad(draws[1]))
+    assert np.array_equal(plain["xyz"][:, 0], draws[2]) and np.array_equal(plain["xyz"][:, 2], draws[3]) and not plain["xyz"][:, 1].any()
+    wide = generate_data.make(16, 12, seed=1, shift_px=b.shift_px, ang_deg=b.tilt_deg)
+    assert np.max(np.abs(wide["xyz"])) > 2.0 and np.max(np.abs(wide["xyz"])) <= 10.0 and np.max(np.abs(np.rad2deg(wide["alpha"]))) <= 0.5
+
+
+class _Stop(Exception):
+    pass
+
+
+class _RecordingLoop(object):
+    calls = []
+
+    def __init__(self, data, **kw):
+        type(self).calls.append(kw)
+        raise _Stop()
+
+
+class _FakeBackend(object):
+    def upload(self, a):
+        return a
+
+    def is_buffer(self, a):
+        return False
+
+
+class _FakePyramid(object):
+    def bin_projections(self, d, f, shape=None):
+        return d
+
+    def bin_volume(self, d, f, shape=None):
+        return d
+
+
+def test_run_without_prealign_builds_the_loop_it_always_built(monkeypatch):
+    monkeypatch.setattr(align_rigid, "OuterLoop", _RecordingLoop)
+    _RecordingLoop.calls = []
+    n = 8
+    data = dict(projections=np.zeros((n, 16, 16), np.float32), phi=np.linspace(0, np.pi, n))
+    xyz0 = np.random.default_rng(0).uniform(-8, 8, (n, 3))
+    for kw in (dict(), dict(prealign=None), dict(prealign=xyz0)):
+        with pytest.raises(_Stop):
+            align_rigid.run(data, n_outer=1, verbose=False, **kw)
+    plain, none, given = _RecordingLoop.calls
+    assert plain == none == dict(backend=None, comm=None, kernel_names=None, cor=None)      # no `base` at all: the call of before
+    assert none.get("base") is None
+    base = given.pop("base")
+    assert given == plain
+    assert np.array_equal(base[0], xyz0) and base[0] is not xyz0 and not base[1].any() and not base[2].any() and base[1].shape == (n,)
+    # coarse to fine: the coarsest level's base is the start divided by that level's factor
+    _RecordingLoop.calls = []
+    for kw in (dict(), dict(prealign=xyz0)):
+        with pytest.raises(_Stop):
+            align_rigid.run_multires(data, levels=3, n_outer=1, verbose=False, backend_factory=lambda g: _FakeBackend(), pyramid=_FakePyramid(), **kw)
+    plain, given = _RecordingLoop.calls
+    assert plain["base"] is None and plain["factor"] == 4
+    assert given["factor"] == 4 and np.array_equal(given["base"][0], xyz0 / 4.0) and not given["base"][1].any() and not given["base"][2].any()
+    assert {k: v for k, v in given.items() if k not in ("base", "backend")} == {k: v for k, v in plain.items() if k not in ("base", "backend")}
+
+
+def test_pose_errors_report_the_gauge_fixed_error_beside_the_plain_one():
+    phi = np.linspace(0, np.pi, 12)
+    rng = np.random.default_rng(1)
+    truth = rng.uniform(-2, 2, (12, 3))
+    absorbed = np.zeros((12, 3))
+    absorbed[:, 0], absorbed[:, 2] = 5.0 + 2.0 * np.cos(phi) - np.sin(phi), 1.5
+    assert align_rigid.gauge_shift_error(truth + absorbed, truth, phi) <= 1e-12
+    assert align_rigid.gauge_shift_error(truth[:, [0, 2]], truth, phi) <= 1e-12
+    loop = align_rigid.OuterLoop.__new__(align_rigid.OuterLoop)
+    loop.data, loop.phi, loop.factor = dict(xyz=truth, alpha=np.zeros(12), beta=np.zeros(12)), phi, 2
+    loop.xyz_rec, loop.alpha_rec, loop.beta_rec = 0.5 * (truth + absorbed), np.zeros(12), np.zeros(12)
+    e = loop.pose_errors()
+    assert sorted(e) == ["shift_err_gauge_px", "shift_err_px", "tilt_err_deg"]
+    assert e["shift_err_gauge_px"] <= 1e-12 and e["shift_err_px"] == pytest.approx(float(np.abs(absorbed[:, [0, 2]]).mean()))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the binding
+
+def test_load_binds_the_whole_table_once():
+    lib = _mom_lib.load()
+    assert _mom_lib.load() is lib
+    assert _mom_lib.SIGNATURES
+    for sym, (res, args) in _mom_lib.SIGNATURES.items():
+        assert sym.startswith("tomo_mom_"), sym
+        fn = getattr(lib, sym)
+        assert fn.restype is res and list(fn.argtypes) == list(args), sym
+
+
+def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
+    _mom_lib.load()
+    missing = str(tmp_path / "libtomo_mom.so")
+    monkeypatch.setattr(_mom_lib, "LIB_PATH", missing)
+    monkeypatch.delitem(_binding._loaded, "mom")
+    with pytest.raises(_lib.TomoError) as e:
+        _mom_lib.load()
+    text = str(e.value)
+    assert "libtomo_mom.so not built" in text and missing in text
+    assert "`make -C tomography_alignment_amd/csrc/mom`" in text
+    assert "mom" not in _binding._loaded
+    monkeypatch.undo()
+    assert _mom_lib.load() is _binding._loaded["mom"]
+
+
+def test_handle_less_calls_raise_in_the_common_format():
+    assert issubclass(_mom_lib.MomUnsupported, _lib.TomoError) and consistency.MomUnsupported is _mom_lib.MomUnsupported
+    for n, nx, nz, z0, z1 in ((0, 8, 8, 0, 8), (1, 0, 8, 0, 8), (1, 8, 0, 0, 0), (1, 8, 16385, 0, 8), (1, 8, 8, -1, 8), (1, 8, 8, 4, 4), (1, 8, 8, 0, 9)):
+        with pytest.raises(_mom_lib.MomUnsupported, match=r"^libtomo_mom error 4: tomo_mom"):
+            _mom_lib.check_shape(n, nx, nz, z0, z1)
+    _mom_lib.check_shape(1, 1, 1)
+    _mom_lib.check_shape(4096, 4096, 16384, 16383, 16384)
+    with pytest.raises(_mom_lib.MomUnsupported):
+        _mom_lib.batch(0, 64, 64)
+    with pytest.raises(_mom_lib.MomUnsupported):
+        _mom_lib.scratch_bytes(64, 16385)
+
+
+def test_no_device_means_no_handle():
+    n = ctypes.c_int(0)
+    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
+        pytest.skip("a GPU is present")
+    h = _mom_lib.MomHandle.__new__(_mom_lib.MomHandle)
+    with pytest.raises(_lib.TomoError):
+        h.__init__(0)
+    assert h._h is None
+    h.close()
+    h.close()
+    with pytest.raises(_lib.TomoError, match="mom handle closed"):
+        h.handle
+
+
+def test_batches_follow_the_budget():
+    """Per projection: a float64 partial of Z per tile of 128 columns (per half / quarter tile where nz <= 512 / 256), one of Q per
+    chunk of 1024 rows, an int per (tile, chunk)."""
+    assert (_mom_lib.TILE_X, _mom_lib.CHUNK_Z) == (128, 1024)
+    assert _mom_lib.scratch_bytes(5, 7) == 8 * 7 * 4 + 8 * 5 + 4 and _mom_lib.scratch_bytes(300, 512) == 8 * 512 * 3 * 2 + 8 * 300 + 4 * 3
+    assert _mom_lib.scratch_bytes(300, 513) == 8 * 513 * 3 + 8 * 300 + 4 * 3
+    per = 8 * 130 * 4 + 8 * 70 * 1 + 4
+    assert _mom_lib.scratch_bytes(70, 130) == per
+    assert _mom_lib.scratch_bytes(129, 2049) == 8 * 2049 * 2 + 8 * 129 * 3 + 4 * 6
+    assert _mom_lib.batch(5, 70, 130, 0) == 5 and _mom_lib.batch(5, 70, 130, 1) == 1 and _mom_lib.batch(5, 70, 130, per) == 1
+    assert _mom_lib.batch(5, 70, 130, 2 * per + 7) == 2 and _mom_lib.batch(5, 70, 130, 100 * per) == 5
+    assert _mom_lib.batch(100000, 8, 8, 0) == 65535                    # the z extent of a grid

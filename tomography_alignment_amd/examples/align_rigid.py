@@ -22,6 +22,13 @@ only.  cor is the x component of `Geometry(cor_shift=)` in full-size pixels -- a
 AUTO_COR_ROWS detector rows of the measured projections, the median offset turned into a cor_shift by rotation_axis.to_cor_shift.  The
 reconstruction, the alignment pass and the FSC's FBPs all use it; None (the default) leaves every call as it was.
 
+Pre-alignment (prealign=, --prealign): stages of nano-tomography jitter by tens of pixels, and the passes above search +-3 px around
+their start.  prealign is that start -- "moment" or "profile": align.consistency.estimate_shifts on the measured projections (shifts
+from the projections' own moments, no reconstruction); or an (n_proj, 3) array, e.g. the `xyz0` examples/preprocess --prealign stored.
+It becomes the loop's base pose (xyz0, 0, 0): every alignment pass searches an increment around it.  None (the default) leaves every
+call as it was.  Such a start is determined only up to what the consistency conditions absorb (a translation of the object and of the
+axis), so the history's `shift_err_gauge_px` compares estimate and truth after consistency.gauge_fix.
+
 Coarse to fine (run_multires, --levels): the first outer iterations run on data binned by 2^(levels-1), ..., 2 (multires.py: the
 binning and prolongation kernels of libtomo_pyr.so), each level a unit-pitch geometry of its own; the poses (translations times 2, tilts
 as they are) and the prolonged reconstruction are handed up, and only the last iterations run at full size.  The bounds of the optimiser
@@ -31,6 +38,7 @@ are in pixels of the level, so the same +-3 px reach +-12 full-size pixels at a 
     python -m tomography_alignment_amd.examples.align_rigid data.npz --levels 3 --outer 3 --sirt-iters 50
     python -m tomography_alignment_amd.examples.align_rigid measured.npz --fsc          # no phantom needed: a resolution per outer iteration
     python -m tomography_alignment_amd.examples.align_rigid measured.npz --cor auto     # find the rotation axis first (rotation_axis.py)
+    python -m tomography_alignment_amd.examples.align_rigid measured.npz --prealign moment   # start from the moments' shifts
     python -m torch.distributed.run --nproc-per-node 8 -m tomography_alignment_amd.examples.align_rigid data.npz
 """
 import argparse
@@ -39,6 +47,7 @@ import time
 import numpy as np
 
 from .. import alignment, multires, resolution, rotation_axis
+from ..align import consistency
 from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
 
@@ -170,6 +179,7 @@ class OuterLoop(object):
             return {}
         shifts = self.xyz_rec[:, [0, 2]] if self.factor == 1 else self.factor * self.xyz_rec[:, [0, 2]]
         return {"shift_err_px": float(np.abs(shifts - np.asarray(d["xyz"])[:, [0, 2]]).mean()),
+                "shift_err_gauge_px": gauge_shift_error(shifts, np.asarray(d["xyz"])[:, [0, 2]], self.phi),
                 "tilt_err_deg": float(np.rad2deg(np.abs(np.column_stack([self.alpha_rec, self.beta_rec]) - np.column_stack([d["alpha"], d["beta"]])).mean()))}
 
     def half_set_fsc(self, res=None):
@@ -181,6 +191,43 @@ class OuterLoop(object):
 
     def download(self):
         return self.be.download(self.d_rec).reshape(self.vox_shape)
+
+
+def gauge_shift_error(shifts, truth, phi):
+    """The mean |difference| of two (n, 2) or (n, 3) shift tables after consistency.gauge_fix on both: what is left once the part no
+    method can see -- x in span{1, cos phi, sin phi}, a constant z -- is taken out of estimate and truth alike."""
+    a, b = consistency.gauge_fix(shifts, phi), consistency.gauge_fix(truth, phi)
+    return float(np.abs(a[:, [0, -1]] - b[:, [0, -1]]).mean())
+
+
+def resolve_prealign(data, prealign, comm=None, ctx=None, verbose=False):
+    """The (n_proj, 3) start of the shifts that `prealign` stands for, full-size pixels: None -> None, an array -> itself (checked),
+    "moment" / "profile" -> consistency.estimate_shifts on the measured projections.  With a communicator only an array is taken: a
+    rank holds a block of the angles and the fit needs all of them; a string raises ValueError there -- estimate beforehand."""
+    if prealign is None:
+        return None
+    n = np.size(data["phi"])
+    if not isinstance(prealign, str):
+        xyz0 = np.array(prealign, np.float64)
+        if xyz0.shape != (n, 3) or not np.all(np.isfinite(xyz0)):
+            raise ValueError("align_rigid: prealign must be None, 'moment', 'profile' or a finite (n_proj, 3) = (%d, 3) array" % n)
+        return xyz0
+    if prealign not in ("moment", "profile"):
+        raise ValueError("align_rigid: prealign must be None, 'moment', 'profile' or an (n_proj, 3) array, not %r" % (prealign,))
+    if comm is not None:
+        raise ValueError("align_rigid: prealign=%r needs all projections on one GPU; with a communicator pass the (n_proj, 3) array "
+                         "(consistency.estimate_shifts beforehand)" % (prealign,))
+    proj = data["projections"]
+    shape = tuple(int(v) for v in (data["projections_shape"] if "projections_shape" in data else np.shape(proj)))
+    est = consistency.estimate_shifts(proj, np.asarray(data["phi"], np.float64), vertical=prealign, ctx=ctx, shape=shape)
+    if verbose:
+        print({"prealign": prealign, "axis_offset": est.axis_offset, "mass_spread": est.mass_spread, "residual_rms": est.residual_rms})
+    return est.xyz0
+
+
+def _base_of(xyz0, factor=1):
+    """OuterLoop's base for a start of the shifts alone, in pixels of a level binned by `factor`."""
+    return (xyz0 / float(factor), np.zeros(xyz0.shape[0]), np.zeros(xyz0.shape[0]))
 
 
 AUTO_COR_ROWS = 9      # cor="auto" searches this many detector rows, spread evenly over the central half of z, and takes the median
@@ -217,18 +264,22 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
-        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None):
+        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
     fsc            True: every history entry gains `fsc_resolution` (pixels) and `fsc_curve` (_fsc_entry); needs no phantom.
     cor            None, a number or "auto" (resolve_cor; "auto" only without a communicator): the geometry's cor_shift x.  With a
                    value every history entry carries it as `cor`; with None nothing changes.
+    prealign       None, "moment", "profile" (only without a communicator) or an (n_proj, 3) array (resolve_prealign): the loop's base
+                   pose is (xyz0, 0, 0); with None the loop is built as before.
     kernel_names   with a HIP context: the history carries the HIP-event kernel time of each half of each outer iteration for these names.
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
     cor = resolve_cor(data, cor, comm, getattr(backend, "ctx", None), verbose)
-    loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names, cor=cor)
+    xyz0 = resolve_prealign(data, prealign, comm, getattr(backend, "ctx", None), verbose)
+    start = {} if xyz0 is None else {"base": _base_of(xyz0)}
+    loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names, cor=cor, **start)
     history = []
     res = resolution.Resolution(loop.ctx) if fsc else None
     try:
@@ -294,7 +345,7 @@ def _per_level(value, levels, name):
 
 def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, align_kwargs=None, comm=None,
                  kernel_names=None, download=True, return_loop=False, init="zero", ctx=None, backend_factory=None, pyramid=None, fsc=False,
-                 cor=None):
+                 cor=None, prealign=None):
     """`run` coarse to fine (module docstring): levels binned by 2^(levels-1), ..., 2, 1, coarsest first.
     n_outer, sirt_iters   one number, or one per level, coarsest first.
     bounds                of the increment every pass searches around the pose carried up from the coarser level (zero at the coarsest),
@@ -302,6 +353,8 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
     init                  the start of the coarsest level's first SIRT; every finer level starts from the prolonged coarser reconstruction.
     fsc                   as in `run`; `fsc_resolution` is in full-size pixels at every level.
     cor                   as in `run`, in full-size pixels (found on the full-size data); a level binned by f projects with cor / f.
+    prealign              as in `run`, in full-size pixels (estimated on the full-size data); the coarsest level's base pose is it divided
+                          by that level's factor, and every finer level starts from the coarser level's estimate as before.
     ctx                   the _lib.Context all levels share (default: the communicator's, or a new one).
     backend_factory, pyramid   test seams: geometry -> backend (default a HipBackend on ctx per level), and the object with multires.Pyramid's
                           three methods (default a Pyramid on ctx).
@@ -318,7 +371,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
     n_outer, sirt_iters = _per_level(n_outer, levels, "n_outer"), _per_level(sirt_iters, levels, "sirt_iters")
     if levels == 1:
         out = run(data, n_outer[0], sirt_iters[0], bounds=bounds, verbose=verbose, align_kwargs=align_kwargs, comm=comm,
-                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init, fsc=fsc, cor=cor)
+                  kernel_names=kernel_names, download=download, return_loop=return_loop, init=init, fsc=fsc, cor=cor, prealign=prealign)
         for entry in out[4]:
             entry.update(level=0, factor=1)
         return out
@@ -347,6 +400,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
             ctx = _lib.Context()
         backend_factory = lambda g: HipBackend(g, ctx=ctx)      # noqa: E731
     cor = resolve_cor(data, cor, comm, ctx, verbose)
+    xyz0 = resolve_prealign(data, prealign, comm, ctx, verbose)
     own_pyramid = pyramid is None
     if own_pyramid:
         pyramid = multires.Pyramid(ctx)
@@ -359,7 +413,7 @@ def run_multires(data, levels=3, n_outer=(3, 3, 2), sirt_iters=50, bounds=DEFAUL
         d_gt = None
         if ground_truth is not None:
             d_gt = ground_truth if be.is_buffer(ground_truth) else be.upload(np.asarray(ground_truth, np.float32).ravel())
-        history, carried, d_rec, loop = [], None, None, None
+        history, carried, d_rec, loop = [], None if xyz0 is None else _base_of(xyz0, f_max), None, None
         for level in range(levels):
             f = 2 ** (levels - 1 - level)
             shape = (nx // f, ny // f, nz // f)
@@ -427,17 +481,25 @@ def main():
                     "iteration (needs no phantom)")
     ap.add_argument("--cor", default=None, metavar="D|auto", help="the rotation axis as Geometry's cor_shift x in pixels, or 'auto' to find it "
                     "from the sinograms first (rotation_axis.find_center; one GPU)")
+    ap.add_argument("--prealign", default=None, metavar="moment|profile|file", help="start the shifts from the projections' moments "
+                    "(align.consistency; one GPU), or from the key xyz0 of the data file itself with 'file' (preprocess --prealign)")
     a = ap.parse_args()
     cor = a.cor if a.cor in (None, "auto") else float(a.cor)
+    if a.prealign not in (None, "moment", "profile", "file"):
+        ap.error("--prealign must be moment, profile or file")
     import os
     comm = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:       # launched one process per GPU: python -m torch.distributed.run --nproc-per-node N -m ...
         from ..comm import RcclComm
         comm = RcclComm.from_env()
+    data = dict(np.load(a.data))
+    if a.prealign == "file" and "xyz0" not in data:
+        ap.error("--prealign file: %s holds no xyz0 (write it with examples/preprocess --prealign)" % a.data)
+    prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
-        run(dict(np.load(a.data)), a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor)
+        run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     else:
-        run_multires(dict(np.load(a.data)), a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor)
+        run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:
         comm.close()
 

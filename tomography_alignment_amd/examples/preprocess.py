@@ -22,6 +22,10 @@ the result are exactly what they were.
 (rotation_axis.find_center on K detector rows spread over the central half of z, the median offset), and stores it as `cor_offset`: the
 x component of Geometry's cor_shift, the number align_rigid's --cor takes.  The data need `phi`, covering pi uniformly.
 
+`--prealign [moment|profile]` estimates the per-projection shifts from the moments of the finished sinogram, where it lies on the device
+(align.consistency.estimate_shifts; `profile` for samples that extend past the detector vertically), and stores `xyz0` ((n, 3), the
+number align_rigid's --prealign takes from the file), `axis_offset` and `mass_spread`.  The data need `phi`, spanning at least pi / 2.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -37,9 +41,11 @@ import argparse
 import numpy as np
 
 from .. import _lib, preprocess, rotation_axis
+from ..align import consistency
 
 RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols", "zinger_mask")
 STRIPE_MODES = ("sorting", "all", "none")
+PREALIGN_MODES = ("moment", "profile")
 LA_SIZE = 61              # the window of the dead- and large-stripe passes of --stripe all, where the detector is wide enough
 PHASE_KEYS = ("strength", "pixel_size", "dist", "energy", "wavelength", "delta_beta", "pad", "min_ratio", "max_scratch_bytes")
 
@@ -52,16 +58,23 @@ def la_size_for(nx, la_size=None):
 
 
 def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
-        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9):
+        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9, prealign=None):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
     energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
     sorting pass alone), 'all' (remove_all_stripe with snr stripe_snr, la_size -- default la_size_for(nx) -- and sm_size = stripe_size)
     or 'none'.  zinger_dif: None, or the threshold (counts) of preprocess.remove_outlier, window zinger_size, applied to the counts and to
     the flats before anything else.  find_center: True stores the rotation axis found on the finished sinogram as `cor_offset` (module
-    docstring), searched on center_rows detector rows."""
+    docstring), searched on center_rows detector rows.  prealign: None, or 'moment' / 'profile': stores consistency.estimate_shifts'
+    xyz0, axis_offset and mass_spread of the finished sinogram (module docstring)."""
     if find_center and "phi" not in data:
         raise ValueError("preprocess: find_center needs the angles `phi`")
+    if prealign is not None:
+        if prealign not in PREALIGN_MODES:
+            raise ValueError("preprocess: prealign must be None or one of %s, got %r" % (", ".join(PREALIGN_MODES), prealign))
+        if "phi" not in data:
+            raise ValueError("preprocess: prealign needs the angles `phi`")
+        consistency.check_angles(np.shape(data["counts"])[0] if "counts" in data else np.size(data["phi"]), data["phi"])
     if stripe not in STRIPE_MODES:
         raise ValueError("preprocess: stripe must be one of %s, got %r" % (", ".join(STRIPE_MODES), stripe))
     if stripe == "all" and not stripe_size:
@@ -105,6 +118,10 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
                 found = axis.find_center(sino, angles=np.asarray(data["phi"], np.float64), rows=rotation_axis.spread_rows(nz, center_rows),
                                          smin=smin, smax=smax)
             cor = float(rotation_axis.to_cor_shift(found.offset, 1)[0, 0])
+        est = None
+        if prealign is not None:
+            with consistency.Consistency(ctx) as c:
+                est = c.estimate_shifts(sino, np.asarray(data["phi"], np.float64), vertical=prealign)
         proj = sino.download()
     finally:
         for d in (d_frames, sino):
@@ -119,12 +136,16 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     out["projections"] = proj
     if cor is not None:
         out["cor_offset"] = np.float64(cor)
+    if est is not None:
+        out.update(xyz0=est.xyz0, axis_offset=np.float64(est.axis_offset), mass_spread=np.float64(est.mass_spread))
     if verbose:
         print("preprocess: %s counts -> projections %s (stripe removal %s, window %s, phase retrieval %s)"
               % (counts.shape, proj.shape, stripe, (stripe_size or "off") if stripe != "none" else "off",
                  phase if phase is not None else "off"))
         if cor is not None:
             print("preprocess: rotation axis at cor_offset %+.3f px (offsets per row %s)" % (cor, found.offsets.tolist()))
+        if est is not None:
+            print("preprocess: pre-alignment %r" % (est,))
     return out
 
 
@@ -152,6 +173,8 @@ def parse_args(argv=None):
     ap.add_argument("--zinger-size", type=int, default=3, metavar="S", help="with --zinger-dif: the median window, 3, 5 or 7")
     ap.add_argument("--find-center", action="store_true", help="find the rotation axis on the finished sinogram and store it as cor_offset")
     ap.add_argument("--center-rows", type=int, default=9, metavar="K", help="with --find-center: the detector rows searched")
+    ap.add_argument("--prealign", nargs="?", const="moment", default=None, choices=PREALIGN_MODES,
+                    help="estimate the per-projection shifts from the sinogram's moments and store them as xyz0 (with axis_offset, mass_spread)")
     a = ap.parse_args(argv)
     if a.center_rows < 1:
         ap.error("--center-rows must be >= 1")
@@ -188,7 +211,7 @@ def main(argv=None):
     a = parse_args(argv)
     d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
             stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size,
-            find_center=a.find_center, center_rows=a.center_rows)
+            find_center=a.find_center, center_rows=a.center_rows, prealign=a.prealign)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 
