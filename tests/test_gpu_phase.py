@@ -102,6 +102,21 @@ def test_scratch_budgets_give_the_same_bits(ctx, pre):
             assert np.array_equal(_bits(got), _bits(ref)), budget
 
 
+def test_a_repeated_call_finds_every_plan_in_the_cache(pre):
+    """Batch 2 of 5 frames: a plan of two and the tail's plan of one.  A wrong cache key would make them again, or grow the work area."""
+    shape = (5, 64, 48)
+    T = _frames(shape, seed=6)
+    px, pz = pm.padded_shape(shape, 400.0, None)
+    budget = 4 * 4 * px * (pz + 2)
+    assert _phase_lib.batch(5, px, pz, budget) == 2
+    first = pre.retrieve_phase(T, 400.0, max_scratch_bytes=budget)
+    seconds, held = pre._phase.plan_seconds(), pre._phase.device_bytes()
+    second = pre.retrieve_phase(T, 400.0, max_scratch_bytes=budget)
+    print("plan seconds %.6f -> %.6f, device bytes %d -> %d" % (seconds, pre._phase.plan_seconds(), held, pre._phase.device_bytes()))
+    assert seconds > 0.0 and pre._phase.plan_seconds() == seconds and pre._phase.device_bytes() == held
+    assert np.array_equal(_bits(second), _bits(first))
+
+
 def test_in_place_host_device_repeats_and_a_fresh_handle_give_the_same_bits(ctx, pre):
     shape = (4, 128, 96)
     T = _frames(shape, seed=2)

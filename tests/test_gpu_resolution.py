@@ -174,8 +174,10 @@ def test_device_residency_and_no_leaks(res, ctx):
     assert np.array_equal(d_a.download(), a) and np.array_equal(d_b.download(), b)          # the inputs are not written
     bytes_one = res.device_bytes()
     assert bytes_one >= 2 * 8 * 32 * 40 * 25
+    plan_seconds = res.handle.plan_seconds()
     res.fsc(d_a, d_b)
     assert res.device_bytes() == bytes_one                # the plan and the buffers are reused
+    assert plan_seconds > 0.0 and res.handle.plan_seconds() == plan_seconds
     c_own = resolution.fsc(a, b)                          # a handle and a context of its own, closed again
     assert np.array_equal(c_own.C, c_dev.C)
     with pytest.raises(ValueError):

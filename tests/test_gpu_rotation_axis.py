@@ -140,6 +140,26 @@ def test_budgets_repeats_handles_batching_and_paths_give_the_same_bits(ctx, axis
     d.free()
 
 
+def test_a_repeated_metric_finds_every_plan_in_the_cache(ctx):
+    """The smallest sinogram, five pairs in batches of two: a plan of two and the tail's plan of one.  A wrong cache key would make
+    them again, or grow the work area."""
+    n, nx = _cor_lib.MIN_N, _cor_lib.MIN_NX
+    S = np.random.default_rng(3).uniform(0.0, 1.0, (n, nx)).astype(np.float32)
+    budget = 4 * 4 * (2 * n) * 2 * (nx // 2 + 1)
+    assert (n, nx) == (8, 16) and _cor_lib.batch(5, n, nx, budget) == 2
+    d = ctx.to_device(S[:, :, None])
+    slices, ts = [0] * 5, [0.0, 1.0, -2.5, 3.25, -4.0]
+    with _cor_lib.CorHandle(ctx.device) as h:
+        h.load_rows(ctx.stream(), d.ptr, n, nx, 1, 0, n, [0])
+        first = h.metric(ctx.stream(), slices, ts, max_scratch_bytes=budget)
+        seconds, held = h.plan_seconds(), h.device_bytes()
+        second = h.metric(ctx.stream(), slices, ts, max_scratch_bytes=budget)
+        print("m %s, plan seconds %.6f -> %.6f, device bytes %d -> %d" % (first, seconds, h.plan_seconds(), held, h.device_bytes()))
+        assert seconds > 0.0 and h.plan_seconds() == seconds and h.device_bytes() == held
+    assert np.all(first > 0) and np.array_equal(_bits(second), _bits(first))
+    d.free()
+
+
 # ---------------------------------------------------------------------------------------------------------------------- T6: layout
 
 @pytest.mark.parametrize("nz", [5, 64])

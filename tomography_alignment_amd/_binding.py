@@ -59,7 +59,8 @@ def _ptr(p):
 
 class Handle(object):
     """One tomo_<NAME> handle of a side library: tomo_<NAME>_create on construction, tomo_<NAME>_destroy on close().  A context
-    manager.  A subclass sets NAME, load (its module's) and, where return codes map to classes of its own, ERRORS."""
+    manager.  A subclass sets NAME, load (its module's) and, where return codes map to classes of its own, ERRORS.  device_bytes() and
+    plan_seconds() are here for the libraries whose header declares them; on another library they raise AttributeError."""
     NAME = None
     load = None
     ERRORS = {}
@@ -83,6 +84,18 @@ class Handle(object):
         if self._h is None:
             raise TomoError("%s handle closed" % self.NAME)
         return self._h
+
+    def device_bytes(self):
+        """The device bytes the handle holds between calls, where the library's header declares tomo_<NAME>_device_bytes(h, &n)."""
+        n = ctypes.c_int64(0)
+        self._check(self._fn("device_bytes")(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def plan_seconds(self):
+        """The seconds the handle has spent making hipFFT plans, where the header declares tomo_<NAME>_plan_seconds(h, &s)."""
+        s = ctypes.c_double(0.0)
+        self._check(self._fn("plan_seconds")(self.handle, ctypes.byref(s)))
+        return s.value
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -100,16 +100,6 @@ class CorHandle(Handle):
         super(CorHandle, self).__init__(device)
         self.shape = None           # (nslices, n, nx) of the last load
 
-    def device_bytes(self):
-        n = ctypes.c_int64(0)
-        self._check(self.lib.tomo_cor_device_bytes(self.handle, ctypes.byref(n)))
-        return n.value
-
-    def plan_seconds(self):
-        s = _c_double(0.0)
-        self._check(self.lib.tomo_cor_plan_seconds(self.handle, ctypes.byref(s)))
-        return s.value
-
     def load_rows(self, stream, d_p, n_p, nx, nz, first, n, rows, timed=False):
         """Gather the detector rows `rows` of the device sinogram p[n_p][nx][nz], angles first .. first + n - 1, and prefilter them.
         timed=True waits and returns the device ms of the two passes."""

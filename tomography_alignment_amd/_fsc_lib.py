@@ -81,16 +81,6 @@ class FscHandle(Handle):
         self.n_shells = n_shells(*shape)
         return self.n_shells
 
-    def device_bytes(self):
-        n = ctypes.c_int64(0)
-        self._check(self.lib.tomo_fsc_device_bytes(self.handle, ctypes.byref(n)))
-        return n.value
-
-    def plan_seconds(self):
-        s = _c_double(0.0)
-        self._check(self.lib.tomo_fsc_plan_seconds(self.handle, ctypes.byref(s)))
-        return s.value
-
     def prepare(self, stream, slot, d_vol, mask=MASK_NONE, d_mask=None, radius=0.0, edge=0.0, subtract_mean=True):
         self._check(self.lib.tomo_fsc_prepare(self.handle, _ptr(stream), int(slot), _ptr(d_vol), int(mask), _ptr(d_mask), float(radius),
                                               float(edge), 1 if subtract_mean else 0))

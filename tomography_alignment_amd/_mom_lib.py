@@ -92,11 +92,6 @@ class MomHandle(Handle):
         super(MomHandle, self).__init__(device)
         self.shape = None           # (n, nx, nz) of the last marginals()
 
-    def device_bytes(self):
-        n = ctypes.c_int64(0)
-        self._check(self.lib.tomo_mom_device_bytes(self.handle, ctypes.byref(n)))
-        return n.value
-
     def set_max_scratch(self, max_scratch_bytes):
         """The budget of the partial sums for the calls that follow (0 / None: no limit)."""
         self._check(self.lib.tomo_mom_set_max_scratch(self.handle, int(max_scratch_bytes or 0)))

@@ -77,21 +77,11 @@ class PhaseHandle(Handle):
     load = staticmethod(load)
     ERRORS = ERRORS
 
-    def device_bytes(self):
-        n = ctypes.c_int64(0)
-        self._check(self.lib.tomo_phase_device_bytes(self.handle, ctypes.byref(n)))
-        return n.value
-
     def mem_info(self):
         """(free, total) bytes of the device's memory, as hipMemGetInfo reports them."""
         f, t = _c_size(0), _c_size(0)
         self._check(self.lib.tomo_phase_mem_info(self.handle, ctypes.byref(f), ctypes.byref(t)))
         return f.value, t.value
-
-    def plan_seconds(self):
-        s = _c_double(0.0)
-        self._check(self.lib.tomo_phase_plan_seconds(self.handle, ctypes.byref(s)))
-        return s.value
 
     def retrieve(self, stream, d_in, d_out, n, nx, nz, strength, pad_x, pad_z, minus_log=True, min_ratio=1e-6, max_scratch_bytes=0,
                  timed=False):

@@ -22,11 +22,8 @@
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <map>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../../include/tomo_cor.h"
@@ -35,6 +32,7 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_COR_ERR_ARG, SIDE_ERR_HIP = TOMO_COR_ERR_HIP, SIDE_ERR_NODEV = TOMO_COR_ERR_NODEV, SIDE_ERR_FFT = TOMO_COR_ERR_FFT;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_fft.h"
 
 namespace {
 
@@ -42,8 +40,6 @@ constexpr int TPB = 256;
 constexpr int PR = 16, TW = 64;                    // k_prefilter: rows of a work-group, columns of a tile
 constexpr int HORIZON = 128;                       // terms of the causal start: |pole|^128 = 5e-74
 constexpr int RPB = 16;                            // k_reduce: rows of the spectrum per work-group
-constexpr int MAX_BATCH = 65535;                   // pairs of one batch: the y extent of a grid
-constexpr long long MAX_BATCH_FLOATS = 1LL << 31;  // floats of one batch's buffer
 constexpr double POLE = -0.26794919243112270647;   // sqrt(3) - 2
 
 struct Shape {
@@ -205,19 +201,13 @@ __global__ __launch_bounds__(64) void k_final(const double *__restrict__ partial
     m[pair] = s / denom;
 }
 
-struct Plan {
-    hipfftHandle r2c = 0;
-    size_t work_bytes = 0;
-};
-
 }  // namespace
 
 struct tomo_cor {
     int device = 0;
     std::string err;
     Shape g{};                   // of the last load; n = 0 before it
-    std::map<std::tuple<int, int, int>, Plan> plans;
-    std::map<std::tuple<int, int, int>, int> lowered;   // (R, nx, first batch) -> the batch a too large work area lowered it to
+    FftPlans<std::tuple<int, int, int>> plans;   // R2C per (R, nx, batch)
     Buf work;                    // the hipFFT work area all plans share
     Buf S, coef, rows;           // float S[ns][n][nx], double coef[ns][n][nx], int rows[ns]
     Buf spec;                    // the batch buffer
@@ -226,9 +216,9 @@ struct tomo_cor {
     Buf part, dm;                // double partial[batch][nblk], double m[npairs]
     std::vector<int> host_rows, host_tab;
     std::vector<unsigned char> host_pairs;
-    hipEvent_t ev[4] = {};
+    PassTimer<TOMO_COR_METRIC_MS_N> timer;       // of a load's passes as well
+    static_assert(TOMO_COR_LOAD_MS_N <= TOMO_COR_METRIC_MS_N, "the timer has an event for every mark of a load");
     bool rows_in_flight = false; // a load's copy of host_rows may not have run yet: cleared by every call that waits for the stream
-    double t_plan = 0.0;
 };
 
 namespace {
@@ -258,49 +248,6 @@ void wedge(int n, int nx, double ratio, int drop, int *hi) {
     }
 }
 
-size_t frame_bytes(int R, int nx) { return sizeof(float) * (size_t)R * (size_t)(2 * (nx / 2 + 1)); }
-
-int batch_for(int npairs, int R, int nx, size_t budget, size_t work_per_frame) {
-    const size_t fb = frame_bytes(R, nx);
-    long long b = npairs;
-    if (budget) b = std::min<long long>(b, (long long)(budget / (fb + work_per_frame)));
-    b = std::min<long long>(b, MAX_BATCH);
-    b = std::min<long long>(b, MAX_BATCH_FLOATS / (long long)(fb / sizeof(float)));
-    return (int)std::max<long long>(b, 1);
-}
-
-int get_plan(tomo_cor *h, int R, int nx, int b, Plan **out) {
-    auto key = std::make_tuple(R, nx, b);
-    auto it = h->plans.find(key);
-    if (it != h->plans.end()) {
-        *out = &it->second;
-        return TOMO_COR_OK;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    Plan p;
-    int dims[2] = {R, nx};
-    size_t ws = 0;
-    hipfftResult r = hipfftCreate(&p.r2c);
-    if (r == HIPFFT_SUCCESS) r = hipfftSetAutoAllocation(p.r2c, 0);
-    if (r == HIPFFT_SUCCESS) r = hipfftMakePlanMany(p.r2c, 2, dims, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_R2C, b, &ws);
-    if (r != HIPFFT_SUCCESS) {
-        if (p.r2c) hipfftDestroy(p.r2c);
-        return fail(h, TOMO_COR_ERR_FFT, "hipfft plan (" + std::to_string(R) + " x " + std::to_string(nx) + ", batch " + std::to_string(b) +
-                                             "): hipfft error " + std::to_string((int)r));
-    }
-    p.work_bytes = ws;
-    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    *out = &(h->plans[key] = p);
-    return TOMO_COR_OK;
-}
-
-void drop_plan(tomo_cor *h, int R, int nx, int b) {
-    auto it = h->plans.find(std::make_tuple(R, nx, b));
-    if (it == h->plans.end()) return;
-    hipfftDestroy(it->second.r2c);
-    h->plans.erase(it);
-}
-
 inline dim3 grid(long long per, int b) { return dim3((unsigned)((per + TPB - 1) / TPB), (unsigned)b); }
 
 int launch_build(tomo_cor *h, hipStream_t st, int b, const int *d_slice, const double *d_t, float *buf) {
@@ -312,20 +259,18 @@ int launch_build(tomo_cor *h, hipStream_t st, int b, const int *d_slice, const d
 }
 
 // Pairs p0 .. p0 + b - 1, enqueued on st.  ms: NULL or the three pass times to add to (synchronises).
-int run_batch(tomo_cor *h, hipStream_t st, Plan *plan, int p0, int b, int npairs, float *ms) {
+int run_batch(tomo_cor *h, hipStream_t st, const FftPlan *plan, int p0, int b, int npairs, float *ms) {
     const Shape &g = h->g;
     const double *d_t = static_cast<const double *>(h->pairs.p) + p0;
     const int *d_slice = reinterpret_cast<const int *>(static_cast<const double *>(h->pairs.p) + npairs) + p0;
     float *buf = static_cast<float *>(h->spec.p);
     const int nblk = (g.R + RPB - 1) / RPB;
     int e = 0;
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    if (ms) CHK(h->timer.mark(h, st, e++));
     CHK(launch_build(h, st, b, d_slice, d_t, buf));
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
-    FFTCHK(h, hipfftSetStream(plan->r2c, st));
-    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->r2c, h->work.p));
-    FFTCHK(h, hipfftExecR2C(plan->r2c, (hipfftReal *)buf, (hipfftComplex *)buf));
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    if (ms) CHK(h->timer.mark(h, st, e++));
+    CHK(exec_forward(h, *plan, st, h->work.p, buf));
+    if (ms) CHK(h->timer.mark(h, st, e++));
     hipLaunchKernelGGL(k_reduce, dim3((unsigned)nblk, (unsigned)b), dim3(TPB), 0, st, (const float2 *)buf, g, (const int *)h->tab.p, nblk,
                        (double *)h->part.p);
     HIPCHK(h, hipGetLastError());
@@ -333,13 +278,8 @@ int run_batch(tomo_cor *h, hipStream_t st, Plan *plan, int p0, int b, int npairs
                        static_cast<double *>(h->dm.p) + p0);
     HIPCHK(h, hipGetLastError());
     if (ms) {
-        HIPCHK(h, hipEventRecord(h->ev[e], st));
-        HIPCHK(h, hipEventSynchronize(h->ev[e]));
-        for (int p = 0; p < TOMO_COR_METRIC_MS_N; ++p) {
-            float t = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&t, h->ev[p], h->ev[p + 1]));
-            ms[p] += t;
-        }
+        CHK(h->timer.mark(h, st, e));
+        CHK(h->timer.add_elapsed(h, ms, TOMO_COR_METRIC_MS_N));
     }
     return TOMO_COR_OK;
 }
@@ -361,13 +301,10 @@ TOMO_API int tomo_cor_create(int device, tomo_cor **out) {
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_COR_ERR_HIP, "hipSetDevice failed");
     tomo_cor *h = new tomo_cor();
     h->device = device;
-    for (hipEvent_t &e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            for (hipEvent_t &d : h->ev)
-                if (d) (void)hipEventDestroy(d);
-            delete h;
-            return fail(nullptr, TOMO_COR_ERR_HIP, "hipEventCreate failed");
-        }
+    if (!h->timer.create()) {
+        delete h;
+        return fail(nullptr, TOMO_COR_ERR_HIP, "hipEventCreate failed");
+    }
     *out = h;
     return TOMO_COR_OK;
 }
@@ -375,11 +312,10 @@ TOMO_API int tomo_cor_create(int device, tomo_cor **out) {
 TOMO_API int tomo_cor_destroy(tomo_cor *h) {
     if (!h) return TOMO_COR_OK;
     (void)hipSetDevice(h->device);
-    for (auto &kv : h->plans) hipfftDestroy(kv.second.r2c);
+    h->plans.destroy_all();
     for (Buf *b : {&h->work, &h->S, &h->coef, &h->rows, &h->spec, &h->pairs, &h->tab, &h->part, &h->dm})
         if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t &e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     delete h;
     return TOMO_COR_OK;
 }
@@ -400,7 +336,7 @@ TOMO_API int tomo_cor_batch(int npairs, int n, int nx, size_t max_scratch_bytes,
     if (!batch) return fail(nullptr, TOMO_COR_ERR_ARG, "tomo_cor_batch: NULL");
     if (npairs < 1) return fail(nullptr, TOMO_COR_ERR_ARG, "tomo_cor_batch: needs at least one pair");
     CHK(check_shape(nullptr, n, nx, 1));
-    *batch = batch_for(npairs, 2 * n, nx, max_scratch_bytes, frame_bytes(2 * n, nx));
+    *batch = batch_for(npairs, frame_bytes(2 * n, nx), max_scratch_bytes, frame_bytes(2 * n, nx));
     return TOMO_COR_OK;
 }
 
@@ -412,7 +348,7 @@ TOMO_API int tomo_cor_device_bytes(tomo_cor *h, int64_t *bytes) {
 
 TOMO_API int tomo_cor_plan_seconds(tomo_cor *h, double *seconds) {
     if (!h || !seconds) return fail(h, TOMO_COR_ERR_ARG, "tomo_cor_plan_seconds: NULL");
-    *seconds = h->t_plan;
+    *seconds = h->plans.seconds;
     return TOMO_COR_OK;
 }
 
@@ -438,19 +374,19 @@ TOMO_API int tomo_cor_load(tomo_cor *h, void *stream, const float *d_p, int n_p,
     h->host_rows.assign(rows, rows + nslices);
     h->rows_in_flight = true;
     HIPCHK(h, hipMemcpyAsync(h->rows.p, h->host_rows.data(), sizeof(int) * (size_t)nslices, hipMemcpyHostToDevice, st));
-    if (pass_ms) HIPCHK(h, hipEventRecord(h->ev[0], st));
+    if (pass_ms) CHK(h->timer.mark(h, st, 0));
     const long long per = (long long)n * nx;
     hipLaunchKernelGGL(k_gather, dim3((unsigned)((per + TPB - 1) / TPB)), dim3(TPB), 0, st, d_p, nx, nz, first, n, (const int *)h->rows.p, nslices,
                        (float *)h->S.p);
     HIPCHK(h, hipGetLastError());
-    if (pass_ms) HIPCHK(h, hipEventRecord(h->ev[1], st));
+    if (pass_ms) CHK(h->timer.mark(h, st, 1));
     const long long total = (long long)nslices * n;
     hipLaunchKernelGGL(k_prefilter, dim3((unsigned)((total + PR - 1) / PR)), dim3(64), 0, st, (const float *)h->S.p, nx, total, (double *)h->coef.p);
     HIPCHK(h, hipGetLastError());
     if (pass_ms) {
-        HIPCHK(h, hipEventRecord(h->ev[2], st));
-        HIPCHK(h, hipEventSynchronize(h->ev[2]));
-        for (int p = 0; p < TOMO_COR_LOAD_MS_N; ++p) HIPCHK(h, hipEventElapsedTime(&pass_ms[p], h->ev[p], h->ev[p + 1]));
+        CHK(h->timer.mark(h, st, TOMO_COR_LOAD_MS_N));
+        for (int p = 0; p < TOMO_COR_LOAD_MS_N; ++p) pass_ms[p] = 0.f;
+        CHK(h->timer.add_elapsed(h, pass_ms, TOMO_COR_LOAD_MS_N));
     }
     h->g.n = n, h->g.nx = nx, h->g.ns = nslices, h->g.R = 2 * n, h->g.H = nx / 2 + 1;
     return TOMO_COR_OK;
@@ -472,26 +408,14 @@ TOMO_API int tomo_cor_metric(tomo_cor *h, void *stream, const int *slice, const 
     if (pass_ms)
         for (int p = 0; p < TOMO_COR_METRIC_MS_N; ++p) pass_ms[p] = 0.f;
 
-    // the batch: first with the work area taken to be one spectrum a pair, then with what the plan asks for
-    const size_t budget = max_scratch_bytes, fb = frame_bytes(g.R, g.nx);
-    int b = batch_for(npairs, g.R, g.nx, budget, fb);
-    Plan *plan = nullptr, *tail = nullptr;
-    const auto first = std::make_tuple(g.R, g.nx, b);
-    const auto low = h->lowered.find(first);
-    if (budget && low != h->lowered.end() && (size_t)low->second * fb < budget) b = low->second;
-    CHK(get_plan(h, g.R, g.nx, b, &plan));
-    if (budget && b > 1 && (size_t)b * fb + plan->work_bytes > budget) {
-        const size_t per = (plan->work_bytes + b - 1) / b;
-        const int b2 = std::min(b - 1, batch_for(npairs, g.R, g.nx, budget, per));
-        drop_plan(h, g.R, g.nx, b);
-        h->lowered[first] = b2;
-        b = b2;
-        CHK(get_plan(h, g.R, g.nx, b, &plan));
-    }
-    if (npairs % b) CHK(get_plan(h, g.R, g.nx, npairs % b, &tail));
+    // the batch and its plans (fit_batch)
+    const size_t fb = frame_bytes(g.R, g.nx);
+    BatchFit fit;
+    CHK(fit_r2c_2d(h, h->plans, g.R, g.nx, npairs, max_scratch_bytes, false, &fit));
+    const int b = fit.b;
     // every call that used these buffers waited for the stream before it returned, so nothing in flight uses a block a grow frees
     const int nblk = (g.R + RPB - 1) / RPB;
-    CHK(grow(h, h->work, std::max(plan->work_bytes, tail ? tail->work_bytes : (size_t)0)));
+    CHK(grow(h, h->work, fit.max_work()));
     CHK(grow(h, h->spec, (size_t)b * fb));
     CHK(grow(h, h->part, sizeof(double) * (size_t)b * nblk));
     CHK(grow(h, h->dm, sizeof(double) * (size_t)npairs));
@@ -506,7 +430,7 @@ TOMO_API int tomo_cor_metric(tomo_cor *h, void *stream, const int *slice, const 
     HIPCHK(h, hipMemcpyAsync(h->pairs.p, h->host_pairs.data(), h->host_pairs.size(), hipMemcpyHostToDevice, st));
     for (int p0 = 0; p0 < npairs; p0 += b) {
         const int bb = std::min(b, npairs - p0);
-        CHK(run_batch(h, st, bb == b ? plan : tail, p0, bb, npairs, pass_ms));
+        CHK(run_batch(h, st, bb == b ? fit.plan : fit.tail, p0, bb, npairs, pass_ms));
     }
     HIPCHK(h, hipMemcpyAsync(m, h->dm.p, sizeof(double) * (size_t)npairs, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));

@@ -17,11 +17,9 @@
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
-#include <chrono>
-#include <map>
 #include <string>
-#include <tuple>
 #include <type_traits>
+#include <vector>
 
 #include "../../../include/tomo_fsc.h"
 
@@ -29,6 +27,7 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_FSC_ERR_ARG, SIDE_ERR_HIP = TOMO_FSC_ERR_HIP, SIDE_ERR_NODEV = TOMO_FSC_ERR_NODEV, SIDE_ERR_FFT = TOMO_FSC_ERR_FFT;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_fft.h"
 
 namespace {
 
@@ -254,12 +253,6 @@ __global__ __launch_bounds__(TPB) void k_take_rows(const float *__restrict__ src
     reinterpret_cast<vec_t *>(dst)[i] = reinterpret_cast<const vec_t *>(src)[(first + r * step) * row_v + c];
 }
 
-struct Plan {
-    hipfftHandle fft = 0;
-    void *work = nullptr;
-    size_t work_bytes = 0;
-};
-
 }  // namespace
 
 struct tomo_fsc {
@@ -267,10 +260,10 @@ struct tomo_fsc {
     std::string err;
     bool shaped = false;
     Shape g{};
-    std::map<std::tuple<int, int, int, int, int>, Plan> plans;
-    Plan *plan = nullptr;
+    FftPlans<std::tuple<int, int, int, int, int>> plans;   // R2C per (ndim, nb, nx, ny, nz), each with a work area of its own
+    FftPlan *plan = nullptr;
+    std::vector<void *> areas;       // the plans' work areas, set when a plan is made; a plan's size is its work_bytes
     Buf spec[2], sums, part, table;
-    double t_plan = 0.0;
 };
 
 namespace {
@@ -307,46 +300,25 @@ int make_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, int nz, Shape *out
 
 size_t spectrum_bytes(const Shape &g) { return sizeof(float2) * (size_t)g.nb * (size_t)g.rows * (size_t)g.nzh; }
 
-int get_plan(tomo_fsc *h, const Shape &g, Plan **out) {
-    auto key = std::make_tuple(g.ndim, g.nb, g.nx, g.ny, g.nz);
-    auto it = h->plans.find(key);
-    if (it != h->plans.end()) {
-        *out = &it->second;
-        return TOMO_FSC_OK;
+// One 3-D transform, or nb 2-D ones, with the work area they ask for.
+int make_plan(tomo_fsc *h, const Shape &g, FftPlan &p) {
+    const hipfftResult r = new_plan(&p.fwd, &p.work_bytes, [&](hipfftHandle f, size_t *ws) {
+        if (g.ndim == 3) return hipfftMakePlan3d(f, g.nx, g.ny, g.nz, HIPFFT_R2C, ws);
+        int n[2] = {g.nx, g.nz};
+        return hipfftMakePlanMany(f, 2, n, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_R2C, g.nb, ws);
+    });
+    if (r != HIPFFT_SUCCESS) return fail(h, TOMO_FSC_ERR_FFT, "hipfft R2C plan: hipfft error " + std::to_string((int)r));
+    if (!p.work_bytes) return TOMO_FSC_OK;
+    void *work = nullptr;
+    const hipError_t e = hipMalloc(&work, p.work_bytes);
+    const hipfftResult w = e == hipSuccess ? hipfftSetWorkArea(p.fwd, work) : HIPFFT_SUCCESS;
+    if (e != hipSuccess || w != HIPFFT_SUCCESS) {
+        if (e == hipSuccess) (void)hipFree(work);
+        release(p);
+        return e != hipSuccess ? fail(h, TOMO_FSC_ERR_HIP, std::string("hipMalloc of the hipFFT work area: ") + hipGetErrorString(e))
+                               : fail(h, TOMO_FSC_ERR_FFT, "hipfftSetWorkArea: hipfft error " + std::to_string((int)w));
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    Plan p;
-    FFTCHK(h, hipfftCreate(&p.fft));
-    hipfftResult r = hipfftSetAutoAllocation(p.fft, 0);
-    size_t ws = 0;
-    if (r == HIPFFT_SUCCESS) {
-        if (g.ndim == 3) {
-            r = hipfftMakePlan3d(p.fft, g.nx, g.ny, g.nz, HIPFFT_R2C, &ws);
-        } else {
-            int n[2] = {g.nx, g.nz};
-            r = hipfftMakePlanMany(p.fft, 2, n, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_R2C, g.nb, &ws);
-        }
-    }
-    if (r != HIPFFT_SUCCESS) {
-        hipfftDestroy(p.fft);
-        return fail(h, TOMO_FSC_ERR_FFT, "hipfft R2C plan: hipfft error " + std::to_string((int)r));
-    }
-    if (ws) {
-        hipError_t e = hipMalloc(&p.work, ws);
-        if (e != hipSuccess) {
-            hipfftDestroy(p.fft);
-            return fail(h, TOMO_FSC_ERR_HIP, std::string("hipMalloc of the hipFFT work area: ") + hipGetErrorString(e));
-        }
-        p.work_bytes = ws;
-        r = hipfftSetWorkArea(p.fft, p.work);
-        if (r != HIPFFT_SUCCESS) {
-            (void)hipFree(p.work);
-            hipfftDestroy(p.fft);
-            return fail(h, TOMO_FSC_ERR_FFT, "hipfftSetWorkArea: hipfft error " + std::to_string((int)r));
-        }
-    }
-    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    *out = &(h->plans[key] = p);
+    h->areas.push_back(work);
     return TOMO_FSC_OK;
 }
 
@@ -375,10 +347,8 @@ TOMO_API int tomo_fsc_create(int device, tomo_fsc **out) {
 TOMO_API int tomo_fsc_destroy(tomo_fsc *h) {
     if (!h) return TOMO_FSC_OK;
     (void)hipSetDevice(h->device);
-    for (auto &kv : h->plans) {
-        hipfftDestroy(kv.second.fft);
-        if (kv.second.work) (void)hipFree(kv.second.work);
-    }
+    h->plans.destroy_all();
+    for (void *w : h->areas) (void)hipFree(w);
     for (Buf *b : {&h->spec[0], &h->spec[1], &h->sums, &h->part, &h->table})
         if (b->p) (void)hipFree(b->p);
     delete h;
@@ -401,7 +371,7 @@ TOMO_API int tomo_fsc_set_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, i
     CHK(make_shape(h, ndim, nb, nx, ny, nz, &g));
     HIPCHK(h, hipSetDevice(h->device));
     h->shaped = false;
-    CHK(get_plan(h, g, &h->plan));
+    CHK(h->plans.get(std::make_tuple(g.ndim, g.nb, g.nx, g.ny, g.nz), [&](FftPlan &p) { return make_plan(h, g, p); }, &h->plan));
     CHK(grow(h, h->spec[0], spectrum_bytes(g)));
     CHK(grow(h, h->spec[1], spectrum_bytes(g)));
     CHK(grow(h, h->sums, sizeof(double) * 2 * SUM_G * (size_t)g.nb));
@@ -415,14 +385,14 @@ TOMO_API int tomo_fsc_set_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, i
 TOMO_API int tomo_fsc_device_bytes(tomo_fsc *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_device_bytes: NULL");
     size_t t = h->spec[0].n + h->spec[1].n + h->sums.n + h->part.n + h->table.n;
-    for (auto &kv : h->plans) t += kv.second.work_bytes;
+    for (auto &kv : h->plans.plans) t += kv.second.work_bytes;
     *bytes = (int64_t)t;
     return TOMO_FSC_OK;
 }
 
 TOMO_API int tomo_fsc_plan_seconds(tomo_fsc *h, double *seconds) {
     if (!h || !seconds) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_plan_seconds: NULL");
-    *seconds = h->t_plan;
+    *seconds = h->plans.seconds;
     return TOMO_FSC_OK;
 }
 
@@ -458,8 +428,8 @@ TOMO_API int tomo_fsc_fft(tomo_fsc *h, void *stream, int slot) {
     CHK(ready(h, "tomo_fsc_fft"));
     if (slot != 0 && slot != 1) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_fft: slot must be 0 or 1");
     HIPCHK(h, hipSetDevice(h->device));
-    FFTCHK(h, hipfftSetStream(h->plan->fft, reinterpret_cast<hipStream_t>(stream)));
-    FFTCHK(h, hipfftExecR2C(h->plan->fft, (hipfftReal *)h->spec[slot].p, (hipfftComplex *)h->spec[slot].p));
+    FFTCHK(h, hipfftSetStream(h->plan->fwd, reinterpret_cast<hipStream_t>(stream)));       // the work area was set with the plan
+    FFTCHK(h, hipfftExecR2C(h->plan->fwd, (hipfftReal *)h->spec[slot].p, (hipfftComplex *)h->spec[slot].p));
     return TOMO_FSC_OK;
 }
 

@@ -20,11 +20,8 @@
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <map>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../../include/tomo_phase.h"
@@ -33,12 +30,11 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_PHASE_ERR_ARG, SIDE_ERR_HIP = TOMO_PHASE_ERR_HIP, SIDE_ERR_NODEV = TOMO_PHASE_ERR_NODEV, SIDE_ERR_FFT = TOMO_PHASE_ERR_FFT;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_fft.h"
 
 namespace {
 
 constexpr int TPB = 256;
-constexpr int MAX_BATCH = 65535;                 // frames of one batch: the y extent of a grid
-constexpr long long MAX_BATCH_FLOATS = 1LL << 31;  // floats of one batch's buffer
 
 struct Shape {
     int nx, nz;          // a frame
@@ -138,23 +134,16 @@ __global__ __launch_bounds__(TPB) void k_log(const float *in, float *out, size_t
     }
 }
 
-struct Plan {
-    hipfftHandle r2c = 0, c2r = 0;
-    size_t work_bytes = 0;       // the larger of the two
-};
-
 }  // namespace
 
 struct tomo_phase {
     int device = 0;
     std::string err;
-    std::map<std::tuple<int, int, int>, Plan> plans;
-    std::map<std::tuple<int, int, int>, int> lowered;   // (px, pz, first batch) -> the batch a too large work area lowered it to
+    FftPlans<std::tuple<int, int, int>> plans;   // R2C + C2R per (px, pz, batch)
     Buf work;                    // the hipFFT work area all plans share
     Buf tables;                  // double tx[px], tz[pzh]
     std::vector<double> host_tables;
-    hipEvent_t ev[TOMO_PHASE_MS_N + 1] = {};
-    double t_plan = 0.0;
+    PassTimer<TOMO_PHASE_MS_N> timer;
 };
 
 namespace {
@@ -179,56 +168,6 @@ int padded(tomo_phase *h, int n, int m, int *out) {
     return TOMO_PHASE_OK;
 }
 
-size_t frame_bytes(int px, int pz) { return sizeof(float) * (size_t)px * (size_t)(2 * (pz / 2 + 1)); }
-
-// The frames of a batch when the work area is work_per_frame bytes a frame.
-int batch_for(int n, int px, int pz, size_t budget, size_t work_per_frame) {
-    const size_t fb = frame_bytes(px, pz);
-    long long b = n;
-    if (budget) b = std::min<long long>(b, (long long)(budget / (fb + work_per_frame)));
-    b = std::min<long long>(b, MAX_BATCH);
-    b = std::min<long long>(b, MAX_BATCH_FLOATS / (long long)(fb / sizeof(float)));
-    return (int)std::max<long long>(b, 1);
-}
-
-int get_plan(tomo_phase *h, int px, int pz, int b, Plan **out) {
-    auto key = std::make_tuple(px, pz, b);
-    auto it = h->plans.find(key);
-    if (it != h->plans.end()) {
-        *out = &it->second;
-        return TOMO_PHASE_OK;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    Plan p;
-    int n[2] = {px, pz};
-    hipfftHandle *hs[2] = {&p.r2c, &p.c2r};
-    const hipfftType types[2] = {HIPFFT_R2C, HIPFFT_C2R};
-    for (int i = 0; i < 2; ++i) {
-        size_t ws = 0;
-        hipfftResult r = hipfftCreate(hs[i]);
-        if (r == HIPFFT_SUCCESS) r = hipfftSetAutoAllocation(*hs[i], 0);
-        if (r == HIPFFT_SUCCESS) r = hipfftMakePlanMany(*hs[i], 2, n, nullptr, 1, 0, nullptr, 1, 0, types[i], b, &ws);
-        if (r != HIPFFT_SUCCESS) {
-            if (p.r2c) hipfftDestroy(p.r2c);
-            if (p.c2r) hipfftDestroy(p.c2r);
-            return fail(h, TOMO_PHASE_ERR_FFT, "hipfft plan (" + std::to_string(px) + " x " + std::to_string(pz) + ", batch " + std::to_string(b) +
-                                                   "): hipfft error " + std::to_string((int)r));
-        }
-        p.work_bytes = std::max(p.work_bytes, ws);
-    }
-    h->t_plan += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    *out = &(h->plans[key] = p);
-    return TOMO_PHASE_OK;
-}
-
-void drop_plan(tomo_phase *h, int px, int pz, int b) {
-    auto it = h->plans.find(std::make_tuple(px, pz, b));
-    if (it == h->plans.end()) return;
-    hipfftDestroy(it->second.r2c);
-    hipfftDestroy(it->second.c2r);
-    h->plans.erase(it);
-}
-
 inline dim3 grid(long long per_frame, int b) { return dim3((unsigned)((per_frame + TPB - 1) / TPB), (unsigned)b); }
 
 int launch_log(tomo_phase *h, hipStream_t st, const float *d_in, float *d_out, size_t count, float min_ratio) {
@@ -242,26 +181,22 @@ int launch_log(tomo_phase *h, hipStream_t st, const float *d_in, float *d_out, s
 }
 
 // One batch of b frames, enqueued on st.  ms: NULL or the five pass times to add to (synchronises).
-int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, Plan *plan, int b, const float *d_in, float *d_out, float *buf, int minus_log,
+int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, const FftPlan *plan, int b, const float *d_in, float *d_out, float *buf, int minus_log,
               float min_ratio, float *ms) {
     const double *tx = static_cast<const double *>(h->tables.p), *tz = tx + g.px;
     const int per_row = (g.pzh + 1) / 2 + 1;
     int e = 0;
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    if (ms) CHK(h->timer.mark(h, st, e++));
     hipLaunchKernelGGL(k_pad, grid((long long)g.px * g.pzh, b), dim3(TPB), 0, st, d_in, g, buf);
     HIPCHK(h, hipGetLastError());
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
-    FFTCHK(h, hipfftSetStream(plan->r2c, st));
-    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->r2c, h->work.p));
-    FFTCHK(h, hipfftExecR2C(plan->r2c, (hipfftReal *)buf, (hipfftComplex *)buf));
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    if (ms) CHK(h->timer.mark(h, st, e++));
+    CHK(exec_forward(h, *plan, st, h->work.p, buf));
+    if (ms) CHK(h->timer.mark(h, st, e++));
     hipLaunchKernelGGL(k_filter, grid((long long)g.px * per_row, b), dim3(TPB), 0, st, (float2 *)buf, g, tx, tz, per_row);
     HIPCHK(h, hipGetLastError());
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
-    FFTCHK(h, hipfftSetStream(plan->c2r, st));
-    if (plan->work_bytes) FFTCHK(h, hipfftSetWorkArea(plan->c2r, h->work.p));
-    FFTCHK(h, hipfftExecC2R(plan->c2r, (hipfftComplex *)buf, (hipfftReal *)buf));
-    if (ms) HIPCHK(h, hipEventRecord(h->ev[e++], st));
+    if (ms) CHK(h->timer.mark(h, st, e++));
+    CHK(exec_inverse(h, *plan, st, h->work.p, buf));
+    if (ms) CHK(h->timer.mark(h, st, e++));
     const bool v4 = g.nz % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
     const dim3 gr = grid((long long)g.nx * (v4 ? g.nz / 4 : g.nz), b);
     if (v4 && g.oz % 2 == 0)
@@ -272,13 +207,8 @@ int run_batch(tomo_phase *h, hipStream_t st, const Shape &g, Plan *plan, int b, 
         hipLaunchKernelGGL((k_crop<1, false>), gr, dim3(TPB), 0, st, (const float *)buf, g, minus_log, min_ratio, d_out);
     HIPCHK(h, hipGetLastError());
     if (ms) {
-        HIPCHK(h, hipEventRecord(h->ev[e], st));
-        HIPCHK(h, hipEventSynchronize(h->ev[e]));
-        for (int p = 0; p < TOMO_PHASE_MS_N; ++p) {
-            float t = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&t, h->ev[p], h->ev[p + 1]));
-            ms[p] += t;
-        }
+        CHK(h->timer.mark(h, st, e));
+        CHK(h->timer.add_elapsed(h, ms, TOMO_PHASE_MS_N));
     }
     return TOMO_PHASE_OK;
 }
@@ -300,31 +230,18 @@ int retrieve(tomo_phase *h, hipStream_t st, const Shape &g, int n, double a, con
     CHK(grow(h, h->tables, tb));
     HIPCHK(h, hipMemcpyAsync(h->tables.p, h->host_tables.data(), tb, hipMemcpyHostToDevice, st));
 
-    // the batch: first with the work area taken to be one spectrum a frame, then with what the plan asks for
+    // the batch and its plans (fit_batch)
     const size_t fb = frame_bytes(g.px, g.pz);
-    int b = batch_for(n, g.px, g.pz, budget, fb);
-    Plan *plan = nullptr;
-    const auto first = std::make_tuple(g.px, g.pz, b);
-    const auto low = h->lowered.find(first);
-    if (budget && low != h->lowered.end() && (size_t)low->second * fb < budget) b = low->second;     // decided by an earlier call
-    CHK(get_plan(h, g.px, g.pz, b, &plan));
-    if (budget && b > 1 && (size_t)b * fb + plan->work_bytes > budget) {
-        const size_t per = (plan->work_bytes + b - 1) / b;
-        const int b2 = std::min(b - 1, batch_for(n, g.px, g.pz, budget, per));
-        drop_plan(h, g.px, g.pz, b);
-        h->lowered[first] = b2;                       // so that the next call does not make the large plan again
-        b = b2;
-        CHK(get_plan(h, g.px, g.pz, b, &plan));
-    }
-    Plan *tail = nullptr;
-    if (n % b) CHK(get_plan(h, g.px, g.pz, n % b, &tail));
+    BatchFit fit;
+    CHK(fit_r2c_2d(h, h->plans, g.px, g.pz, n, budget, true, &fit));
+    const int b = fit.b;
     // retrieve() waits for the stream before it returns, so nothing of this handle is in flight when the work area is replaced
-    CHK(grow(h, h->work, std::max(plan->work_bytes, tail ? tail->work_bytes : (size_t)0)));
+    CHK(grow(h, h->work, fit.max_work()));
     HIPCHK(h, hipMalloc((void **)spec, (size_t)b * fb));
     const size_t in_frame = (size_t)g.nx * g.nz;
     for (int f0 = 0; f0 < n; f0 += b) {
         const int bb = std::min(b, n - f0);
-        CHK(run_batch(h, st, g, bb == b ? plan : tail, bb, d_in + f0 * in_frame, d_out + f0 * in_frame, *spec, minus_log, min_ratio, ms));
+        CHK(run_batch(h, st, g, bb == b ? fit.plan : fit.tail, bb, d_in + f0 * in_frame, d_out + f0 * in_frame, *spec, minus_log, min_ratio, ms));
     }
     HIPCHK(h, hipStreamSynchronize(st));
     return TOMO_PHASE_OK;
@@ -341,13 +258,10 @@ TOMO_API int tomo_phase_create(int device, tomo_phase **out) {
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipSetDevice failed");
     tomo_phase *h = new tomo_phase();
     h->device = device;
-    for (hipEvent_t &e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            for (hipEvent_t &d : h->ev)
-                if (d) (void)hipEventDestroy(d);
-            delete h;
-            return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipEventCreate failed");
-        }
+    if (!h->timer.create()) {
+        delete h;
+        return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipEventCreate failed");
+    }
     *out = h;
     return TOMO_PHASE_OK;
 }
@@ -355,14 +269,10 @@ TOMO_API int tomo_phase_create(int device, tomo_phase **out) {
 TOMO_API int tomo_phase_destroy(tomo_phase *h) {
     if (!h) return TOMO_PHASE_OK;
     (void)hipSetDevice(h->device);
-    for (auto &kv : h->plans) {
-        hipfftDestroy(kv.second.r2c);
-        hipfftDestroy(kv.second.c2r);
-    }
+    h->plans.destroy_all();
     if (h->work.p) (void)hipFree(h->work.p);
     if (h->tables.p) (void)hipFree(h->tables.p);
-    for (hipEvent_t &e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     delete h;
     return TOMO_PHASE_OK;
 }
@@ -378,7 +288,7 @@ TOMO_API int tomo_phase_batch(int n, int px, int pz, size_t max_scratch_bytes, i
     if (!batch) return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_batch: NULL");
     if (n < 1 || px < 2 || pz < 2 || px > TOMO_PHASE_MAX_P || pz > TOMO_PHASE_MAX_P || pz % 2)
         return fail(nullptr, TOMO_PHASE_ERR_ARG, "tomo_phase_batch: bad shape");
-    *batch = batch_for(n, px, pz, max_scratch_bytes, frame_bytes(px, pz));
+    *batch = batch_for(n, frame_bytes(px, pz), max_scratch_bytes, frame_bytes(px, pz));
     return TOMO_PHASE_OK;
 }
 
@@ -397,7 +307,7 @@ TOMO_API int tomo_phase_mem_info(tomo_phase *h, size_t *free_bytes, size_t *tota
 
 TOMO_API int tomo_phase_plan_seconds(tomo_phase *h, double *seconds) {
     if (!h || !seconds) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_plan_seconds: NULL");
-    *seconds = h->t_plan;
+    *seconds = h->plans.seconds;
     return TOMO_PHASE_OK;
 }
 

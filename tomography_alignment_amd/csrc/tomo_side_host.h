@@ -5,8 +5,9 @@
 //
 // The libraries number their errors differently (include/tomo_*.h), so this header names no code of its own.  Before including it a
 // .hip defines, in an anonymous namespace,
-//     constexpr int SIDE_ERR_ARG = ..., SIDE_ERR_HIP = ..., SIDE_ERR_NODEV = ...;     and, if it uses FFTCHK,  SIDE_ERR_FFT = ...;
-// 0 is success in all of them.  The handle struct of a library has a member `std::string err`.
+//     constexpr int SIDE_ERR_ARG = ..., SIDE_ERR_HIP = ..., SIDE_ERR_NODEV = ...;     and, with hipFFT,  SIDE_ERR_FFT = ...;
+// 0 is success in all of them.  The handle struct of a library has a member `std::string err`.  A library that uses hipFFT includes
+// tomo_side_fft.h after this header: FFTCHK, the plan cache, the batch rule and the pass timer.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,11 +35,6 @@ inline int fail(std::nullptr_t, int code, const std::string &msg) {
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
         if (e_ != hipSuccess) return fail(h, SIDE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define FFTCHK(h, call)                                                                                                             \
-    do {                                                                                                                            \
-        hipfftResult r_ = (call);                                                                                                   \
-        if (r_ != HIPFFT_SUCCESS) return fail(h, SIDE_ERR_FFT, std::string(#call) + ": hipfft error " + std::to_string((int)r_));   \
     } while (0)
 #define CHK(expr)                \
     do {                         \

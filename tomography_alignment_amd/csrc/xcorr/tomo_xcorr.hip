@@ -19,6 +19,7 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_XCORR_ERR_ARG, SIDE_ERR_HIP = TOMO_XCORR_ERR_HIP, SIDE_ERR_NODEV = TOMO_XCORR_ERR_NODEV, SIDE_ERR_FFT = TOMO_XCORR_ERR_FFT;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_fft.h"
 
 namespace {
 
