@@ -99,6 +99,10 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *   "fwd_flat_tab" 1 (default): the flat forward over 16 x 16 x 128-voxel blocks with the two 64-plane images interleaved per plane and
  *                 each row's weights in an LDS table (k_fwd_flat_tab), run over the blocks that hold a non-zero voxel only; 0: the round-2
  *                 kernel (entries broadcast with v_readlane)
+ *   "fwd_flat_gather" 1 (default): a whole-volume tomo_forward call ALL of whose poses qualify for the gather adjoint with step >= 0.95
+ *                 voxel (untilted, detector pitch = voxel), on a volume of at most 4 GiB with nx, ny <= 8192, takes the gather-form forward (k_fwd_gather_flat:
+ *                 rays keep their sums in registers, no atomics, the same bits on every run).  Calls that do not qualify, tomo_forward_xslab
+ *                 and value 0 keep k_fwd_flat_tab; needs "adj_flat_gather" 1 (the two kernels share their per-projection constants)
  *   "fwd_flat_wide" 0 (default); 1: measurement variant of the flat forward with a 32 x 16 x 63 tile footprint and one image
  *                 per work-group (half the tile crossings, hence half the sinogram atomics; whole-volume calls only)
  *   "adj_flat_gather" 1 (default): untilted projections on a unit lattice (detector pitch = step = voxel) take the gather-form

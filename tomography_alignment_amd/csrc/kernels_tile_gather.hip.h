@@ -394,3 +394,276 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// GATHER-form FORWARD for the same lattices (k_fwd_gather_flat; per list fwd_gather_flat_body<NW, WALKY>): the role swap of k_adj_gather_flat.  Rays own their sums in
+// registers, the volume streams through wave-private LDS rows, nothing is added across work-groups:
+//     (A x)(ix, iz) = (1 - tau) S(ix, iz + zc) + tau S(ix, iz + zc + 1),     S(ix, Z) = sum_{X, Y} W(X, Y, ix) x(X, Y, Z)
+// with the adjoint's W.  A wave owns 8 projections x 8 adjacent detector rows x 64 volume planes (lane = ray, 64 plane sums per lane) and
+// WALKS the volume one slab at a time: x slabs for the projections with |d_x| >= |d_y| (WALKY = 0: slab S = X, line L = Y), y slabs for
+// the others (WALKY = 1: S = Y, L = X).  The host sorts the projections into one list per (walk, NW), so no group straddles 45 degrees,
+// and pads a list with -1 where it jumps to another range of poses: eight rays of distant angles share no lines.
+//   1. lane = RAY: the <= 3 samples with |p_S - S| < 1 (exact 32.32 positions, the adjoint's tents) give the first line L0 and the weights
+//      W0 .. W(NW-1) of the nodes (S, L0 + k).  The samples lie in an open interval of p_S of length 2, i.e. of p_L of length
+//      2 |d_L / d_S|: <= 1 -> 3 nodes (NW = 3), else (|d_L| <= |d_S|, <= 3 samples, 2 |d_L| < 2) -> 4.  The table does not depend on z: the
+//      live waves of a work-group (z chunks of the same rays) share it through the adjoint's triple-buffered LDS table;
+//   2. lane = PLANE: the FGROWS lines from wave_min(L0) on are loaded (coalesced 256 B) one slab ahead and written to the wave's LDS rows;
+//   3. lane = RAY again: per four planes NW ds_read_b128 at row(lane) + immediate and 2 NW v_pk_fma_f32.
+// Rays of eight different projections drift apart with the distance from the rotation centre (tools/fwd_gather_model.py): a slab whose
+// lanes span more than FGROWS lines is done in WINDOWS of FGROWS lines advancing by FGROWS - NW + 1 (a lane's NW lines lie in exactly
+// one window); the first window rides the pipelined loads, the others (rare at FGROWS = 24) load on the spot.
+// The z lerp comes last, once per ray.  The sinogram is zero-filled by the caller: a wave stores its rays' 63 (tau != 0) or 64 values
+// with plain stores; the value that also needs the next chunk's first plane is completed by one atomic from each of the two waves
+// (0 + a + b = 0 + b + a: still the same bits on every run).
+// ------------------------------------------------------------------------------------------------
+#define FGROWS 24
+#define FG_NONE (1 << 29)          // "this lane has no line": above every real line index, far from integer overflow
+
+// The body of k_fwd_gather_flat for one list.  (A line's plane is addressed as slab base, wave-uniform 64-bit, + 32-bit byte offset: the host
+// checks that the volume is <= 4 GiB.)
+template <int NW, int WALKY>
+__device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs, const int *__restrict__ perm, int n_list, unsigned block_id,
+                                                     float *__restrict__ proj, const float *__restrict__ vol, const TomoGeomC &g,
+                                                     const unsigned char *__restrict__ vflags, const int *__restrict__ zshift,
+                                                     float (*rows)[FGROWS * GPITCH], float4 (*wtab)[GWAVES][64], int (*ltab)[GWAVES][64], int *wlive)
+{
+    static_assert(NW == 3 || NW == 4, "NW");
+    constexpr int SW = FGROWS - NW + 1;             // window advance
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nS = WALKY ? g.ny : g.nx, nL = WALKY ? g.nx : g.ny;
+    const uint32_t strideL4 = (WALKY ? (uint32_t)g.ny * (uint32_t)g.nz : (uint32_t)g.nz) * 4u;
+    const size_t strideS = WALKY ? (size_t)g.nz : (size_t)g.ny * g.nz;
+    // Work-group -> (projection group, row tile, z quad).  Work-groups are dealt to the 8 XCDs round-robin: XCD k takes the k-th eighth of
+    // the (group, tile) pairs of one z quad after the other, row tiles fastest -- its resident work-groups walk the same slabs of the same
+    // z quad at about the same time and find each other's lines in that XCD's L2.
+    const int npg = (n_list + 7) / 8, nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
+    const int m_all = npg * nrt, m8 = (m_all + 7) / 8;
+    const int slot_id = (int)(block_id >> 3), xcd = (int)(block_id & 7);
+    const int zq = slot_id / m8, tile = xcd * m8 + slot_id % m8;
+    if (tile >= m_all || zq >= nzq) return;                               // uniform over the work-group
+    const int pg = tile / nrt, rt = tile % nrt;
+    const int z0 = (zq * GWAVES + wv - *zshift) * 64;
+    bool zlive = z0 >= 0 && z0 < g.nz;
+    if (zlive) {
+        const int i = z0 + lane;
+        zlive = __builtin_amdgcn_ballot_w64(i < g.nz && vflags[i] != 0) != 0;
+    }
+    if (lane == 0) wlive[wv] = zlive ? 1 : 0;
+    __syncthreads();
+    int nl = 0, rk = 0;
+#pragma unroll
+    for (int w = 0; w < GWAVES; ++w) { nl += wlive[w]; rk += w < wv ? wlive[w] : 0; }
+    // (the dead waves leave; the live ones keep meeting at barriers: see k_adj_gather_flat for the hardware behaviour relied on)
+#if !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__) && defined(__HIP_DEVICE_COMPILE__)
+#error "k_fwd_gather_flat: divergent exit before barriers is only known to be safe on gfx9-family targets (s_barrier ignores ended waves)"
+#endif
+    if (!zlive) return;
+
+    // ---- the lane's ray
+    const int ipl = pg * 8 + (lane >> 3), ix = rt * 8 + (lane & 7);
+    const int pe = perm[min(ipl, n_list - 1)];                            // < 0: padding (the host starts a new group where the poses jump)
+    const bool ray_ok = ipl < n_list && ix < g.ndx && pe >= 0;
+    const GfC &c = cs[max(pe, 0)];
+    const int64_t fds = WALKY ? c.fdy : c.fdx, fdl = WALKY ? c.fdx : c.fdy;
+    const int64_t bs0 = (WALKY ? c.fp0y : c.fp0x) + (int64_t)ix * (WALKY ? c.fuy : c.fux);
+    const int64_t bl0 = (WALKY ? c.fp0x : c.fp0y) + (int64_t)ix * (WALKY ? c.fux : c.fuy);
+    const float bsf = (float)((double)bs0 * 2.3283064365386963e-10), inv_ds = (float)(4294967296.0 / (double)fds);
+    const int n_smp = ray_ok ? c.n : 0;
+    const float two_m32 = 2.3283064365386963e-10f;
+    const int Zl = z0 + lane;
+    const unsigned long long mz = __builtin_amdgcn_ballot_w64(Zl < g.nz);
+    const uint32_t o0 = (uint32_t)min(Zl, g.nz - 1) * 4u;
+    float *wrows = rows[wv];
+    f32x2 acc2[32];
+#pragma unroll
+    for (int p = 0; p < 32; ++p) acc2[p] = f32x2{0.f, 0.f};
+
+    // ---- 1. the table of this lane's ray for slab SX -> wtab / ltab[BUF][SLOT][lane]
+#define FG_TABLE(SX, BUF, SLOT)                                                                                            \
+    {                                                                                                                      \
+        float W[4] = {0.f, 0.f, 0.f, 0.f};                                                                                 \
+        int L0 = FG_NONE;                                                                                                  \
+        if ((SX) < nS) {                                                                                                   \
+            const float ta = ((float)((SX) - 1) - bsf) * inv_ds, tb = ((float)((SX) + 1) - bsf) * inv_ds;                  \
+            const int j0 = (int)ceilf(fminf(ta, tb) - 5e-3f);                                                              \
+            int64_t sx = bs0 + (int64_t)j0 * fds - ((int64_t)(SX) << 32), sl = bl0 + (int64_t)j0 * fdl;                    \
+            float wx[3], fl[3];                                                                                            \
+            int hl[3];                                                                                                     \
+            _Pragma("unroll") for (int mth = 0; mth < 3; ++mth) {                                                          \
+                const int hx = (int)(sx >> 32);                                                                            \
+                const float fx = (float)(unsigned)sx * two_m32;                                                            \
+                float w = hx == -1 ? fx : (hx == 0 ? 1.f - fx : 0.f);                                                      \
+                w = (unsigned)(j0 + mth) < (unsigned)n_smp ? w : 0.f;                                                      \
+                wx[mth] = w;                                                                                               \
+                hl[mth] = (int)(sl >> 32);                                                                                 \
+                fl[mth] = (float)(unsigned)sl * two_m32;                                                                   \
+                if (w > 0.f) L0 = min(L0, hl[mth]);                                                                        \
+                sx += fds; sl += fdl;                                                                                      \
+            }                                                                                                              \
+            _Pragma("unroll") for (int mth = 0; mth < 3; ++mth) {                                                          \
+                const int rel = hl[mth] - L0;                                                                              \
+                const float wl1 = wx[mth] * fl[mth], wl0 = wx[mth] - wl1;                                                  \
+                _Pragma("unroll") for (int k = 0; k < NW; ++k) W[k] += rel == k ? wl0 : (rel == k - 1 ? wl1 : 0.f);        \
+            }                                                                                                              \
+            bool any = false;                                                                                              \
+            _Pragma("unroll") for (int k = 0; k < NW; ++k) {                                                               \
+                W[k] = (unsigned)(L0 + k) < (unsigned)nL ? W[k] : 0.f;                                                     \
+                any |= W[k] != 0.f;                                                                                        \
+            }                                                                                                              \
+            if (!any) L0 = FG_NONE;                                                                                        \
+        }                                                                                                                  \
+        wtab[BUF][SLOT][lane] = make_float4(W[0], W[1], W[2], W[3]);                                                       \
+        ltab[BUF][SLOT][lane] = L0;                                                                                        \
+    }
+    // ---- 2a. fetch slab SX's table entry and ISSUE the loads of its first window (consumed one slab later)
+    float4 tn;
+    int Ln, Llo_n, Lhi_n, need_n = 0;
+    float yv[FGROWS];
+#define FG_SETUP(SX, BUF, SLOT)                                                                                            \
+    {                                                                                                                      \
+        tn = wtab[BUF][SLOT][lane];                                                                                        \
+        Ln = ltab[BUF][SLOT][lane];                                                                                        \
+        Llo_n = __builtin_amdgcn_readfirstlane(wave_min_i32(Ln));                                                          \
+        Lhi_n = __builtin_amdgcn_readfirstlane(wave_max_i32(Ln == FG_NONE ? -FG_NONE : Ln));                               \
+        if (Llo_n != FG_NONE) {                                                                                            \
+            const char *sbase = (const char *)(vol + (size_t)(SX) * strideS);                          /* wave-uniform */  \
+            const uint32_t lineoff = (uint32_t)min(max(Llo_n + min(lane, FGROWS - 1), 0), nL - 1) * strideL4;              \
+            /* only the lines the wave needs, in blocks of four (wave-uniform branches): 17 of the 24 on average */        \
+            need_n = min(Lhi_n - Llo_n + NW, FGROWS);                                                                      \
+            _Pragma("unroll") for (int r4 = 0; r4 < FGROWS; r4 += 4)                                                       \
+                if (r4 < need_n) {                                                                                         \
+                    _Pragma("unroll") for (int r = r4; r < r4 + 4; ++r)                                                    \
+                        yv[r] = *(const float *)(sbase + (o0 + (uint32_t)__builtin_amdgcn_readlane((int)lineoff, r)));     \
+                }                                                                                                          \
+        }                                                                                                                  \
+    }
+    // ---- 3. accumulate the lanes whose lines lie in the window that starts at line LBASE
+#define FG_ACCUM(LBASE)                                                                                                    \
+    {                                                                                                                      \
+        const int rel = L - (LBASE);                                                                                       \
+        const bool inw = (unsigned)rel < (unsigned)SW;                                                                     \
+        const int slot0 = inw ? rel : 0;                                                                                   \
+        const float W0 = inw ? t.x : 0.f, W1 = inw ? t.y : 0.f, W2 = inw ? t.z : 0.f, W3 = inw ? t.w : 0.f;                \
+        const float4 *q = (const float4 *)__builtin_assume_aligned(wrows + slot0 * GPITCH, 16);                            \
+        float4 n0 = q[0], n1 = q[GPITCH / 4], n2 = q[2 * GPITCH / 4], n3 = {0.f, 0.f, 0.f, 0.f};                           \
+        if (NW == 4) n3 = q[3 * GPITCH / 4];                                                                               \
+        _Pragma("unroll") for (int p = 0; p < 64; p += 4) {                                                                \
+            const float4 r0 = n0, r1 = n1, r2 = n2, r3 = n3;                                                               \
+            if (p + 4 < 64) {                                                                                              \
+                n0 = q[(p + 4) / 4]; n1 = q[(GPITCH + p + 4) / 4]; n2 = q[(2 * GPITCH + p + 4) / 4];                       \
+                if (NW == 4) n3 = q[(3 * GPITCH + p + 4) / 4];                                                             \
+            }                                                                                                              \
+            f32x2 a = W2 * f32x2{r2.x, r2.y} + (W1 * f32x2{r1.x, r1.y} + (W0 * f32x2{r0.x, r0.y} + acc2[p / 2]));          \
+            f32x2 b = W2 * f32x2{r2.z, r2.w} + (W1 * f32x2{r1.z, r1.w} + (W0 * f32x2{r0.z, r0.w} + acc2[p / 2 + 1]));      \
+            if (NW == 4) { a = W3 * f32x2{r3.x, r3.y} + a; b = W3 * f32x2{r3.z, r3.w} + b; }                               \
+            acc2[p / 2] = a; acc2[p / 2 + 1] = b;                                                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                                             \
+        }                                                                                                                  \
+    }
+    const int n_grp = (nS + nl - 1) / nl;
+    int buf = 0;
+    FG_TABLE(rk, 0, rk)
+    __syncthreads();
+    FG_SETUP(0, 0, 0)
+    for (int grp = 0; grp < n_grp; ++grp) {
+        const int nbuf = buf == 2 ? 0 : buf + 1;
+        if (grp + 1 < n_grp) FG_TABLE((grp + 1) * nl + rk, nbuf, rk)
+        __syncthreads();
+        const int g0 = grp * nl, g1 = min(nS, g0 + nl);
+        for (int sx = g0; sx < g1; ++sx) {
+            const float4 t = tn;
+            const int L = Ln, Llo = Llo_n, Lhi = Lhi_n, need = need_n;
+            const bool hit = Llo != FG_NONE;
+            // ---- 2b. the lines loaded one slab ago -> the wave's LDS rows (lane = plane; planes past the volume are zeros)
+            if (hit) {
+                // (rows past `need` keep stale values: a lane reads rows L - Llo .. + NW - 1 < need, one outside the window rows 0 .. NW - 1)
+                if (mz == ~0ull) {
+#pragma unroll
+                    for (int r4 = 0; r4 < FGROWS; r4 += 4)
+                        if (r4 < need) {
+#pragma unroll
+                            for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = yv[r];
+                        }
+                } else {
+#pragma unroll
+                    for (int r4 = 0; r4 < FGROWS; r4 += 4)
+                        if (r4 < need) {
+#pragma unroll
+                            for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = select_lanes(yv[r], mz);
+                        }
+                }
+            }
+            if (sx + 1 < g1) FG_SETUP(sx + 1, buf, sx + 1 - g0)
+            else if (sx + 1 < nS) FG_SETUP(sx + 1, nbuf, 0)
+            if (hit) {
+                FG_ACCUM(Llo)
+                // further windows: lines loaded on the spot, four at a time (the registers yv hold the next slab's loads in flight)
+                for (int lb = Llo + SW; lb <= Lhi; lb += SW) {
+                    const char *sbase = (const char *)(vol + (size_t)sx * strideS);
+                    for (int r = 0; r < FGROWS; r += 4) {
+                        float e[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            e[k] = *(const float *)(sbase + (o0 + (uint32_t)min(max(lb + r + k, 0), nL - 1) * strideL4));
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) wrows[(r + k) * GPITCH + lane] = select_lanes(e[k], mz);
+                    }
+                    FG_ACCUM(lb)
+                }
+            }
+        }
+        buf = nbuf;
+    }
+#undef FG_TABLE
+#undef FG_SETUP
+#undef FG_ACCUM
+    // ---- z lerp and store: ray iz = Z - zc takes (1 - tau) S(Z) + tau S(Z + 1); the lane's 64 values are consecutive floats of its sinogram row
+    if (!ray_ok) return;
+    const int iz0 = z0 - c.zc;
+    float *dst = proj + (size_t)c.slot * ((size_t)g.ndx * g.ndz) + (size_t)ix * g.ndz + iz0;
+    const float tau = c.tau;
+    if (tau == 0.f) {
+        if (iz0 >= 0 && iz0 + 64 <= g.ndz && ((iz0 | g.ndz) & 3) == 0) {
+#pragma unroll
+            for (int p = 0; p < 64; p += 4) *(float4 *)(dst + p) = make_float4(acc2[p / 2].x, acc2[p / 2].y, acc2[p / 2 + 1].x, acc2[p / 2 + 1].y);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 64; ++p)
+                if ((unsigned)(iz0 + p) < (unsigned)g.ndz) dst[p] = (p & 1) ? acc2[p / 2].y : acc2[p / 2].x;
+        }
+    } else {
+        const float wfz = 1.f - tau;
+#define FG_S(P) (((P) & 1) ? acc2[(P) / 2].y : acc2[(P) / 2].x)
+#pragma unroll
+        for (int p = 0; p < 63; ++p)
+            if ((unsigned)(iz0 + p) < (unsigned)g.ndz) dst[p] = wfz * FG_S(p) + tau * FG_S(p + 1);
+        // the two values shared with the neighbouring chunks' waves: one atomic from each side onto the caller's zero
+        if ((unsigned)(iz0 + 63) < (unsigned)g.ndz) atomicAdd(dst + 63, wfz * FG_S(63));
+        if ((unsigned)(iz0 - 1) < (unsigned)g.ndz) atomicAdd(dst - 1, tau * FG_S(0));
+#undef FG_S
+    }
+}
+
+// One launch per forward call: the work-groups of the four lists (x walk NW 3 | x walk NW 4 | y walk NW 3 | y walk NW 4, each 8 * m8 * nzq
+// work-groups, see the body) follow each other in the grid; a work-group finds its list from its index and runs that instantiation.
+__global__ __launch_bounds__(GWAVES * 64, 3) void k_fwd_gather_flat(const GfC *__restrict__ cs, const int *__restrict__ perm, int n0, int n1, int n2, int n3,
+                                                                    float *__restrict__ proj, const float *__restrict__ vol, TomoGeomC g,
+                                                                    const unsigned char *__restrict__ vflags, const int *__restrict__ zshift)
+{
+    __shared__ __attribute__((aligned(16))) float rows[GWAVES][FGROWS * GPITCH];
+    __shared__ float4 wtab[3][GWAVES][64];          // [group mod 3][slab of the group][ray] = W0 .. W3
+    __shared__ int ltab[3][GWAVES][64];             //                                      = L0
+    __shared__ int wlive[GWAVES];
+    const unsigned nrt = (unsigned)(g.ndx + 7) / 8, nzq = (unsigned)(g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
+    const unsigned w0 = 8u * ((((unsigned)n0 + 7) / 8 * nrt + 7) / 8) * nzq, w1 = 8u * ((((unsigned)n1 + 7) / 8 * nrt + 7) / 8) * nzq,
+                   w2 = 8u * ((((unsigned)n2 + 7) / 8 * nrt + 7) / 8) * nzq;
+    unsigned b = blockIdx.x;
+    if (b < w0) { fwd_gather_flat_body<3, 0>(cs, perm, n0, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    b -= w0;
+    if (b < w1) { fwd_gather_flat_body<4, 0>(cs, perm + n0, n1, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    b -= w1;
+    if (b < w2) { fwd_gather_flat_body<3, 1>(cs, perm + n0 + n1, n2, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    b -= w2;
+    fwd_gather_flat_body<4, 1>(cs, perm + n0 + n1 + n2, n3, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive);
+}

@@ -50,6 +50,11 @@ struct tomo_ctx {
     int tile_cache_zc_lo = 0, tile_cache_zc_hi = 0;   // range of the gather-eligible projections' integer z offsets (GfC::zc)
     double tile_cache_eb_max = 0.0;     // largest |m10| + |m11| of the gather-eligible projections staged (picks NJ)
     size_t tile_cache_gfoff = 0;
+    // the gather forward's projection lists (indices into the GfC array), staged behind the GfC array: [x walk NW 3 | x walk NW 4 | y walk NW 3 |
+    // y walk NW 4], each in pose order; tile_cache_fg_ok: every gather-eligible projection also meets the forward kernel's bounds
+    size_t tile_cache_fgoff = 0;
+    int tile_cache_fg_n[4] = {0, 0, 0, 0};
+    bool tile_cache_fg_ok = false;
     // reduction scratch
     double *d_red = nullptr;
     double *h_red = nullptr;
@@ -94,6 +99,7 @@ struct tomo_ctx {
     int tile_flat = 1;      // 1: untilted projections take the flat tile kernels
     int fused_update = 1;     // 1: tomo_adjoint_update folds the SIRT update into the gather adjoint's store when all its poses take that kernel; 0: it always declines (the caller's two calls)
     int adj_flat_gather = 1;  // 1: untilted unit lattices take the gather-form adjoint (k_adj_gather_flat) instead of the LDS-atomic flat kernel
+    int fwd_flat_gather = 1;  // 1 (default): whole-volume forward calls ALL of whose poses take the gather adjoint (three samples per row) take the gather-form forward (k_fwd_gather_flat: no atomics, same bits every run); other calls, and 0: k_fwd_flat_tab
     int fwd_flat_tab = 1;     // 1 (default): the flat forward with the sample table in LDS and the two images interleaved per plane (k_fwd_flat_tab); 0: the round-2 kernel (k_fwd_flat_z<2>: entries broadcast with v_readlane)
     int fwd_flat_wide = 0;    // 1: measurement variant of the flat forward -- 32 x 16 x 63 footprint, one image per work-group (k_fwd_flat_z<1, 32>); only in builds with -DTOMO_MEASUREMENT_VARIANTS
     int fwd_flat_ztiles = 2;  // 2: the flat forward processes two z-adjacent tiles per work-group (k_fwd_flat_z<2>); 1: one tile (k_tile_flat<true>)

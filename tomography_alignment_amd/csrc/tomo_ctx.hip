@@ -203,6 +203,7 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
 #endif
     }
     else if (!strcmp(key, "fwd_flat_tab")) ctx->fwd_flat_tab = value;
+    else if (!strcmp(key, "fwd_flat_gather")) ctx->fwd_flat_gather = value;
     else if (!strcmp(key, "reuse_staged_volume")) ctx->reuse_staged = value;
     else if (!strcmp(key, "reuse_sino_flags")) ctx->reuse_sino_flags = value;
     else if (!strcmp(key, "roctx")) {

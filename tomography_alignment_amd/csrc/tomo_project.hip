@@ -140,10 +140,13 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
     }
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t gf_off = (sizeof(AdjC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;
-    int rc = tomo_ensure_stage(ctx, gf_off + sizeof(GfC) * (size_t)std::max(n_proj, 1));
+    const size_t fg_off = (gf_off + sizeof(GfC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;      // the gather forward's projection lists (+ padding)
+    int rc = tomo_ensure_stage(ctx, fg_off + sizeof(int) * 8 * ((size_t)std::max(n_proj, 1) + 4));
     if (rc) return rc;
     std::vector<AdjC> gath, flat, gen;
     std::vector<GfC> gfc;
+    std::vector<int> fg_list[4];                   // k_fwd_gather_flat: [2 * walk + (NW == 4)] -> indices into gfc, pose order
+    bool fg_ok = true;
     double eb_max = 0.0;
     int zc_lo = INT_MAX, zc_hi = INT_MIN;          // range of the gather projections' integer z offsets (k_sino_zflags / zlive in the kernel)
     for (int i = 0; i < n_proj; ++i) {
@@ -186,6 +189,18 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
             q.zc = (int32_t)(a.fp0[2] >> 32);                                       // floor of the constant z offset
             q.tau = (float)((double)(uint32_t)(a.fp0[2] & 0xffffffffll) / 4294967296.0);
             q.n = a.n; q.slot = a.slot;
+            // the gather forward walks the slabs of the axis the rays mostly follow (|d_S| >= |d_L|).  Its three candidate samples per slab
+            // need 2 / |d_S| + slack < 3, its NW nodes per slab 2 |d_L| <= |d_S| (NW = 3) or |d_L| < 1 (NW = 4): kernels_tile_gather.hip.h
+            {
+                const bool walky = llabs(q.fdx) < llabs(q.fdy);
+                const int64_t ads = llabs(walky ? q.fdy : q.fdx), adl = llabs(walky ? q.fdx : q.fdy);
+                fg_ok = fg_ok && (double)ads >= 0.67 * 4294967296.0 && (double)adl < 0.999 * 4294967296.0;
+                std::vector<int> &fl = fg_list[2 * (walky ? 1 : 0) + (2 * adl <= ads ? 0 : 1)];
+                // groups are eight consecutive entries: where the list jumps to another range of poses, pad to the next group (-1 = no ray)
+                if (!fl.empty() && fl.back() != (int)gfc.size() - 1)
+                    while (fl.size() % 8) fl.push_back(-1);
+                fl.push_back((int)gfc.size());
+            }
             gath.push_back(a);
             gfc.push_back(q);
             eb_max = std::max(eb_max, eb);
@@ -201,10 +216,18 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
     for (const AdjC &a : gen) h[k++] = a;
     GfC *hg = (GfC *)((char *)ctx->h_stage + gf_off);
     for (size_t i = 0; i < gfc.size(); ++i) hg[i] = gfc[i];
+    int *hf = (int *)((char *)ctx->h_stage + fg_off);
+    size_t fg_total = 0;
+    for (int l = 0; l < 4; ++l) {
+        for (int v : fg_list[l]) hf[fg_total++] = v;
+        ctx->tile_cache_fg_n[l] = (int)fg_list[l].size();
+    }
+    ctx->tile_cache_fgoff = fg_off;
+    ctx->tile_cache_fg_ok = fg_ok;
     *n_flat = (int)(gath.size() + flat.size());
     if (n_gather) *n_gather = (int)gath.size();
     if (d_gfc) *d_gfc = (const GfC *)((char *)ctx->d_stage + gf_off);
-    if (n_proj) TOMO_HIP(ctx, hipMemcpyAsync(ctx->d_stage, h, gf_off + sizeof(GfC) * gfc.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (n_proj) TOMO_HIP(ctx, hipMemcpyAsync(ctx->d_stage, h, fg_off + sizeof(int) * fg_total, hipMemcpyHostToDevice, ctx->stream));
     *all_ok = true;
     ctx->tile_cache_poses.assign(h_poses, h_poses + n_pose_doubles);
     ctx->tile_cache_opts = opts;
@@ -224,7 +247,8 @@ static inline dim3 tile_grid(const TomoGeomC &g, int tz = ATZ) { return dim3((g.
 
 // Tile forward restricted to the x tile columns [xt0, xt1): ADDS the partial ray sums of those tiles into d_proj (the caller
 // zeroes it).  *done = false when the poses do not qualify for the tile kernels (nothing launched).
-static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_vol, float *d_proj, int xt0, int xt1, bool *done)
+static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const float *d_vol, float *d_proj, int xt0, int xt1, bool *done,
+                         bool whole = false)
 {
     const TomoGeomC &g = ctx->g;
     *done = false;
@@ -245,6 +269,36 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     const AdjC *d_c = (const AdjC *)ctx->d_stage;
     ctx->fwd_blk_flat_ints = 0;
     ctx->zf_src = nullptr;                  // the block lists below overwrite the back-projection's cached plane flags in d_blk
+    // Gather-form forward (option "fwd_flat_gather"): whole-volume calls ALL of whose poses take the gather adjoint with three samples per
+    // row (step >= 0.95 voxel) and meet the kernel's bounds, on a volume its 32-bit line offsets can address.  Everything else -- the x-slab
+    // calls of the sharded solvers included -- keeps k_fwd_flat_tab below.  nx, ny <= 8192: the kernel finds a slab's first candidate sample
+    // from float32 positions (|p| about the plane's diagonal, ulp 1e-3 there) with a slack of 5e-3; wider planes would bring the rounding up
+    // to the slack.
+    if (whole && ctx->fwd_flat_gather && ctx->tile_cache_ngather == n_proj && ctx->tile_cache_fg_ok && ctx->tile_cache_eb_max < 1.49 &&
+        std::max(g.nx, g.ny) <= 8192 && (unsigned long long)g.nx * g.ny * g.nz * 4ull <= (1ull << 32)) {
+        const size_t zf_ints = ((size_t)g.nz + 3) / 4;
+        rc = tomo_ensure_blk(ctx, zf_ints + 1);
+        if (rc) return rc;
+        unsigned char *d_vf = (unsigned char *)ctx->d_blk;
+        int *d_shift = ctx->d_blk + zf_ints;
+        // which volume planes hold anything (the volume is [nx * ny] lines of nz), and the z chunk grouping that starts at the first live chunk
+        TOMO_HIP(ctx, hipMemsetAsync(d_vf, 0, (size_t)g.nz, ctx->stream));
+        const long long n_lines = (long long)g.nx * g.ny;
+        TOMO_LAUNCH(ctx, "k_fwd_live", k_sino_zflags, dim3((unsigned)((g.nz + 255) / 256), (unsigned)std::min<long long>(n_lines, 4096)), dim3(256), 0,
+                    d_vol, n_lines, g.nz, d_vf);
+        TOMO_LAUNCH(ctx, "k_fwd_live", k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)d_vf, g.nz, g.nz, 0, -1, d_shift);
+        const GfC *d_gfc = (const GfC *)((char *)ctx->d_stage + ctx->tile_cache_gfoff);
+        const int *d_perm = (const int *)((char *)ctx->d_stage + ctx->tile_cache_fgoff);
+        const int nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
+        // one launch: the four lists' work-groups follow each other in the grid (an empty list has none)
+        const int *fn = ctx->tile_cache_fg_n;
+        long long n_wg = 0;
+        for (int l = 0; l < 4; ++l) n_wg += 8 * (((long long)((fn[l] + 7) / 8) * nrt + 7) / 8) * nzq;
+        if (n_wg >= ((long long)1 << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather forward: grid too large");
+        TOMO_LAUNCH(ctx, "k_fwd_tile_flat", k_fwd_gather_flat, dim3((unsigned)n_wg), dim3(GWAVES * 64), 0, d_gfc, d_perm, fn[0], fn[1], fn[2], fn[3], d_proj, d_vol, g,
+                    (const unsigned char *)d_vf, (const int *)d_shift);
+        return TOMO_OK;
+    }
     if (n_flat > 0) {
         dim3 fg = tile_grid(g, FTZ);
         fg.z = grid.z;
@@ -305,7 +359,7 @@ extern "C" int tomo_forward(tomo_ctx *ctx, const double *h_poses, int n_proj, co
         // the tile kernels add into d_proj: zero it first; if the poses turn out not to qualify, the ray-driven path overwrites anyway
         TOMO_HIP(ctx, hipMemsetAsync(d_proj, 0, n_det * (size_t)n_proj * sizeof(float), ctx->stream));
         bool done = false;
-        rc = forward_tiles(ctx, h_poses, n_proj, d_vol, d_proj, 0, INT_MAX, &done);
+        rc = forward_tiles(ctx, h_poses, n_proj, d_vol, d_proj, 0, INT_MAX, &done, true);
         if (rc) return rc;
         if (done) return TOMO_OK;
     }

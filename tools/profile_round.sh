@@ -24,6 +24,7 @@ if [ -z "$SKIP_STATS" ]; then
     timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/${tag}_stats -o run -- python3 $R/bench.py --full --no-cpu-baseline --detail $RAW/${tag}_bench_under_rocprof_detail.json > $RAW/${tag}_bench_under_rocprof.json 2> $RAW/${tag}_stats.err || { echo "stats pass failed"; tail -5 $RAW/${tag}_stats.err; exit 1; }
     echo "stats pass done"
 fi
+STATS_OF="stats: bench.py --full; "; [ -n "$SKIP_STATS" ] && STATS_OF=""       # a call without the stats pass does not claim one
 SQ1="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE"
 SQ2="SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_BUSY_CYCLES"
 TA="TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum"
@@ -40,7 +41,7 @@ for leg in $legs; do
                 echo "gradient $sub: $pass pass done"
             done
             cd $R
-            python3 tools/summarise_rocprof.py $t $RAW/${tag}_stats $RAW/${t}_fetch $RAW/${t}_write --which last --workload "config 5: 512^3 x 720 poses, alignment gradient, $sub (stats: bench.py --full; PMC passes: bench.py --only-align $sub, last dispatch of each kernel)" --key C5_N512_P720_G1_$sub --out $OUT > /dev/null
+            python3 tools/summarise_rocprof.py $t $RAW/${tag}_stats $RAW/${t}_fetch $RAW/${t}_write --which last --workload "config 5: 512^3 x 720 poses, alignment gradient, $sub (${STATS_OF}PMC passes: bench.py --only-align $sub, last dispatch of each kernel)" --key C5_N512_P720_G1_$sub --out $OUT > /dev/null
             python3 tools/summarise_sq.py $t C5_N512_P720_G1_$sub gpurun_out/${t}_sq1 gpurun_out/${t}_sq2 gpurun_out/${t}_ta --workload "bench.py --only-align $sub" --out $OUT > /dev/null
         done
         continue
@@ -61,7 +62,7 @@ for leg in $legs; do
         echo "$what: $pass pass done"
     done
     cd $R
-    python3 tools/summarise_rocprof.py $t $RAW/${tag}_stats $RAW/${t}_fetch $RAW/${t}_write --which last --workload "N=1024 n_proj=1024 n_gpus=1, $what (stats: bench.py --full; PMC passes: bench.py $SIDE $flag, last dispatch of each kernel)" --key N1024_A1024_G1$sfx --out $OUT > /dev/null
+    python3 tools/summarise_rocprof.py $t $RAW/${tag}_stats $RAW/${t}_fetch $RAW/${t}_write --which last --workload "N=1024 n_proj=1024 n_gpus=1, $what (${STATS_OF}PMC passes: bench.py $SIDE $flag, last dispatch of each kernel)" --key N1024_A1024_G1$sfx --out $OUT > /dev/null
     python3 tools/summarise_sq.py $t N1024_A1024_G1$sfx gpurun_out/${t}_sq1 gpurun_out/${t}_sq2 --workload "bench.py $SIDE $flag" --out $OUT > /dev/null
 done
 cd $R

@@ -26,7 +26,9 @@ ALIAS = {"k_adj_gather_flat<3>": "k_adj_gather_flat", "k_adj_gather_flat<6>": "k
          "k_adj_gather_flat<3, 0>": "k_adj_gather_flat", "k_adj_gather_flat<6, 0>": "k_adj_gather_flat", "k_adj_gather_flat<3, 1>": "k_adj_gather_flat",
          "k_adj_gather_flat<6, 1>": "k_adj_gather_flat", "k_residual_scale_flags": "k_residual_scale",
          "k_tile_flat<true>": "k_fwd_tile_flat", "k_fwd_flat_z<2>": "k_fwd_tile_flat", "k_fwd_flat_z<1>": "k_fwd_tile_flat", "k_fwd_flat_z<2, 16>": "k_fwd_tile_flat", "k_fwd_flat_z<1, 16>": "k_fwd_tile_flat",
-         "k_fwd_flat_z<1, 32>": "k_fwd_tile_flat", "k_fwd_flat_tab": "k_fwd_tile_flat", "k_tile_flat<false>": "k_adj_tile_flat", "k_tile<true>": "k_fwd_tile",
+         "k_fwd_flat_z<1, 32>": "k_fwd_tile_flat", "k_fwd_flat_tab": "k_fwd_tile_flat",
+         # the gather-form flat forward (option fwd_flat_gather)
+         "k_fwd_gather_flat": "k_fwd_tile_flat", "k_tile_flat<false>": "k_adj_tile_flat", "k_tile<true>": "k_fwd_tile",
          "k_tile<false>": "k_adj_tile", "k_proj_grad<true>": "k_cost_grad(v1)", "k_proj_grad<false>": "k_proj_grad(v1)",
          "k_proj_grad_v2<true>": "k_cost_grad(v2)", "k_proj_grad_v2<false>": "k_proj_grad(v2)",
          "k_proj_grad_v3<true>": "k_cost_grad(v3)", "k_proj_grad_v3<false>": "k_proj_grad(v3)"}
@@ -94,9 +96,10 @@ def main():
     stats_csv = find(a.stats_dir, "*kernel_stats.csv")
     rows = list(csv.DictReader(open(stats_csv))) if stats_csv else []       # (a PMC-only call of a round has no stats pass of its own)
     fetch, write = pmc(a.fetch_dir, "FETCH_SIZE"), pmc(a.write_dir, "WRITE_SIZE")
-    lines = ["# rocprofv3 summary `%s`" % a.tag, "", "workload: %s" % a.workload, "",
-             "## `rocprofv3 --kernel-trace --stats -- python3 bench.py ...`", "",
-             "| kernel | calls | avg ms | total ms | % |", "|---|---|---|---|---|"]
+    lines = ["# rocprofv3 summary `%s`" % a.tag, "", "workload: %s" % a.workload]
+    if rows:
+        lines += ["", "## `rocprofv3 --kernel-trace --stats -- python3 bench.py ...`", "",
+                  "| kernel | calls | avg ms | total ms | % |", "|---|---|---|---|---|"]
     for r in rows:
         lines.append("| `%s` | %s | %.3f | %.1f | %s |" % (short(r["Name"]), r["Calls"], float(r["AverageNs"]) / 1e6,
                                                           float(r["TotalDurationNs"]) / 1e6, r["Percentage"]))
