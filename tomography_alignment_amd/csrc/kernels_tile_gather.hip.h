@@ -35,6 +35,28 @@
 #define GPY 12
 #endif
 
+// wave_min_i32 / wave_max_i32 (kernels_ray.hip.h) for a wave whose 64 lanes are all active: the lane exchange is written so that it becomes
+// the DPP operand of the v_min / v_max itself (every lane of these patterns reads a lane of its own row, so bound_ctrl and the old value
+// never apply) -- 4 VALU instructions where the plain form compiles to 12 (a copy and a v_mov_dpp in front of each v_min).
+#define G_DPP(V, CTRL) __builtin_amdgcn_update_dpp(0, (V), (CTRL), 0xf, 0xf, true)
+__device__ __forceinline__ int gwave_min_i32(int v)
+{
+    v = min(v, G_DPP(v, 0xB1));         // quad_perm [1,0,3,2]
+    v = min(v, G_DPP(v, 0x4E));         // quad_perm [2,3,0,1]
+    v = min(v, G_DPP(v, 0x141));        // row_half_mirror
+    v = min(v, G_DPP(v, 0x140));        // row_mirror
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+__device__ __forceinline__ int gwave_max_i32(int v)
+{
+    v = max(v, G_DPP(v, 0xB1));
+    v = max(v, G_DPP(v, 0x4E));
+    v = max(v, G_DPP(v, 0x141));
+    v = max(v, G_DPP(v, 0x140));
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+#undef G_DPP
+
 struct GfC {
     int64_t fp0x, fp0y, fux, fuy, fdx, fdy;   // x, y of the 32.32 lattice  p = fp0 + ix fu + j fd
     float m00, m01, m10, m11;                 // (ix, j) = M ((x, y) - p0)
@@ -261,50 +283,84 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         }                                                                                                                  \
         wtab[BUF][SLOT][lane] = t4;                                                                                        \
     }
-    // ---- 2a. fetch projection IPX's table entry and ISSUE the 15 loads of the sinogram rows the tile can touch: rows
-    //          ix_lo .. ix_lo+13 at this lane's PLANE (coalesced) plus one gather of their values one plane below the wave's
-    //          first, from clamped -- always valid -- addresses, masked when used.  Straight-line on purpose (with a branch per
-    //          row every row waited for its own round trip to memory).  The loads are consumed one projection later: they fly
-    //          while the previous projection accumulates.
-    float4 tn;
-    int ix_lo_n;
-    float y0v[GROWS], yedge = 0.f;                                         // yedge: lane r holds row r one plane below the wave's first
+    // ---- 2. projection IPX's sinogram rows.  G_SETUP fetches the table entry and ISSUES the 15 loads of the rows the tile can touch: rows
+    //         ix_lo .. ix_lo+13 at this lane's PLANE (coalesced) plus one gather of their values one plane below the wave's
+    //         first, from clamped -- always valid -- addresses, masked when used.  Straight-line on purpose (with a branch per
+    //         row every row waited for its own round trip to memory).  G_STAGE z-lerps them into the wave's LDS rows.  The projection
+    //         before IPX accumulates between the two: the loads fly meanwhile, and the registers y0v[] live only from the one to the other,
+    //         inside one pass of the projection loop (nothing of them is carried round the loop: no copies at the hand-over).
+    //         Addresses: a buffer resource over the projection's sinogram (its base is wave-uniform); the lane's plane offset is the
+    //         vector offset, the row's byte offset the SCALAR offset of the load.  The 14 clamped row offsets are computed by 14 LANES
+    //         at once and handed out with v_readlane: per row one readlane, no add, no scalar clamp / multiply / 64-bit add (the kernel
+    //         once issued 335 SALU instructions per projection and wave against 290 VALU -- the scalar unit, one per CU, was the limit).
+    //         Every offset is clamped to the sinogram here; the resource's own range check is never relied on.
 #ifdef TOMO_ABLATE_GATHER_LOADS     /* measurement builds only: the kernel without its sinogram loads (wrong sums) */
-#define G_ROW_LOAD(P) __int_as_float(0x3f800000 + (int)(size_t)(P))
+#define G_ROW_LOAD(RS, VOFF, SOFF) __int_as_float(0x3f800000 + (int)((VOFF) + (SOFF)))
 #else
-#define G_ROW_LOAD(P) (*(const float *)(P))
+#define G_ROW_LOAD(RS, VOFF, SOFF) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32((RS), (VOFF), (SOFF), 0))
 #endif
+    const uint32_t det_bytes = (uint32_t)min((unsigned long long)n_det * 4ull, 0xffffffffull);      // (< 4 GiB, as for pitch4 above: all of it)
 #define G_SETUP(IPX, BUF, SLOT)                                                                                            \
     {                                                                                                                      \
         tn = wtab[BUF][SLOT][lane];                                                                                        \
         const int i0s = __builtin_bit_cast(int, tn.x);                                                                     \
-        ix_lo_n = __builtin_amdgcn_readfirstlane(wave_min_i32(i0s));                                                       \
-        if (zlive) {                                                                                                       \
-            const GfC &cn = cs[IPX];                                                                                       \
-            const int iz0 = Zl - cn.zc;                                                                                    \
-            const char *srow = (const char *)(proj + (size_t)cn.slot * n_det);                          /* wave-uniform */ \
-            /* addresses: the projection's base is a wave-uniform SGPR pair (saddr); the 32-bit voffset is the lane's plane     */ \
-            /* offset + the row's byte offset.  The 14 clamped row offsets are computed by 14 LANES at once and handed out    */ \
-            /* with v_readlane: per row one readlane and one add, no scalar clamp / multiply / 64-bit add (the kernel issued */ \
-            /* 335 SALU instructions per projection and wave against 290 VALU -- the scalar unit, one per CU, was the limit) */ \
-            const uint32_t o0 = (uint32_t)min(max(iz0, 0), g.ndz - 1) * 4u;                                                 \
-            const uint32_t rowoff = (uint32_t)min(max(ix_lo_n + min(lane, GROWS - 1), 0), g.ndx - 1) * pitch4;              \
-            _Pragma("unroll") for (int r = 0; r < GROWS; ++r)                                                              \
-                y0v[r] = G_ROW_LOAD(srow + (o0 + (uint32_t)__builtin_amdgcn_readlane((int)rowoff, r)));                     \
-            /* the plane below (iz0 - 1) is the neighbouring lane's value (DPP shift when used); lane 0 has no neighbour: one  */ \
-            /* more load, lane r fetching row r at the wave's first plane - 1 -- 15 loads per projection instead of 28      */ \
-            if (cn.tau != 0.f) {                                            /* (tau = 0: the plane below is never used) */ \
-                const uint32_t oe = (uint32_t)min(max(z0 - cn.zc - 1, 0), g.ndz - 1) * 4u;                                  \
-                yedge = *(const float *)(srow + (rowoff + oe));                                                            \
-            }                                                                                                              \
+        ix_lo_n = __builtin_amdgcn_readfirstlane(gwave_min_i32(i0s));                                                      \
+        const GfC &cn = cs[IPX];                                                                                           \
+        const int iz0 = Zl - cn.zc;                                                                                        \
+        const __amdgpu_buffer_rsrc_t srs =                                                                                 \
+            __builtin_amdgcn_make_buffer_rsrc((void *)(proj + (size_t)cn.slot * n_det), 0, (int)det_bytes, 0x00020000);    \
+        const uint32_t o0 = (uint32_t)min(max(iz0, 0), g.ndz - 1) * 4u;                                                    \
+        const uint32_t rowoff = (uint32_t)min(max(ix_lo_n + min(lane, GROWS - 1), 0), g.ndx - 1) * pitch4;                 \
+        _Pragma("unroll") for (int r = 0; r < GROWS; ++r)                                                                  \
+            y0v[r] = G_ROW_LOAD(srs, o0, (uint32_t)__builtin_amdgcn_readlane((int)rowoff, r));                             \
+        /* the plane below (iz0 - 1) is the neighbouring lane's value (DPP shift when used); lane 0 has no neighbour: one  */ \
+        /* more load, lane r fetching row r at the wave's first plane - 1 -- 15 loads per projection instead of 28      */ \
+        if (cn.tau != 0.f) {                                                /* (tau = 0: the plane below is never used) */ \
+            const uint32_t oe = (uint32_t)min(max(z0 - cn.zc - 1, 0), g.ndz - 1) * 4u;                                     \
+            yedge = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, rowoff + oe, 0, 0));               \
         }                                                                                                                  \
     }
+#define G_ZLERP(MASKED, TAU)                                                                                                      \
+    _Pragma("unroll") for (int r = 0; r < GROWS; ++r) {                                                                           \
+        float y1 = dpp_shr1_f(y0v[r]);                                            /* lane l <- lane l - 1: y(ix, iz0 - 1) for l >= 1 */ \
+        asm("v_writelane_b32 %0, %1, 0" : "+v"(y1) : "s"(__builtin_amdgcn_readlane(__builtin_bit_cast(int, yedge), r)));   /* lane 0 <- row r's edge value */ \
+        const float a0 = (MASKED) ? select_lanes(y0v[r], m0) : y0v[r], a1 = (MASKED) ? select_lanes(y1, m1) : y1;                \
+        wrows[r * GPITCH + lane] = fmaf((TAU), a1 - a0, a0);                                                                      \
+    }
+    // (no per-row validity test: a row outside the detector was loaded from a clamped, valid address and every lane's
+    //  weight for it is 0 (G_TABLE); rows past the last one a lane needs are never read)
+#define G_STAGE(IPX)                                                                                                       \
+    {                                                                                                                      \
+        const GfC &cn = cs[IPX];                                                                                           \
+        const int iz0 = Zl - cn.zc, iz1 = iz0 - 1;                                                                         \
+        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(iz0 >= 0) & __builtin_amdgcn_ballot_w64(iz0 < g.ndz);    \
+        const unsigned long long m1 = __builtin_amdgcn_ballot_w64(iz1 >= 0) & __builtin_amdgcn_ballot_w64(iz1 < g.ndz);    \
+        if (cn.tau == 0.f) {            /* samples sit exactly on detector rows (integer z shift: the nominal geometry before */ \
+            if (m0 == ~0ull) {          /* alignment): Yz = y -- no neighbour plane, no lerp (fma(0, a1 - a0, a0) = a0)      */ \
+                _Pragma("unroll") for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = y0v[r];    /* all 64 planes on the detector: no select either */ \
+            } else {                                                                                                       \
+                _Pragma("unroll") for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = select_lanes(y0v[r], m0);     \
+            }                                                                                                              \
+        }                                                                                                                  \
+        else if ((m0 & m1) == ~0ull) { G_ZLERP(false, cn.tau) }     /* all 64 planes and their lower neighbours on the detector: the usual case */ \
+        else { G_ZLERP(true, cn.tau) }                                                                                     \
+    }
+#define G_HIT(T) (__any((T).y != 0.f || (T).z != 0.f || (T).w != 0.f))      /* else this projection's rays miss the tile */
     const int n_grp = (n_proj + nl - 1) / nl;
     int buf = 0;                                                        // table buffer of the current group (three in rotation)
+    float4 t = {0.f, 0.f, 0.f, 0.f};                                    // the projection whose rows are in the LDS rows
+    int ix_lo = 0;
+    bool hit = false;
     if (n_grp > 0) {
         G_TABLE(rk, 0, rk)                                              // group 0
         __syncthreads();
+        float4 tn;
+        int ix_lo_n;
+        float y0v[GROWS], yedge = 0.f;                                  // yedge: lane r holds row r one plane below the wave's first
         G_SETUP(0, 0, 0)
+        hit = G_HIT(tn);
+        if (hit) G_STAGE(0)
+        t = tn; ix_lo = ix_lo_n;
     }
     for (int grp = 0; grp < n_grp; ++grp) {
         const int nbuf = buf == 2 ? 0 : buf + 1;
@@ -312,43 +368,20 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         __syncthreads();                                                // ... and everybody is done with group grp - 1's buffer
         const int g0 = grp * nl, g1 = min(n_proj, g0 + nl);
         for (int ip = g0; ip < g1; ++ip) {
-            const GfC &c = cs[ip];
-            const float4 t = tn;
-            const int i0 = __builtin_bit_cast(int, t.x), ix_lo = ix_lo_n;
-            const float W0 = t.y, W1 = t.z, W2 = t.w;
-            const bool hit = zlive && __any(W0 != 0.f || W1 != 0.f || W2 != 0.f);   // else this projection's rays miss the tile
-            // ---- 2b. z-lerp the rows loaded one projection ago into the wave's LDS rows (lane = plane)
-            if (hit) {
-                const int iz0 = Zl - c.zc, iz1 = iz0 - 1;
-                // (no per-row validity test: a row outside the detector was loaded from a clamped, valid address and every lane's
-                //  weight for it is 0 (G_TABLE); rows past the last one a lane needs are never read)
-                const unsigned long long m0 = __builtin_amdgcn_ballot_w64(iz0 >= 0) & __builtin_amdgcn_ballot_w64(iz0 < g.ndz);
-                const unsigned long long m1 = __builtin_amdgcn_ballot_w64(iz1 >= 0) & __builtin_amdgcn_ballot_w64(iz1 < g.ndz);
-#define G_ZLERP(MASKED)                                                                                                           \
-    _Pragma("unroll") for (int r = 0; r < GROWS; ++r) {                                                                           \
-        float y1 = dpp_shr1_f(y0v[r]);                                            /* lane l <- lane l - 1: y(ix, iz0 - 1) for l >= 1 */ \
-        asm("v_writelane_b32 %0, %1, 0" : "+v"(y1) : "s"(__builtin_amdgcn_readlane(__builtin_bit_cast(int, yedge), r)));   /* lane 0 <- row r's edge value */ \
-        const float a0 = (MASKED) ? select_lanes(y0v[r], m0) : y0v[r], a1 = (MASKED) ? select_lanes(y1, m1) : y1;                \
-        wrows[r * GPITCH + lane] = fmaf(c.tau, a1 - a0, a0);                                                                      \
-    }
-                if (c.tau == 0.f) {                                         // samples sit exactly on detector rows (integer z shift: the nominal geometry
-                    if (m0 == ~0ull) {                                      //  before alignment): Yz = y -- no neighbour plane, no lerp (fma(0, a1 - a0, a0) = a0)
-#pragma unroll
-                        for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = y0v[r];            // all 64 planes on the detector: no select either
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = select_lanes(y0v[r], m0);
-                    }
-                }
-                else if ((m0 & m1) == ~0ull) { G_ZLERP(false) }             // all 64 planes and their lower neighbours on the detector: the usual case
-                else { G_ZLERP(true) }
-#undef G_ZLERP
+            float4 tn = t;
+            int ix_lo_n = ix_lo;
+            float y0v[GROWS], yedge = 0.f;
+            const bool more = ip + 1 < n_proj;
+            if (more) {
+                const bool same = ip + 1 < g1;                              // else the next group's table, already published
+                const int sbuf = same ? buf : nbuf, sslot = same ? ip + 1 - g0 : 0;
+                G_SETUP(ip + 1, sbuf, sslot)
             }
-            if (ip + 1 < g1) G_SETUP(ip + 1, buf, ip + 1 - g0)
-            else if (ip + 1 < n_proj) G_SETUP(ip + 1, nbuf, 0)          // the next group's table is already published
             // ---- 3. accumulate, lane = column: its three rows start at slot0; plane p is an immediate offset.  The LDS rows were
             //         written by this same wave (LDS operations of a wave execute in order), no other wave touches them.
             if (hit) {
+                const int i0 = __builtin_bit_cast(int, t.x);
+                const float W0 = t.y, W1 = t.z, W2 = t.w;
                 const int slot0 = min(max(i0 - ix_lo, 0), GROWS - 3);       // an 8 x 8 column tile touches <= 13 rows (7 (|cos| + |sin|) + 3); clamped for safety
                 // plane QUADS with ds_read_b128 (round 2): 256 B/clk where ds_read_b32 moves 128 B/clk -- the kernel was LDS-bound
                 // (SQ_LDS_IDX_ACTIVE = 0.79 of its cycles) on 3 x 64 dword reads per projection
@@ -366,11 +399,19 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
                     __builtin_amdgcn_sched_barrier(0);                       // keeps the reads from all being hoisted to the top (192 temporaries)
                 }
             }
+            // ---- 2b. the rows loaded above, z-lerped into the wave's LDS rows (lane = plane)
+            hit = more && G_HIT(tn);
+            if (hit) G_STAGE(ip + 1)
+            t = tn; ix_lo = ix_lo_n;
         }
         buf = nbuf;
     }
 #undef G_TABLE
+#undef G_ROW_LOAD
 #undef G_SETUP
+#undef G_ZLERP
+#undef G_STAGE
+#undef G_HIT
     // ---- store: the lane's column is 64 consecutive floats of the volume
     if (UPD) {
         if (X < xe && Y < g.ny) {
@@ -516,25 +557,52 @@ __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs,
         wtab[BUF][SLOT][lane] = make_float4(W[0], W[1], W[2], W[3]);                                                       \
         ltab[BUF][SLOT][lane] = L0;                                                                                        \
     }
-    // ---- 2a. fetch slab SX's table entry and ISSUE the loads of its first window (consumed one slab later)
-    float4 tn;
-    int Ln, Llo_n, Lhi_n, need_n = 0;
-    float yv[FGROWS];
+    // ---- 2. slab SX's first window.  FG_SETUP fetches the table entry and ISSUES the loads of the lines (lane = plane); FG_STAGE writes them to the
+    //         wave's LDS rows.  The slab before SX accumulates between the two: the loads fly meanwhile, and the registers yv[] live only from
+    //         the one to the other, inside one pass of the slab loop -- nothing of them is carried round the loop, so a block of four that is
+    //         not loaded holds nothing (no "old value" to keep) and a loaded one is stored from the registers it arrived in.
+    //         Addresses: a buffer resource over the SLAB (its base is wave-uniform; a slab's lines end slab_bytes behind it: an x slab is
+    //         ny lines in a row, a y slab reaches from its first line to the last x's); the lane's plane offset is the vector offset, the
+    //         line's byte offset (clamped line x line pitch, computed by FGROWS lanes at once and handed out with v_readlane) is the SCALAR
+    //         offset of the load -- no add per line.  Every offset is clamped to the slab here; the resource's own range check is never
+    //         relied on.  (Not one resource over the volume: a resource holds at most 2^32 - 1 bytes, and the last voxel of a volume of
+    //         exactly 4 GiB, which the host admits, would lie outside it and read as zero.)
+    const uint32_t slab_bytes = (uint32_t)min(WALKY ? (unsigned long long)(g.nx - 1) * strideL4 + (unsigned long long)g.nz * 4ull
+                                                    : (unsigned long long)g.ny * g.nz * 4ull, 0xffffffffull);
+#define FG_SLAB_RSRC(SX) __builtin_amdgcn_make_buffer_rsrc((void *)(vol + (size_t)(SX) * strideS), 0, (int)slab_bytes, 0x00020000)
+#define FG_LINE_LOAD(RS, SOFF) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32((RS), o0, (SOFF), 0))
 #define FG_SETUP(SX, BUF, SLOT)                                                                                            \
     {                                                                                                                      \
         tn = wtab[BUF][SLOT][lane];                                                                                        \
         Ln = ltab[BUF][SLOT][lane];                                                                                        \
-        Llo_n = __builtin_amdgcn_readfirstlane(wave_min_i32(Ln));                                                          \
-        Lhi_n = __builtin_amdgcn_readfirstlane(wave_max_i32(Ln == FG_NONE ? -FG_NONE : Ln));                               \
+        Llo_n = __builtin_amdgcn_readfirstlane(gwave_min_i32(Ln));                                                         \
+        Lhi_n = __builtin_amdgcn_readfirstlane(gwave_max_i32(Ln == FG_NONE ? -FG_NONE : Ln));                              \
+        need_n = 0;                                                                                                        \
         if (Llo_n != FG_NONE) {                                                                                            \
-            const char *sbase = (const char *)(vol + (size_t)(SX) * strideS);                          /* wave-uniform */  \
+            const __amdgpu_buffer_rsrc_t srs = FG_SLAB_RSRC(SX);                                                           \
             const uint32_t lineoff = (uint32_t)min(max(Llo_n + min(lane, FGROWS - 1), 0), nL - 1) * strideL4;              \
             /* only the lines the wave needs, in blocks of four (wave-uniform branches): 17 of the 24 on average */        \
             need_n = min(Lhi_n - Llo_n + NW, FGROWS);                                                                      \
             _Pragma("unroll") for (int r4 = 0; r4 < FGROWS; r4 += 4)                                                       \
                 if (r4 < need_n) {                                                                                         \
                     _Pragma("unroll") for (int r = r4; r < r4 + 4; ++r)                                                    \
-                        yv[r] = *(const float *)(sbase + (o0 + (uint32_t)__builtin_amdgcn_readlane((int)lineoff, r)));     \
+                        yv[r] = FG_LINE_LOAD(srs, (uint32_t)__builtin_amdgcn_readlane((int)lineoff, r));                   \
+                }                                                                                                          \
+        }                                                                                                                  \
+    }
+    // (rows past need_n keep stale values: a lane reads rows L - Llo .. + NW - 1 < need_n, one outside the window rows 0 .. NW - 1; planes
+    //  past the volume are zeros; need_n = 0 when no lane has a line in the slab)
+#define FG_STAGE                                                                                                           \
+    {                                                                                                                      \
+        if (mz == ~0ull) {                                                                                                 \
+            _Pragma("unroll") for (int r4 = 0; r4 < FGROWS; r4 += 4)                                                       \
+                if (r4 < need_n) {                                                                                         \
+                    _Pragma("unroll") for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = yv[r];                  \
+                }                                                                                                          \
+        } else {                                                                                                           \
+            _Pragma("unroll") for (int r4 = 0; r4 < FGROWS; r4 += 4)                                                       \
+                if (r4 < need_n) {                                                                                         \
+                    _Pragma("unroll") for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = select_lanes(yv[r], mz); \
                 }                                                                                                          \
         }                                                                                                                  \
     }
@@ -565,58 +633,55 @@ __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs,
     int buf = 0;
     FG_TABLE(rk, 0, rk)
     __syncthreads();
-    FG_SETUP(0, 0, 0)
+    float4 t;                                                             // the slab whose first window is in the LDS rows
+    int L, Llo, Lhi;
+    {
+        float4 tn;
+        int Ln, Llo_n, Lhi_n, need_n;
+        float yv[FGROWS];
+        FG_SETUP(0, 0, 0)
+        FG_STAGE
+        t = tn; L = Ln; Llo = Llo_n; Lhi = Lhi_n;
+    }
     for (int grp = 0; grp < n_grp; ++grp) {
         const int nbuf = buf == 2 ? 0 : buf + 1;
         if (grp + 1 < n_grp) FG_TABLE((grp + 1) * nl + rk, nbuf, rk)
         __syncthreads();
         const int g0 = grp * nl, g1 = min(nS, g0 + nl);
         for (int sx = g0; sx < g1; ++sx) {
-            const float4 t = tn;
-            const int L = Ln, Llo = Llo_n, Lhi = Lhi_n, need = need_n;
-            const bool hit = Llo != FG_NONE;
-            // ---- 2b. the lines loaded one slab ago -> the wave's LDS rows (lane = plane; planes past the volume are zeros)
-            if (hit) {
-                // (rows past `need` keep stale values: a lane reads rows L - Llo .. + NW - 1 < need, one outside the window rows 0 .. NW - 1)
-                if (mz == ~0ull) {
-#pragma unroll
-                    for (int r4 = 0; r4 < FGROWS; r4 += 4)
-                        if (r4 < need) {
-#pragma unroll
-                            for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = yv[r];
-                        }
-                } else {
-#pragma unroll
-                    for (int r4 = 0; r4 < FGROWS; r4 += 4)
-                        if (r4 < need) {
-#pragma unroll
-                            for (int r = r4; r < r4 + 4; ++r) wrows[r * GPITCH + lane] = select_lanes(yv[r], mz);
-                        }
-                }
+            float4 tn = t;
+            int Ln = L, Llo_n = FG_NONE, Lhi_n = 0, need_n = 0;
+            float yv[FGROWS];
+            if (sx + 1 < nS) {
+                const bool same = sx + 1 < g1;                            // else the next group's table, already published
+                const int sbuf = same ? buf : nbuf, sslot = same ? sx + 1 - g0 : 0;
+                FG_SETUP(sx + 1, sbuf, sslot)
             }
-            if (sx + 1 < g1) FG_SETUP(sx + 1, buf, sx + 1 - g0)
-            else if (sx + 1 < nS) FG_SETUP(sx + 1, nbuf, 0)
-            if (hit) {
+            if (Llo != FG_NONE) {
                 FG_ACCUM(Llo)
                 // further windows: lines loaded on the spot, four at a time (the registers yv hold the next slab's loads in flight)
                 for (int lb = Llo + SW; lb <= Lhi; lb += SW) {
-                    const char *sbase = (const char *)(vol + (size_t)sx * strideS);
+                    const __amdgpu_buffer_rsrc_t srs = FG_SLAB_RSRC(sx);
                     for (int r = 0; r < FGROWS; r += 4) {
                         float e[4];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            e[k] = *(const float *)(sbase + (o0 + (uint32_t)min(max(lb + r + k, 0), nL - 1) * strideL4));
+                        for (int k = 0; k < 4; ++k) e[k] = FG_LINE_LOAD(srs, (uint32_t)min(max(lb + r + k, 0), nL - 1) * strideL4);
 #pragma unroll
                         for (int k = 0; k < 4; ++k) wrows[(r + k) * GPITCH + lane] = select_lanes(e[k], mz);
                     }
                     FG_ACCUM(lb)
                 }
             }
+            FG_STAGE
+            t = tn; L = Ln; Llo = Llo_n; Lhi = Lhi_n;
         }
         buf = nbuf;
     }
 #undef FG_TABLE
+#undef FG_SLAB_RSRC
+#undef FG_LINE_LOAD
 #undef FG_SETUP
+#undef FG_STAGE
 #undef FG_ACCUM
     // ---- z lerp and store: ray iz = Z - zc takes (1 - tau) S(Z) + tau S(Z + 1); the lane's 64 values are consecutive floats of its sinogram row
     if (!ray_ok) return;
