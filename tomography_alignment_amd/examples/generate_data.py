@@ -25,6 +25,10 @@ cor= are for.  With D = 0 every other key is that of earlier versions for the sa
 shift_px=S (--shift-px S) and ang_deg=A (--tilt-deg A) set the half-width of the x/z jitter and of the alpha/beta jitter (defaults 2 px
 and 1 degree, the reference's): stages of nano-tomography jitter by tens of pixels, what align.consistency and align_rigid's prealign=
 are for.  With the defaults every key is that of earlier versions for the same seed.
+beam_drift=A (--beam-drift A) lets the illumination move between the frames, what preprocess.normalize_dynamic is for: every flat and
+every projection frame is multiplied by a beam profile 0.6 + 0.4 exp(-|r - c|^2 / (2 (0.6 nx)^2)) whose centre c lies uniform(-A, A) px
+from the frame's centre in x and in z (beam_profiles).  The draws come from a generator of their own, and n_flat (--flats N) says how
+many flats there are (default 10): with A = 0 every array is that of earlier versions for the same seed.
 
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --out data.npz
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --out raw.npz
@@ -84,14 +88,29 @@ def add_zingers(frames, k, rng):
     return mask
 
 
+def beam_profiles(n, nz, nx, drift, rng):
+    """n beam profiles [n][z][x], float64: 0.6 + 0.4 exp(-|r - c|^2 / (2 (0.6 nx)^2)), the centre c displaced from the frame's centre by
+    uniform(-drift, drift) px in x and in z (x drawn first, for all n)."""
+    cx = (nx - 1) / 2.0 + rng.uniform(-drift, drift, n)
+    cz = (nz - 1) / 2.0 + rng.uniform(-drift, drift, n)
+    z, x = np.arange(nz, dtype=np.float64)[None, :, None], np.arange(nx, dtype=np.float64)[None, None, :]
+    r2 = (x - cx[:, None, None]) ** 2 + (z - cz[:, None, None]) ** 2
+    return 0.6 + 0.4 * np.exp(-r2 / (2.0 * (0.6 * nx) ** 2))
+
+
 def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=100.0, n_stripes=None, stripe_gain=0.03, propagate=None,
-             dead_columns=0, gain_columns=0, zingers=0):
+             dead_columns=0, gain_columns=0, zingers=0, beam_drift=0.0):
     """Detector frames of the projections proj [n_proj][nx][nz]: dict(counts, flats, darks, mu) (module docstring).  mu defaults to
     4 / nx, which keeps exp(-mu p) of a phantom of values <= 1 well above the noise floor.  propagate: the strength of the propagation
     applied to the noiseless transmission (None or 0: none, and the frames are those of earlier versions for the same seed).
     dead_columns, gain_columns: how many stuck and how many mis-gained columns to add (module docstring); with any, the dict also holds
     their indices as dead_cols and gain_cols.  zingers: how many zingers every count frame and every flat frame gets (module docstring);
-    with any, the dict also holds zinger_mask, and with 0 every array is that of earlier versions for the same seed."""
+    with any, the dict also holds zinger_mask, and with 0 every array is that of earlier versions for the same seed.  beam_drift: the
+    half-width in pixels of the jitter of the beam's centre (module docstring); with 0 there is no beam profile and every array is that
+    of earlier versions for the same seed."""
+    beam_drift = float(beam_drift)
+    if not (np.isfinite(beam_drift) and beam_drift >= 0):
+        raise ValueError("beam_drift must be finite and >= 0, got %r" % (beam_drift,))
     zingers = int(zingers)
     if zingers < 0 or zingers > proj.shape[1] * proj.shape[2]:
         raise ValueError("zingers must be >= 0 and at most the pixels of a frame, got %d" % zingers)
@@ -118,8 +137,14 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
     if len(gained):
         drift = drift.copy()
         drift[gained] *= DEFECT_GAIN
-    counts = frames(i0 * gain * drift * att)
-    flats = frames(np.broadcast_to(i0 * gain, (n_flat, nz, nx)))
+    if beam_drift:
+        brng = np.random.default_rng(None if seed is None else [int(seed), 0x22])
+        beam_flats, beam_proj = beam_profiles(n_flat, nz, nx, beam_drift, brng), beam_profiles(n_proj, nz, nx, beam_drift, brng)
+        counts = frames(i0 * gain * drift * att * beam_proj)
+        flats = frames(i0 * gain * beam_flats)
+    else:
+        counts = frames(i0 * gain * drift * att)
+        flats = frames(np.broadcast_to(i0 * gain, (n_flat, nz, nx)))
     darks = np.clip(rng.poisson(np.broadcast_to(np.maximum(dark_mean, 0), (n_dark, nz, nx))), 0, 65535).astype(np.uint16)
     out = dict(counts=counts, flats=flats, darks=darks, mu=np.float64(mu))
     if len(dead) or len(gained):
@@ -134,7 +159,7 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
 
 
 def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0,
-         zingers=0, cor_offset=0.0):
+         zingers=0, cor_offset=0.0, beam_drift=0.0, n_flat=10):
     cor_offset = float(cor_offset)
     if not np.isfinite(cor_offset):
         raise ValueError("cor_offset must be finite, got %r" % (cor_offset,))
@@ -157,7 +182,8 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, pr
     d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp, cor_offset=np.float64(cor_offset))
     if raw:
         d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate, dead_columns=dead_columns,
-                          gain_columns=gain_columns, zingers=zingers))  # a generator of its own: the other keys do not change
+                          gain_columns=gain_columns, zingers=zingers, beam_drift=beam_drift, n_flat=n_flat))
+        # a generator of its own: the other keys do not change
     return d
 
 
@@ -178,7 +204,16 @@ def parse_args(argv=None):
     ap.add_argument("--zingers", type=int, default=0, metavar="K", help="with --raw: K zingers in every count frame and every flat frame")
     ap.add_argument("--shift-px", type=float, default=2.0, metavar="S", help="half-width of the x and z jitter in pixels (default 2)")
     ap.add_argument("--tilt-deg", type=float, default=1.0, metavar="A", help="half-width of the alpha and beta jitter in degrees (default 1)")
+    ap.add_argument("--beam-drift", type=float, default=0.0, metavar="A",
+                    help="with --raw: the beam's centre jitters by +-A px between the frames (preprocess.normalize_dynamic)")
+    ap.add_argument("--flats", type=int, default=10, metavar="N", help="with --raw: how many flat frames (default 10)")
     a = ap.parse_args(argv)
+    if not (0 <= a.beam_drift < float("inf")):
+        ap.error("--beam-drift must be finite and >= 0")
+    if a.beam_drift and not a.raw:
+        ap.error("--beam-drift needs --raw")
+    if a.flats < 1:
+        ap.error("--flats must be >= 1")
     if not (0 <= a.shift_px < float("inf")) or not (0 <= a.tilt_deg < float("inf")):
         ap.error("--shift-px and --tilt-deg must be finite and >= 0")
     if a.zingers < 0:
@@ -195,7 +230,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     d = make(a.size, a.angles, a.seed, ang_deg=a.tilt_deg, shift_px=a.shift_px, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns,
-             zingers=a.zingers, cor_offset=a.cor_offset)
+             zingers=a.zingers, cor_offset=a.cor_offset, beam_drift=a.beam_drift, n_flat=a.flats)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

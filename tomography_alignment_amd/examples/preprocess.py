@@ -26,6 +26,12 @@ x component of Geometry's cor_shift, the number align_rigid's --cor takes.  The 
 (align.consistency.estimate_shifts; `profile` for samples that extend past the detector vertically), and stores `xyz0` ((n, 3), the
 number align_rigid's --prealign takes from the file), `axis_offset` and `mass_spread`.  The data need `phi`, spanning at least pi / 2.
 
+`--dynamic-flat [M]` divides every projection by a flat of its own (preprocess.normalize_dynamic, for a beam that moves between the flats
+and the projections: generate_data --beam-drift): the mean flat plus M eigen flat fields of the flats -- without a number, as many as
+the flats' eigenvalues call for -- weighted per projection for the least total variation.  The weights are stored as `flat_weights`
+((n, m)).  It takes the place of normalize, before the phase retrieval too, and needs --method mean.  Without it the calls and the
+result are exactly what they were.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -58,7 +64,7 @@ def la_size_for(nx, la_size=None):
 
 
 def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
-        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9, prealign=None):
+        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9, prealign=None, dynamic_flat=None):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
     energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
@@ -66,7 +72,15 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     or 'none'.  zinger_dif: None, or the threshold (counts) of preprocess.remove_outlier, window zinger_size, applied to the counts and to
     the flats before anything else.  find_center: True stores the rotation axis found on the finished sinogram as `cor_offset` (module
     docstring), searched on center_rows detector rows.  prealign: None, or 'moment' / 'profile': stores consistency.estimate_shifts'
-    xyz0, axis_offset and mass_spread of the finished sinogram (module docstring)."""
+    xyz0, axis_offset and mass_spread of the finished sinogram (module docstring).  dynamic_flat: None, or 'auto' / an integer >= 0:
+    preprocess.normalize_dynamic with that many eigen flat fields ('auto': chosen from the flats' eigenvalues) in place of normalize;
+    stores the weights as `flat_weights`."""
+    if dynamic_flat is not None:
+        if dynamic_flat != "auto" and (isinstance(dynamic_flat, (bool, np.bool_)) or not isinstance(dynamic_flat, (int, np.integer))
+                                       or dynamic_flat < 0):
+            raise ValueError("preprocess: dynamic_flat must be None, 'auto' or an integer >= 0, got %r" % (dynamic_flat,))
+        if method != "mean":
+            raise ValueError("preprocess: dynamic_flat works on the mean flat: method must be 'mean', got %r" % (method,))
     if find_center and "phi" not in data:
         raise ValueError("preprocess: find_center needs the angles `phi`")
     if prealign is not None:
@@ -99,7 +113,11 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
             flats = np.asarray(flats)
             flats = p.remove_outlier(flats if flats.dtype in (np.uint16, np.float32) else flats.astype(np.float32), zinger_dif,
                                      size=zinger_size)
-        if phase is None:
+        flat_weights = None
+        if dynamic_flat is not None:
+            sino, flat_weights, _ = p.normalize_dynamic(d_frames, flats, data["darks"], n_eff=None if dynamic_flat == "auto" else int(dynamic_flat),
+                                                        cutoff=cutoff, crop=crop, minus_log=phase is None, return_weights=True)
+        elif phase is None:
             sino = p.normalize(d_frames, flats, data["darks"], cutoff=cutoff, method=method, crop=crop)
         else:
             sino = p.normalize(d_frames, flats, data["darks"], cutoff=cutoff, method=method, crop=crop, minus_log=False)
@@ -134,6 +152,8 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         proj = (proj / np.float32(data["mu"])).astype(np.float32)
     out = {k: v for k, v in data.items() if k not in RAW_KEYS}
     out["projections"] = proj
+    if flat_weights is not None:
+        out["flat_weights"] = flat_weights
     if cor is not None:
         out["cor_offset"] = np.float64(cor)
     if est is not None:
@@ -142,6 +162,9 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         print("preprocess: %s counts -> projections %s (stripe removal %s, window %s, phase retrieval %s)"
               % (counts.shape, proj.shape, stripe, (stripe_size or "off") if stripe != "none" else "off",
                  phase if phase is not None else "off"))
+        if flat_weights is not None:
+            print("preprocess: dynamic flat field with %d eigen flat fields, largest |weight| %.2f"
+                  % (flat_weights.shape[1], float(np.abs(flat_weights).max()) if flat_weights.size else 0.0))
         if cor is not None:
             print("preprocess: rotation axis at cor_offset %+.3f px (offsets per row %s)" % (cor, found.offsets.tolist()))
         if est is not None:
@@ -175,7 +198,19 @@ def parse_args(argv=None):
     ap.add_argument("--center-rows", type=int, default=9, metavar="K", help="with --find-center: the detector rows searched")
     ap.add_argument("--prealign", nargs="?", const="moment", default=None, choices=PREALIGN_MODES,
                     help="estimate the per-projection shifts from the sinogram's moments and store them as xyz0 (with axis_offset, mass_spread)")
+    ap.add_argument("--dynamic-flat", nargs="?", const="auto", default=None, metavar="M",
+                    help="a flat per projection from M eigen flat fields of the flats (no number: as many as their eigenvalues call for); "
+                    "stores the weights as flat_weights")
     a = ap.parse_args(argv)
+    if a.dynamic_flat is not None and a.dynamic_flat != "auto":
+        try:
+            a.dynamic_flat = int(a.dynamic_flat)
+        except ValueError:
+            ap.error("--dynamic-flat takes no value, 'auto' or an integer >= 0")
+        if a.dynamic_flat < 0:
+            ap.error("--dynamic-flat must be >= 0")
+    if a.dynamic_flat is not None and a.method != "mean":
+        ap.error("--dynamic-flat needs --method mean")
     if a.center_rows < 1:
         ap.error("--center-rows must be >= 1")
     if a.zinger_dif is not None and not a.zinger_dif >= 0:
@@ -211,7 +246,7 @@ def main(argv=None):
     a = parse_args(argv)
     d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
             stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size,
-            find_center=a.find_center, center_rows=a.center_rows, prealign=a.prealign)
+            find_center=a.find_center, center_rows=a.center_rows, prealign=a.prealign, dynamic_flat=a.dynamic_flat)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 

@@ -88,6 +88,23 @@ float32 transforms.  Frames are filtered in batches whose spectra and hipFFT wor
 never fewer than one frame); every frame is transformed on its own, so the result does not depend on the batch.  The work is per
 projection: a rank that holds a block of angles filters its own block.
 
+Dynamic flat-field correction (eigen_flats, normalize_dynamic; libtomo_dff.so, include/tomo_dff.h, whose comment defines the arithmetic):
+Van Nieuwenhove et al., Opt. Express 23, 27975 (2015), for a beam that moves or changes shape between the flats and the projections.
+    eigen_flats        fbar, dark = the float32 means of the stacks; G = the float64 Gram matrix of the K flats' deviations from fbar;
+                       numpy.linalg.eigh(G), eigenvalues descending, every eigenvector's largest component positive; the eigen flat
+                       fields e_j = float32(sum_k V[k][j] (F_k - fbar) / sqrt(K)), j < m.  n_eff=None keeps every leading eigenvalue
+                       above eig_ratio x the median eigenvalue, at most MAX_EFF, possibly none.
+    normalize_dynamic  projection i is divided by a flat of its own, fbar + sum_j w_ij e_j.  The m weights minimise the total variation
+                       of s_i (raw_i - dark) / (flat_i - dark) on frames binned by `bin`, s_i the mean of the binned flat_i - dark
+                       (without it a brighter flat would always lower the cost); L-BFGS-B from zero within +-w_max, every projection's
+                       optimiser advanced side by side and all pending costs and gradients evaluated in one launch.  The apply step is
+                       normalize's arithmetic with flat_i: with n_eff=0 or zero weights the result is normalize(method="mean") bit for bit.
+A weight is in standard deviations of the flats' own variation along e_j.  A beam whose total intensity changes by a constant factor is
+not recovered: s_i makes the cost blind to it, by design.  Limits (DffUnsupported before anything is uploaded): 2 <= K <= 128 flats,
+m <= 8 and m <= K - 1, bin in 1 ... 8 with at least 2 x 2 binned pixels.  The binned counts live in the handle's scratch, in batches of
+projections bounded by max_scratch_bytes (default 2 GiB; 0: no limit; never fewer than one); the result does not depend on the batch.
+Every rank computes the same eigen flat fields from the same flats and normalises its own block of angles, on its own or with weights=.
+
 The kernels live in their own library, like libtomo_fbp.so and libtomo_xcorr.so, so that the projector's sources and the kernel-source
 hash that keys the committed PMC counters do not change.  Host arrays and _lib.DeviceArrays are both accepted; a device input gives a
 device output, with no host round trip, and every temporary buffer is freed before a call returns.  Arguments are checked (ValueError)
@@ -97,13 +114,20 @@ import math
 
 import numpy as np
 
-from . import _phase_lib, _prep_lib
+from . import _dff_lib, _lbfgsb_batch, _phase_lib, _prep_lib
+from ._dff_lib import DffUnsupported  # noqa: F401  (re-exported)
 from ._ops import HandleOwner, _is_dev
 from ._prep_lib import PrepUnsupported  # noqa: F401  (re-exported)
 
 DEFAULT_SCRATCH_BYTES = 2 << 30
 METHODS = {"mean": _prep_lib.MEAN, "median": _prep_lib.MEDIAN}
 _DTYPES = {np.dtype(np.uint16): _prep_lib.U16, np.dtype(np.float32): _prep_lib.F32}
+_DFF_DTYPES = {np.dtype(np.uint16): _dff_lib.U16, np.dtype(np.float32): _dff_lib.F32}
+MAX_EFF = _dff_lib.MAX_EFF
+# L-BFGS-B options of normalize_dynamic's minimisation (scipy's names).  ftol: the device evaluates the cost in float32 with float64 sums
+# and agrees with float64 arithmetic to 1e-7 of the cost; scipy's default 2.2e-9 asks the line search for decreases
+# below that noise, which cost five times the evaluations on the test data and moved no weight by more than 0.006.
+TV_OPTIONS = {"ftol": 1e-7}
 
 
 def _shape_dtype(a, what, ndims):
@@ -283,6 +307,69 @@ def _check_dif(dif):
     return float(dif32)
 
 
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _positive(v, name):
+    try:
+        ok = not isinstance(v, (bool, np.bool_)) and math.isfinite(float(v)) and float(v) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be finite and > 0, got %r" % (name, v))
+    return float(v)
+
+
+def eigen_decomposition(G):
+    """(eigenvalues descending, V): numpy.linalg.eigh of the Gram matrix G, every eigenvector V[:, j] signed so that its component of
+    largest magnitude -- the lowest index on a tie -- is positive."""
+    lam, V = np.linalg.eigh(np.asarray(G, np.float64))
+    lam, V = lam[::-1].copy(), V[:, ::-1].copy()
+    for j in range(V.shape[1]):
+        if V[np.argmax(np.abs(V[:, j])), j] < 0:
+            V[:, j] = -V[:, j]
+    return lam, V
+
+
+def count_eigen_flats(eigenvalues, eig_ratio=2.0):
+    """How many leading eigenvalues exceed eig_ratio x the median eigenvalue, at most MAX_EFF (and possibly none)."""
+    med = float(np.median(eigenvalues))
+    m = 0
+    while m < min(len(eigenvalues), MAX_EFF) and eigenvalues[m] > eig_ratio * med:
+        m += 1
+    return m
+
+
+class EigenFlats(object):
+    """What eigen_flats returns, on the device: `flat` and `dark`, float32 [z][x]; `eff`, the eigen flat fields, float32 [m][z][x] (None
+    where n_eff = 0); and on the host `eigenvalues` (K,) of the flats' Gram matrix, descending, and `n_eff` = m.  free() releases the
+    device buffers; a context manager."""
+
+    def __init__(self, flat, dark, eff, eigenvalues, n_eff):
+        self.flat, self.dark, self.eff = flat, dark, eff
+        self.eigenvalues, self.n_eff = np.asarray(eigenvalues, np.float64), int(n_eff)
+        self.shape = tuple(flat.shape)
+
+    def free(self):
+        for d in (self.flat, self.dark, self.eff):
+            if d is not None:
+                d.free()
+        self.flat = self.dark = self.eff = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def _check_n_eff(n_eff):
+    if n_eff is not None and (not _is_int(n_eff) or n_eff < 0):
+        raise ValueError("n_eff must be None or an integer >= 0, got %r" % (n_eff,))
+    return None if n_eff is None else int(n_eff)
+
+
 class Preprocessor(HandleOwner):
     """One libtomo_prep handle and its scratch, reused across calls.  ctx: the _lib.Context whose device and stream the work uses (work
     is enqueued on ctx.stream(), in order with the projector work that follows); default the context of the first DeviceArray passed in,
@@ -291,6 +378,7 @@ class Preprocessor(HandleOwner):
     def __init__(self, ctx=None):
         HandleOwner.__init__(self, ctx)
         self._phase = None
+        self._dff = None
 
     def _new_handle(self):
         return _prep_lib.PrepHandle(self.ctx.device)
@@ -299,6 +387,9 @@ class Preprocessor(HandleOwner):
         if self._phase is not None:
             self._phase.close()
             self._phase = None
+        if self._dff is not None:
+            self._dff.close()
+            self._dff = None
         HandleOwner.close(self)
 
     def _upload(self, a, temps):
@@ -390,6 +481,181 @@ class Preprocessor(HandleOwner):
             return res if _is_dev(frames) else res.download()
         finally:
             self._free(temps)
+
+    def _ready_dff(self, like):
+        self._ready(like)
+        if self._dff is None:
+            self._dff = _dff_lib.DffHandle(self.ctx.device)
+
+    def _check_eigen_args(self, flats, darks, n_eff, eig_ratio, bin=1):
+        """((flats' shape, dtype), (darks' shape, dtype), n_eff) or ValueError / DffUnsupported: nothing is uploaded before this."""
+        infos = self._check_reference_args(((flats, "flats"), (darks, "darks")), "mean")
+        n_eff = _check_n_eff(n_eff)
+        _positive(eig_ratio, "eig_ratio")
+        shape = infos[0][0]
+        K = 1 if len(shape) == 2 else shape[0]
+        _dff_lib.check(K, 0 if n_eff is None else n_eff, shape[-2], shape[-1], bin)
+        return infos[0], infos[1], n_eff
+
+    def _eigen_flats(self, flats, darks, infos, n_eff, eig_ratio):
+        (fshape, fdtype), (dshape, ddtype) = infos
+        K, rows, cols = fshape
+        self._ready_dff(flats)
+        st = self.ctx.stream()
+        temps, keep = [], []
+        try:
+            d_flats = self._upload(flats, temps)
+            keep.append(self._reference(d_flats, fshape, fdtype, "mean"))
+            keep.append(self._reference(self._upload(darks, temps), dshape, ddtype, "mean"))
+            lam, V = eigen_decomposition(self._dff.gram(st, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, keep[0].ptr))
+            m = count_eigen_flats(lam, eig_ratio) if n_eff is None else n_eff
+            eff = None
+            if m:
+                eff = self.ctx.empty((m, rows, cols), np.float32)
+                keep.append(eff)
+                self._dff.eff(st, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, keep[0].ptr, V[:, :m], eff.ptr)
+            return EigenFlats(keep[0], keep[1], eff, lam, m)
+        except Exception:
+            self._free(keep)
+            raise
+        finally:
+            self._free(temps)
+
+    def eigen_flats(self, flats, darks, n_eff=None, eig_ratio=2.0):
+        """The EigenFlats (module docstring) of the stacks flats [K][rows][cols] and darks, uint16 or float32, host or device: the mean
+        flat, the mean dark and the n_eff leading eigen flat fields, all on the device.  n_eff=None: as many as have an eigenvalue above
+        eig_ratio x the median eigenvalue (at most MAX_EFF, possibly 0)."""
+        f, d, n_eff = self._check_eigen_args(flats, darks, n_eff, eig_ratio)
+        return self._eigen_flats(flats, darks, (f, d), n_eff, eig_ratio)
+
+    def _estimate_weights(self, d_raw, dtype, n, rows, cols, ef, m, bin, tv_eps, w_max, budget):
+        """((n, m) float64 weights, evaluations): the total-variation minimisation of normalize_dynamic."""
+        from . import alignment
+        h, st = self._dff, self.ctx.stream()
+        zb, xb = rows // bin, cols // bin
+        W, nfev = np.zeros((n, m), np.float64), 0
+        h.set_max_scratch(budget)
+        temps = []
+        try:
+            Fb, Eb = self.ctx.empty((zb, xb), np.float32), self.ctx.empty((m, zb, xb), np.float32)
+            temps += [Fb, Eb]
+            h.bin(st, ef.flat.ptr, _dff_lib.F32, 1, rows, cols, bin, ef.dark.ptr, Fb.ptr)
+            h.bin(st, ef.eff.ptr, _dff_lib.F32, m, rows, cols, bin, None, Eb.ptr)
+            a = np.array([np.mean(Fb.download().astype(np.float64))] + [np.mean(e.astype(np.float64)) for e in Eb.download()], np.float64)
+            bounds = [(-w_max, w_max)] * m
+            nb = min(_dff_lib.batch(n, rows, cols, bin, budget), _dff_lib.MAX_IDS)      # one launch lists at most MAX_IDS projections
+            batched = alignment.batch_driver_available()
+            from concurrent.futures import ThreadPoolExecutor
+            for i0 in range(0, n, nb):
+                cnt = min(nb, n - i0)
+                h.load_projections(st, d_raw.ptr, _DFF_DTYPES[dtype], i0, cnt, rows, cols, bin, ef.dark.ptr)
+
+                def fun_batch(ids, X, i0=i0):
+                    w = np.asarray(X, np.float64).reshape(len(ids), m).astype(np.float32)
+                    s = a[0] + w.astype(np.float64) @ a[1:]              # float64; the library takes it rounded
+                    return h.cost(st, i0 + np.asarray(ids, np.int64), w, s, a, tv_eps, Fb.ptr, Eb.ptr)
+
+                # the helper thread is the only one that touches the GPU while the pass runs (alignment.align_projections)
+                with ThreadPoolExecutor(max_workers=1, initializer=self.ctx.make_current) as pool:
+                    if batched:
+                        x, _, nf, _ = _lbfgsb_batch.minimize_many(fun_batch, np.zeros((cnt, m)), bounds=bounds, options=TV_OPTIONS, overlap=pool.submit)
+                    else:                                                # this scipy's core is laid out differently: one problem at a time
+                        from scipy import optimize
+                        x, nf = np.zeros((cnt, m)), np.zeros(cnt, np.int64)
+                        for i in range(cnt):
+                            def fun(p, i=i):
+                                f, g = pool.submit(fun_batch, [i], p[None]).result()
+                                return f[0], g[0]
+                            res = optimize.minimize(fun, np.zeros(m), jac=True, method="L-BFGS-B", bounds=bounds, options=dict(TV_OPTIONS))
+                            x[i], nf[i] = res.x, res.nfev
+                W[i0:i0 + cnt], nfev = x, nfev + int(np.sum(nf))
+        finally:
+            self._free(temps)
+        return W, nfev
+
+    def normalize_dynamic(self, frames, flats, darks=None, n_eff=None, eig_ratio=2.0, bin=2, tv_eps=1e-3, w_max=10.0, weights=None,
+                          cutoff=None, minus_log=True, min_ratio=1e-6, crop=None, out=None, max_scratch_bytes=None, return_weights=False):
+        """normalize with a flat per projection (module docstring): the (n_proj, nx, nz) float32 sinogram of raw frames
+        [n_proj][rows][cols], an ndarray for host frames, a DeviceArray for device frames (`out`, a float32 DeviceArray of that shape,
+        if given).  flats: the stack of flats (with darks), or an EigenFlats (darks must then be None; n_eff may select fewer of its
+        fields).  weights: an (n_proj, m) array skips the estimation and only applies -- a rank that holds a block of angles passes
+        its rows.  return_weights=True: (result, (n_proj, m) float64 weights, number of cost evaluations)."""
+        shape, dtype = _shape_dtype(frames, "frames", (3,))
+        n, rows, cols = shape
+        given = isinstance(flats, EigenFlats)
+        if not _is_int(bin):
+            raise ValueError("bin must be an integer in 1 ... %d, got %r" % (_dff_lib.MAX_BIN, bin))
+        n_eff = _check_n_eff(n_eff)
+        if weights is not None:
+            weights = np.asarray(weights)
+            if weights.ndim != 2 or weights.shape[0] != n or not np.issubdtype(weights.dtype, np.number) or not np.all(np.isfinite(weights)):
+                raise ValueError("weights must be a finite (%d, m) array, got shape %s" % (n, weights.shape))
+            weights = weights.astype(np.float64)
+            if n_eff is None:
+                n_eff = weights.shape[1]
+            if weights.shape[1] != n_eff:
+                raise ValueError("weights has %d columns for n_eff = %d" % (weights.shape[1], n_eff))
+        if given:
+            if darks is not None:
+                raise ValueError("darks must be None where flats is an EigenFlats (it holds the dark)")
+            if flats.flat is None:
+                raise ValueError("the EigenFlats has been freed")
+            _positive(eig_ratio, "eig_ratio")
+            if flats.shape != (rows, cols):
+                raise ValueError("the EigenFlats must have the frames' shape %s, got %s" % ((rows, cols), flats.shape))
+            if n_eff is not None and n_eff > flats.n_eff:
+                raise ValueError("n_eff = %d exceeds the %d fields of the EigenFlats" % (n_eff, flats.n_eff))
+            infos = None
+        else:
+            if darks is None:
+                raise ValueError("darks must be given with a stack of flats")
+            f, d, n_eff = self._check_eigen_args(flats, darks, n_eff, eig_ratio, bin)
+            infos = (f, d)
+            if f[0][-2:] != (rows, cols):
+                raise ValueError("flats and darks must have the frames' shape %s, got %s" % ((rows, cols), f[0][-2:]))
+        tv_eps, w_max = _positive(tv_eps, "tv_eps"), _positive(w_max, "w_max")
+        (z0, z1), (x0, x1) = _crop(crop, rows, cols)
+        _check_min_ratio(min_ratio)
+        if cutoff is not None and not np.isfinite(cutoff):
+            raise ValueError("cutoff must be finite or None, got %r" % (cutoff,))
+        budget = DEFAULT_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+        if budget < 0:
+            raise ValueError("max_scratch_bytes must be >= 0 (0: no limit)")
+        oshape = (n, x1 - x0, z1 - z0)
+        if out is not None and not (_is_dev(out) and out.dtype == np.float32 and out.size == int(np.prod(oshape))):
+            raise ValueError("out must be a float32 DeviceArray of %d values %s" % (int(np.prod(oshape)), oshape))
+        if out is not None and not _is_dev(frames):
+            raise ValueError("out needs a DeviceArray input (a host input gives a host result)")
+        if given:
+            _dff_lib.check(max(2, flats.n_eff + 1), flats.n_eff, rows, cols, bin)      # the frame and the bin factor
+        self._ready_dff(frames)
+        temps, ef, res = [], None, None
+        try:
+            d_raw = self._upload(frames, temps)
+            ef = flats if given else self._eigen_flats(flats, darks, infos, n_eff, eig_ratio)
+            m = ef.n_eff if n_eff is None else n_eff
+            nfev = 0
+            if weights is None:
+                weights = np.zeros((n, m), np.float64)
+                if m:
+                    weights, nfev = self._estimate_weights(d_raw, dtype, n, rows, cols, ef, m, int(bin), tv_eps, w_max, budget)
+            res = out if out is not None else self.ctx.empty(oshape, np.float32)
+            self._dff.apply(self.ctx.stream(), d_raw.ptr, _DFF_DTYPES[dtype], n, rows, cols, ef.flat.ptr, ef.dark.ptr,
+                            None if not m else ef.eff.ptr, weights.astype(np.float32).reshape(n, m), ((z0, z1), (x0, x1)), cutoff, minus_log,
+                            min_ratio, res.ptr)
+            result = res if _is_dev(frames) else res.download()
+        except Exception:
+            if res is not None and out is None:
+                res.free()
+            raise
+        else:
+            if out is None and not _is_dev(frames):
+                res.free()
+        finally:
+            self._free(temps)
+            if ef is not None and not given:
+                ef.free()
+        return (result, weights, nfev) if return_weights else result
 
     def remove_stripe_sorting(self, proj, size=21, out=None, max_scratch_bytes=None, timed=False):
         """Stripe removal of the sinogram proj [n_proj][nx][nz] (float32; module docstring).  Host in: an ndarray out.  Device in: the
@@ -646,6 +912,32 @@ def normalize(frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6,
     p = Preprocessor(ctx)
     try:
         return p.normalize(frames, flats, darks, cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, method=method, crop=crop, out=out)
+    finally:
+        p.close()
+
+
+def eigen_flats(flats, darks, n_eff=None, eig_ratio=2.0, ctx=None):
+    """The EigenFlats of the stacks flats and darks: Preprocessor.eigen_flats on a handle of its own.  Its buffers belong to ctx (without
+    one: to the context of device flats), which must outlive them."""
+    if ctx is None and not _is_dev(flats):
+        raise ValueError("eigen_flats: the EigenFlats lives on the device, so host flats need a ctx that outlives it")
+    p = Preprocessor(ctx)
+    try:
+        return p.eigen_flats(flats, darks, n_eff=n_eff, eig_ratio=eig_ratio)
+    finally:
+        p.close()
+
+
+def normalize_dynamic(frames, flats, darks=None, n_eff=None, eig_ratio=2.0, bin=2, tv_eps=1e-3, w_max=10.0, weights=None, cutoff=None,
+                      minus_log=True, min_ratio=1e-6, crop=None, ctx=None, out=None, max_scratch_bytes=None, return_weights=False):
+    """The sinogram of raw frames with a flat per projection: Preprocessor.normalize_dynamic on a handle of its own."""
+    if ctx is None and isinstance(flats, EigenFlats) and flats.flat is not None:
+        ctx = flats.flat.ctx
+    p = Preprocessor(ctx)
+    try:
+        return p.normalize_dynamic(frames, flats, darks, n_eff=n_eff, eig_ratio=eig_ratio, bin=bin, tv_eps=tv_eps, w_max=w_max, weights=weights,
+                                   cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, crop=crop, out=out,
+                                   max_scratch_bytes=max_scratch_bytes, return_weights=return_weights)
     finally:
         p.close()
 
