@@ -1,0 +1,387 @@
+"""Half-acquisition scans without a GPU: the numpy model of tests/half_model.py on analytic sinograms (the axis found, the stitch against
+the analytic pi sinogram, the shape and no-gap rules, left = mirrored right), the host half of the library (the stitch's column table
+against the model's), the ctypes table against include/tomo_half.h, every refusal of half_acquisition before a device is touched, and the
+options of both examples."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import half_model as hm
+import mom_model as mm
+
+from tomography_alignment_amd import _binding, _half_lib, _lib, half_acquisition as ha
+from tomography_alignment_amd.examples import generate_data
+from tomography_alignment_amd.examples import preprocess as ex_pre
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GAUSSIANS = tuple(o for o in hm.OBJECTS if o[3] == "g")
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the model
+
+@pytest.mark.parametrize("noise", [0.0, 0.02], ids=["clean", "noisy"])
+@pytest.mark.parametrize("n,nx,c,w", hm.CASES)
+def test_model_finds_the_axis_of_analytic_sinograms(n, nx, c, w, noise):
+    """The side and |c - truth| <= 0.1 px: a condition with a margin of about 4 x over the model's own error on these twelve inputs
+    (at most 0.028 px), not a fitted tolerance."""
+    S = hm.sinogram_360(n, nx, c, noise=noise, seed=1)
+    found, side, k, _ = hm.find_center_row(S, w)
+    print("n %d nx %d c %.2f w %d noise %.2f: side %s, c - truth %+.4f" % (n, nx, c, w, noise, side, found - c))
+    assert side == ("right" if c >= (nx - 1) / 2 else "left")
+    assert abs(found - c) <= 0.1
+    assert hm.find_center_row(S, w, side=side)[0] == found             # asking for the side that wins changes nothing
+    p = np.repeat(S[:, :, None], 3, axis=2)
+    p[:, :, 0] = 0.0                                                    # a row without structure: m = 1 everywhere, the median ignores it
+    centre, centres, sides, ks, _ = hm.find_center_360(p, rows=[0, 1, 2], win_width=w)
+    assert centre == found and centres[1] == centres[2] == found and ks[1] == k and sides[1] == side
+
+
+@pytest.mark.parametrize("n,nx,c", [(n, nx, cc) for n, nx, c, _ in hm.CASES if float(2 * c).is_integer() for cc in (c, nx - 1 - c)])
+def test_model_stitch_equals_the_analytic_pi_sinogram_where_2c_is_an_integer(n, nx, c):
+    """No interpolation: the stitch of the float64 series is the analytic series of width W about c_out within 1e-8 of the maximum
+    (measured: 2e-16)."""
+    out, T = hm.stitch(hm.sinogram_360(n, nx, c, dtype=np.float64), c)
+    ref, c_out = hm.sinogram_180(n, nx, c)
+    e = np.abs(out - ref).max() / ref.max()
+    print("n %d nx %d c %.2f (%s): W %d, c_out %.2f, error %.2e of the maximum" % (n, nx, c, T["side"], T["W"], c_out, e))
+    assert out.shape == ref.shape == (n // 2, T["W"]) and T["c_out"] == c_out
+    assert T["side"] == ("right" if c >= (nx - 1) / 2 else "left")
+    assert e <= 1e-8
+
+
+@pytest.mark.parametrize("n,nx,c", [(n, nx, c) for n, nx, c, _ in hm.CASES if not float(2 * c).is_integer()])
+def test_model_stitch_of_smooth_objects_at_a_fractional_axis(n, nx, c):
+    """Linear interpolation of f between samples one column apart errs by at most max|f''| / 8.  For the Gaussians,
+    f = amp r sqrt(2 pi) exp(-s^2 / 2 r^2), max|f''| = amp sqrt(2 pi) / r, summed over the objects: the bound is 0.1723.  Measured on
+    the model: 0.119, 0.125, 0.164 and 0.093 for c = 52.3, 55.75, 10.2 and 101.37."""
+    bound = sum(amp * np.sqrt(2 * np.pi) / r for _, _, r, _, amp in GAUSSIANS) / 8.0
+    out, T = hm.stitch(hm.sinogram_360(n, nx, c, objects=GAUSSIANS, dtype=np.float64), c)
+    ref, _ = hm.sinogram_180(n, nx, c, objects=GAUSSIANS)
+    e = np.abs(out - ref).max()
+    print("n %d nx %d c %.2f: error %.4f, bound %.4f" % (n, nx, c, e, bound))
+    assert abs(bound - 0.1723) < 1e-4 and e <= bound
+    only_a = T["a_valid"] & ~T["b_valid"]
+    assert only_a.any() and np.abs(out - ref)[:, only_a].max() <= 1e-12 * ref.max()      # the first half's own columns are copies
+
+
+@pytest.mark.parametrize("nx", [16, 48, 64])
+def test_stitched_shape_and_no_gap_over_a_sweep_of_the_axis(nx):
+    """stitched_shape (the module's, the model's and the library's), the no-gap property, and the library's column table against the
+    model's, for c over [0, nx - 1] in steps of 0.37 and at the special values."""
+    sweep = list(np.arange(0.0, nx - 1, 0.37)) + [nx - 1.0, (nx - 1) / 2.0, nx / 2.0, nx / 2.0 - 1.0, 0.5, nx - 1.5]
+    for c in sweep:
+        T = hm.column_table(nx, c)                                       # asserts that every column has a source
+        h, W, j0 = ha.stitched_shape(10, nx, c)
+        assert (h, W, j0) == hm.stitched_shape(10, nx, c) == (5, T["W"], T["j0"])
+        assert _half_lib.stitched_shape(10, nx, c) == (5, W, j0, T["c_out"])
+        assert W == int(np.floor(2 * max(c, nx - 1 - c))) + 1 and nx <= W <= 2 * nx - 1
+        assert j0 == (0 if c >= (nx - 1) / 2 else W - nx)
+        assert T["a_valid"].sum() == nx and np.all(T["a_valid"][j0:j0 + nx])
+        L = _half_lib.table(nx, c)
+        flags = T["a_valid"] * _half_lib.A_VALID + T["b_valid"] * _half_lib.B_VALID
+        assert np.array_equal(L["flags"], flags) and np.all(flags > 0)
+        assert np.array_equal(L["ja"], T["ja"]) and np.array_equal(L["i0"], T["i0"]) and np.array_equal(L["i1"], T["i1"])
+        assert np.array_equal(L["f"], T["f"]) and np.array_equal(L["wA"], T["wA"])
+        assert np.array_equal(L["f1"], T["f"].astype(np.float32)) and np.array_equal(L["f0"], (1.0 - T["f"]).astype(np.float32))
+        assert np.array_equal(L["wa"], T["wA"].astype(np.float32)) and np.array_equal(L["wb"], (1.0 - T["wA"]).astype(np.float32))
+        for k in ("ja", "i0", "i1"):                                     # what the kernel dereferences, whatever the flags say
+            assert L[k].min() >= 0 and L[k].max() <= nx - 1
+        both = T["a_valid"] & T["b_valid"]
+        g = min(c, nx - 1 - c)
+        assert both.sum() in (int(np.floor(2 * g)) + 1, int(np.floor(2 * g)) + 2, int(np.ceil(2 * g)))
+    T = hm.column_table(nx, nx - 1.0)                                    # g = 0: the halves share one column, taken from the first
+    assert T["W"] == 2 * nx - 1 and np.all(T["wA"] == 1.0) and (T["a_valid"] & T["b_valid"]).sum() == 1
+    for bad in (-0.01, nx - 0.99, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="axis must lie on the detector"):
+            ha.stitched_shape(10, nx, bad)
+        with pytest.raises(_half_lib.HalfUnsupported, match="outside 0 <= c <= nx - 1"):
+            _half_lib.stitched_shape(10, nx, bad)
+
+
+def test_left_equals_mirrored_right():
+    """Stitching the column-reversed stack about nx - 1 - c gives the column-reversed output and c_out' = W - 1 - c_out.  Off the
+    centre; at c = (nx - 1) / 2 both are side right and the blend is not symmetric."""
+    rng = np.random.default_rng(5)
+    n, nx, nz = 8, 16, 3
+    p = rng.uniform(0.0, 4.0, (n, nx, nz)).astype(np.float32)
+    for c in (9.0, 9.5, 11.3, 12.62, 14.99, 15.0, 7.75, 7.5001):
+        out, T = hm.stitch(p, c)
+        mirrored, Tm = hm.stitch(p[:, ::-1], nx - 1 - c)
+        assert T["side"] == "right" and Tm["side"] == "left" and Tm["W"] == T["W"]
+        assert abs(Tm["c_out"] - (T["W"] - 1 - T["c_out"])) <= 1e-12
+        assert np.abs(mirrored[:, ::-1] - out).max() <= 1e-12 * 4.0, c
+
+
+def test_the_module_takes_the_minimum_like_the_model():
+    rng = np.random.default_rng(2)
+    for trial in range(50):
+        nx, w = 40, 9
+        mr, ml = rng.uniform(0.1, 1.0, nx - w + 1), rng.uniform(0.1, 1.0, nx - w + 1)
+        if trial % 5 == 0:
+            ml[7] = mr[3] = 0.05                                         # a tie between the sides: right wins
+        if trial % 7 == 0:
+            mr[0] = 0.01                                                 # a minimum at an end: no parabola
+        if trial % 11 == 0:
+            mr[4:7] = 0.02                                               # a flat minimum: the first index, no curvature on one side
+        for side in (None, "right", "left"):
+            assert ha.center_from_curves(mr, ml, nx, w, side) == hm.center_from_curves(mr, ml, nx, w, side)
+        assert ha.refine(mr) == hm.refine(mr)
+    assert ha.center_from_curves(np.array([1.0, 0.2, 0.2, 1.0]), np.array([1.0, 0.2, 0.2, 1.0]), 6, 3)[1:3] == ("right", 1)
+    assert ha.default_window(2048) == 256 and ha.default_window(48) == 8
+
+
+def test_angles():
+    for mod in (ha, hm):
+        assert mod.angle_span(None, 120) == 120
+        assert mod.angle_span(np.linspace(0, 2 * np.pi, 120, endpoint=False), 120) == 120
+        assert mod.angle_span(0.3 - np.linspace(0, 2 * np.pi, 120, endpoint=False), 120) == 120
+        assert mod.angle_span(np.linspace(0, 2 * np.pi, 121), 121) == 120
+        for angles, n, why in ((None, 121, "even number"), (np.linspace(0, 2 * np.pi, 120), 120, "even number"),
+                               (np.linspace(0, np.pi, 120, endpoint=False), 120, "must span 2 pi"), (np.linspace(0, np.pi, 121), 121, "must span 2 pi"),
+                               (np.linspace(0, 2 * np.pi, 120, endpoint=False) ** 2, 120, "uniformly spaced"), (np.zeros(120), 120, "uniformly spaced"),
+                               (np.linspace(0, 2 * np.pi, 100, endpoint=False), 120, "100 angles for 120"), (None, 0, "even number"),
+                               ([0.0], 1, "at least two")):
+            with pytest.raises(ValueError, match=why):
+                mod.angle_span(angles, n)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the binding
+
+def test_ctypes_table_lists_every_symbol_of_the_header():
+    text = open(os.path.join(ROOT, "include", "tomo_half.h")).read()
+    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]+?\b(tomo_half_\w+)\s*\(", text))
+    assert declared == set(_half_lib.SIGNATURES)
+    for macro, value in (("MAX_N", _half_lib.MAX_N), ("MIN_NX", _half_lib.MIN_NX), ("MAX_NX", _half_lib.MAX_NX), ("MAX_NZ", _half_lib.MAX_NZ),
+                         ("MAX_ROWS", _half_lib.MAX_ROWS), ("MIN_W", _half_lib.MIN_W), ("TILE_J", _half_lib.TILE_J), ("TILE_P", _half_lib.TILE_P),
+                         ("TILE_C", _half_lib.TILE_C)):
+        assert int(re.search(r"#define TOMO_HALF_%s (\d+)" % macro, text).group(1)) == value, macro
+    assert int(re.search(r"TOMO_HALF_ERR_UNSUPPORTED = (\d+)", text).group(1)) == _half_lib.ERR_UNSUPPORTED == 4
+    assert (int(re.search(r"TOMO_HALF_A_VALID = (\d+)", text).group(1)), int(re.search(r"TOMO_HALF_B_VALID = (\d+)", text).group(1))) \
+        == (_half_lib.A_VALID, _half_lib.B_VALID)
+    for name, (_, args) in _half_lib.SIGNATURES.items():
+        decl = re.search(r"TOMO_API[^;]*\b%s\s*\(([^;]*)\);" % name, text, re.S).group(1)
+        n = 0 if decl.strip() == "void" else decl.count(",") + 1
+        assert n == len(args), name
+    assert ctypes.sizeof(_half_lib.Column) == 32
+
+
+def test_load_binds_the_whole_table_once():
+    lib = _half_lib.load()
+    assert _half_lib.load() is lib
+    for sym, (res, args) in _half_lib.SIGNATURES.items():
+        assert sym.startswith("tomo_half_"), sym
+        fn = getattr(lib, sym)
+        assert fn.restype is res and list(fn.argtypes) == list(args), sym
+    assert _half_lib.HalfHandle.NAME == "half" and issubclass(_half_lib.HalfHandle, _binding.Handle)
+    assert issubclass(_half_lib.HalfUnsupported, _lib.TomoError) and ha.HalfUnsupported is _half_lib.HalfUnsupported
+    import __graft_entry__ as entry
+    assert ("half", "_half_lib") in entry.LIBRARIES
+
+
+def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
+    _half_lib.load()
+    missing = str(tmp_path / "libtomo_half.so")
+    monkeypatch.setattr(_half_lib, "LIB_PATH", missing)
+    monkeypatch.delitem(_binding._loaded, "half")
+    with pytest.raises(_lib.TomoError) as e:
+        _half_lib.load()
+    text = str(e.value)
+    assert "libtomo_half.so not built" in text and missing in text
+    assert "`make -C tomography_alignment_amd/csrc/half`" in text
+    assert "half" not in _binding._loaded
+    monkeypatch.undo()
+    assert _half_lib.load() is _binding._loaded["half"]
+
+
+def test_the_library_refuses_what_it_does_not_take_with_the_reason():
+    cases = [((0, 64, 8, 1, 8), "even 2 <= n <= 65536"), ((7, 64, 8, 1, 8), "even 2 <= n <= 65536"), ((65538, 64, 8, 1, 8), "even 2 <= n <= 65536"),
+             ((8, 7, 8, 1, 0), "8 <= nx <= 16384"), ((8, 16385, 8, 1, 8), "8 <= nx <= 16384"), ((8, 64, 0, 1, 8), "1 <= nz <= 16384"),
+             ((8, 64, 16385, 1, 8), "1 <= nz <= 16384"), ((8, 64, 8, 4097, 8), "more than 4096"), ((8, 64, 8, 1, 3), "4 <= w <= nx / 2 = 32"),
+             ((8, 64, 8, 1, 33), "4 <= w <= nx / 2 = 32"), ((8, 9, 8, 1, 5), "4 <= w <= nx / 2 = 4")]
+    for args, why in cases:
+        with pytest.raises(_half_lib.HalfUnsupported, match=r"^libtomo_half error 4: tomo_half: .*" + why + ".*nothing was launched"):
+            _half_lib.check_shape(*args)
+    _half_lib.check_shape(2, 8, 1, 1, 4)
+    _half_lib.check_shape(65536, 16384, 16384, 4096, 8192)
+    _half_lib.check_shape(8, 64)                                         # no rows, no window: those of the stitch
+    with pytest.raises(_half_lib.HalfUnsupported):
+        _half_lib.scratch_bytes(64, 33)
+    with pytest.raises(_half_lib.HalfUnsupported):
+        _half_lib.batch(4097, 64, 8)
+    with pytest.raises(_half_lib.HalfUnsupported):
+        _half_lib.table(7, 3.0)
+
+
+def test_batches_follow_the_budget():
+    """The partials of one detector row: for both sides, one float64 per candidate and tile of TILE_J window columns."""
+    assert _half_lib.scratch_bytes(64, 12) == 8 * 2 * 2 * 53 and _half_lib.scratch_bytes(2048, 256) == 8 * 2 * 32 * 1793
+    per = _half_lib.scratch_bytes(64, 12)
+    assert _half_lib.batch(5, 64, 12, 0) == 5 and _half_lib.batch(5, 64, 12, 1) == 1 and _half_lib.batch(5, 64, 12, per) == 1
+    assert _half_lib.batch(5, 64, 12, 2 * per + 3) == 2 and _half_lib.batch(5, 64, 12, 100 * per) == 5
+
+
+def test_no_device_means_no_handle():
+    n = ctypes.c_int(0)
+    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
+        pytest.skip("a GPU is present")
+    h = _half_lib.HalfHandle.__new__(_half_lib.HalfHandle)
+    with pytest.raises(_lib.TomoError):
+        h.__init__(0)
+    assert h._h is None
+    h.close()
+    with pytest.raises(_lib.TomoError, match="half handle closed"):
+        h.handle
+
+
+# ---------------------------------------------------------------------------------------------------- refusals before any device
+
+class NoDevice(ha.HalfAcquisition):
+    """Fails the test if a refusal comes after the first step towards a device."""
+
+    def _ready(self, like):
+        raise AssertionError("a context or a handle was asked for")
+
+
+def test_find_center_360_checks_its_arguments_before_any_device():
+    p = np.zeros((12, 32, 4), np.float32)
+    bad = [(dict(win_width=3), ValueError, "win_width"), (dict(win_width=17), ValueError, "win_width"), (dict(win_width=8.0), ValueError, "win_width"),
+           (dict(win_width=True), ValueError, "win_width"), (dict(side="both"), ValueError, "side must be None, 'left' or 'right'"),
+           (dict(side=0), ValueError, "side"), (dict(angles=np.linspace(0, np.pi, 12, endpoint=False)), ValueError, "must span 2 pi"),
+           (dict(angles=np.linspace(0, 2 * np.pi, 12)), ValueError, "even number"), (dict(angles=np.zeros(5)), ValueError, "5 angles for 12"),
+           (dict(rows=[4]), ValueError, "rows must be in 0 ... 3"), (dict(rows=[-1]), ValueError, "rows"), (dict(rows=[]), ValueError, "rows"),
+           (dict(shape=(12, 32)), ValueError, r"\(n, nx, nz\)"), (dict(shape=(12, 32, 5)), ValueError, "holds"),
+           (dict(max_scratch_bytes=-1), ValueError, "max_scratch_bytes")]
+    for kw, exc, why in bad:
+        with pytest.raises(exc, match=why):
+            NoDevice().find_center_360(p, **kw)
+    with pytest.raises(ValueError, match="side"):
+        ha.find_center_360(p, side="middle")
+    with pytest.raises(ValueError, match="even number"):
+        NoDevice().find_center_360(p[:11])
+    with pytest.raises(ValueError, match="win_width"):
+        NoDevice().find_center_360(np.zeros((12, 7, 4), np.float32))                       # nx / 2 < 4: no window fits
+    for q, kw in ((np.zeros((65538, 8, 1), np.float32), dict(win_width=4)), (np.zeros((2, 16386, 1), np.float32), {}),
+                  (np.zeros((2, 8, 16385), np.float32), dict(win_width=4)), (np.zeros((2, 8, 4100), np.float32), dict(win_width=4, rows=np.arange(4097)))):
+        with pytest.raises(ha.HalfUnsupported, match="nothing was launched"):
+            NoDevice().find_center_360(q, **kw)
+
+
+def test_sino_360_to_180_checks_its_arguments_before_any_device():
+    p = np.zeros((12, 32, 4), np.float32)
+    bad = [(dict(center=-0.5), ValueError, "axis must lie on the detector"), (dict(center=31.2), ValueError, "axis must lie on the detector"),
+           (dict(center=float("nan")), ValueError, "axis must lie"), (dict(center="left"), ValueError, "center must be a number"),
+           (dict(center=20.0, angles=np.linspace(0, np.pi, 12)), ValueError, "must span 2 pi"),
+           (dict(center=20.0, out=np.zeros((6, 40, 4), np.float32)), ValueError, "out must hold the 6 x 41 x 4"),
+           (dict(center=20.0, out=np.zeros((6, 41, 4), np.float64)), ValueError, "out must hold"),
+           (dict(center=20.0, out=np.zeros((6, 4, 41), np.float32)), ValueError, "C-contiguous array of shape"),
+           (dict(center=20.0, out=np.zeros((6, 4, 41), np.float32).transpose(0, 2, 1)), ValueError, "C-contiguous"),
+           (dict(center=20.0, shape=(12, 128)), ValueError, r"\(n, nx, nz\)")]
+    for kw, exc, why in bad:
+        with pytest.raises(exc, match=why):
+            NoDevice().sino_360_to_180(p, **kw)
+    big = np.zeros((12 * 32 * 4 + 6 * 41 * 4,), np.float32)
+    with pytest.raises(ValueError, match="out overlaps proj"):
+        NoDevice().sino_360_to_180(big[:12 * 32 * 4].reshape(12, 32, 4), 20.0, out=big[6 * 41 * 4:2 * 6 * 41 * 4].reshape(6, 41, 4))
+    with pytest.raises(ValueError, match="even number"):
+        NoDevice().sino_360_to_180(p[:11], 20.0)
+    for q in (np.zeros((65538, 8, 1), np.float32), np.zeros((2, 16386, 1), np.float32), np.zeros((2, 8, 16385), np.float32)):
+        with pytest.raises(ha.HalfUnsupported, match="nothing was launched"):
+            NoDevice().sino_360_to_180(q, 5.0)
+    with pytest.raises(ValueError, match="win_width|axis"):
+        NoDevice().sino_360_to_180(np.zeros((2, 7, 1), np.float32), 7.0)
+    with pytest.raises(ha.HalfUnsupported, match="8 <= nx"):
+        NoDevice().sino_360_to_180(np.zeros((2, 7, 1), np.float32), 3.0)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the examples
+
+def test_generate_data_arguments():
+    assert generate_data.parse_args([]).half_acquisition is None
+    a = generate_data.parse_args(["--half-acquisition", "12", "--size", "48", "--angles", "24"])
+    assert a.half_acquisition == 12
+    for argv in (["--half-acquisition", "3"], ["--half-acquisition", "64"], ["--half-acquisition", "12", "--angles", "91"],
+                 ["--half-acquisition", "12", "--cor-offset", "2"], ["--half-acquisition", "x"], ["--half-acquisition"]):
+        with pytest.raises(SystemExit):
+            generate_data.parse_args(argv)
+    assert generate_data.half_acquisition_detector(48, 12) == (30, 23.5, -9.0)
+    assert generate_data.half_acquisition_detector(64, 9) == (37, 32.0, -14.0)
+    for size, ov in ((48, 12), (64, 9), (64, 8), (33, 4), (256, 255)):
+        nx, c, d = generate_data.half_acquisition_detector(size, ov)
+        h, W, j0 = ha.stitched_shape(2, nx, c)
+        assert W in (size, size + 1) and j0 == 0 and 2 * (nx - 1 - c) + 1 == ov and c == (nx - 1) / 2 - d
+    for bad in (3, 48, 12.0, True, None):
+        with pytest.raises(ValueError, match="half_acquisition"):
+            generate_data.half_acquisition_detector(48, bad)
+
+
+def test_examples_preprocess_half_acquisition_arguments():
+    assert ex_pre.parse_args(["raw.npz"]).half_acquisition is None
+    assert ex_pre.parse_args(["raw.npz", "--half-acquisition", "auto"]).half_acquisition == "auto"
+    assert ex_pre.parse_args(["raw.npz", "--half-acquisition", "23.5"]).half_acquisition == 23.5
+    for argv in (["raw.npz", "--half-acquisition"], ["raw.npz", "--half-acquisition", "-1"], ["raw.npz", "--half-acquisition", "nan"],
+                 ["raw.npz", "--half-acquisition", "right"], ["raw.npz", "--half-acquisition", "auto", "--find-center"],
+                 ["raw.npz", "--half-acquisition", "20", "--prealign"]):
+        with pytest.raises(SystemExit):
+            ex_pre.parse_args(argv)
+    data = dict(counts=np.zeros((4, 4, 16), np.uint16), flats=np.zeros((3, 4, 16), np.uint16), darks=np.zeros((2, 4, 16), np.uint16))
+    for bad in ("left", -1.0, float("nan"), True, [3.0]):
+        with pytest.raises(ValueError, match="half_acquisition must be"):
+            ex_pre.run(data, half_acquisition=bad)
+    with pytest.raises(ValueError, match="excludes find_center and prealign"):
+        ex_pre.run(dict(data, phi=np.linspace(0, 2 * np.pi, 4, endpoint=False)), half_acquisition="auto", find_center=True)
+    with pytest.raises(ValueError, match="must span 2 pi"):
+        ex_pre.run(dict(data, phi=np.linspace(0, np.pi, 4)), half_acquisition="auto")
+    with pytest.raises(ValueError, match="even number"):
+        ex_pre.run(dict(data, counts=data["counts"][:3]), half_acquisition=8.0)
+
+
+@pytest.fixture(scope="module")
+def oracle_make():
+    mp = pytest.MonkeyPatch()
+    mp.setattr(generate_data.projection_operators, "ProjectionMatrix", mm.OracleProjector)
+    try:
+        yield generate_data.make
+    finally:
+        mp.undo()
+
+
+def test_generate_data_without_the_option_is_unchanged(oracle_make):
+    a, b = oracle_make(32, 6, seed=4), oracle_make(32, 6, seed=4, half_acquisition=None)
+    assert sorted(a) == sorted(b) == sorted(["projections", "alpha", "beta", "xyz", "phi", "phantom", "cor_offset"])
+    for k in a:
+        assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
+    assert a["projections"].shape == (6, 32, 32) and np.array_equal(a["phi"], np.linspace(0.0, np.pi, 6)) and a["cor_offset"] == 0.0
+    raw = oracle_make(32, 6, seed=4, raw=True)
+    assert sorted(raw) == sorted(list(a) + ["counts", "flats", "darks", "mu"])
+    for k in a:
+        assert np.asarray(a[k]).tobytes() == np.asarray(raw[k]).tobytes(), k
+    for kw, why in ((dict(half_acquisition=3), "half_acquisition"), (dict(half_acquisition=8, cor_offset=1.0), "cor_offset must be 0"),
+                    (dict(half_acquisition=8, n_proj=7), "even number")):
+        with pytest.raises(ValueError, match=why):
+            oracle_make(32, **dict(dict(n_proj=6, seed=4), **kw))
+
+
+def test_generate_data_half_acquisition(oracle_make):
+    """The file of --half-acquisition 12 at size 48: 24 projections over [0, 2 pi) on 30 columns with the axis at column 23.5.  The model
+    finds that axis within 0.25 px on every detector row searched, and its stitch is the phantom's projection over [0, pi) on the 48
+    columns of the stitched detector with cor_shift = -(c_out - (W - 1) / 2) = 0 (the sign of rotation_axis.to_cor_shift)."""
+    d = oracle_make(48, 24, seed=0, ang_deg=0.0, shift_px=0.0, half_acquisition=12)
+    plain = oracle_make(48, 24, seed=0, ang_deg=0.0, shift_px=0.0)
+    assert sorted(d) == sorted(list(plain) + ["half_center", "half_overlap"])
+    assert d["projections"].shape == (24, 30, 48) and d["half_center"] == 23.5 and d["half_overlap"] == 12 and d["cor_offset"] == -9.0
+    assert np.array_equal(d["phi"], np.linspace(0, 2 * np.pi, 24, endpoint=False)) and np.array_equal(d["phantom"], plain["phantom"])
+    p = d["projections"]
+    centre, centres, sides, _, _ = hm.find_center_360(p, angles=d["phi"], rows=[16, 24, 32])
+    print("model on generate_data --half-acquisition 12: centres %s" % centres)
+    assert sides == ["right"] * 3 and np.all(np.abs(centres - 23.5) <= 0.25)
+    out, T = hm.stitch(p, 23.5, angles=d["phi"])
+    assert out.shape == (12, 48, 48) and T["c_out"] == 23.5
+    wide = mm.OracleProjector(generate_data.geometry.Geometry(12, np.array([48, 48, 48]), np.ones(3), np.array([48, 48]), np.ones(2)))
+    z = np.zeros(12)
+    ref = wide.projection_matrix(alpha=z, beta=z, phi=d["phi"][:12], xyz_shift=np.zeros((12, 3))).dot(d["phantom"].ravel()).reshape(12, 48, 48)
+    e = np.abs(out - ref).max() / ref.max()
+    print("model stitch against the full-width projection: %.2e of the maximum" % e)
+    assert e <= 1e-5                    # 2 c is an integer: copies and blends of two float32 projections of the same rays

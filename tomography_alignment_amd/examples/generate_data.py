@@ -29,6 +29,13 @@ beam_drift=A (--beam-drift A) lets the illumination move between the frames, wha
 every projection frame is multiplied by a beam profile 0.6 + 0.4 exp(-|r - c|^2 / (2 (0.6 nx)^2)) whose centre c lies uniform(-A, A) px
 from the frame's centre in x and in z (beam_profiles).  The draws come from a generator of their own, and n_flat (--flats N) says how
 many flats there are (default 10): with A = 0 every array is that of earlier versions for the same seed.
+half_acquisition=OV (--half-acquisition OV) writes a half-acquisition (offset-axis) scan, what half_acquisition.find_center_360 and
+sino_360_to_180 are for: an even number of projections over [0, 2 pi) without the endpoint, on a detector narrower than the volume whose
+rotation axis lies near its right edge, so that the projections at phi and phi + pi overlap by OV columns (half_acquisition_detector:
+nx = ceil((size + OV) / 2) columns, the axis at column c = nx - 1 - (OV - 1) / 2, i.e. Geometry(cor_shift=[(nx - 1) / 2 - c, 0, 0]); the
+stitched series then has 2 nx - OV = size or size + 1 columns).  The file holds c as `half_center` and OV as `half_overlap`, and
+`cor_offset` is the cor_shift used; these keys exist only with the option, and without it every key is that of earlier versions for the
+same seed.  OV should be at least the search window (8 columns by default).
 
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --out data.npz
     python -m tomography_alignment_amd.examples.generate_data --size 64 --angles 90 --raw --out raw.npz
@@ -158,17 +165,37 @@ def make_raw(proj, seed=None, i0=2e4, mu=None, n_flat=10, n_dark=5, dark_level=1
     return out
 
 
+def half_acquisition_detector(size, overlap):
+    """(nx, c, d) of a half-acquisition scan of a volume `size` wide whose halves overlap by `overlap` columns: the detector's columns,
+    the column of the axis (centre convention (nx - 1) / 2, right of the centre) and the x component of Geometry's cor_shift that puts
+    it there, (nx - 1) / 2 - c."""
+    if isinstance(overlap, (bool, np.bool_)) or not isinstance(overlap, (int, np.integer)) or not 4 <= overlap < size:
+        raise ValueError("half_acquisition must be an integer overlap in 4 ... size - 1 = %d columns, got %r" % (size - 1, overlap))
+    nx = (int(size) + int(overlap) + 1) // 2
+    c = nx - 1 - (int(overlap) - 1) / 2.0
+    return nx, c, (nx - 1) / 2.0 - c
+
+
 def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, propagate=None, dead_columns=0, gain_columns=0,
-         zingers=0, cor_offset=0.0, beam_drift=0.0, n_flat=10):
+         zingers=0, cor_offset=0.0, beam_drift=0.0, n_flat=10, half_acquisition=None):
     cor_offset = float(cor_offset)
     if not np.isfinite(cor_offset):
         raise ValueError("cor_offset must be finite, got %r" % (cor_offset,))
+    half = None
+    if half_acquisition is not None:
+        half = half_acquisition_detector(size, half_acquisition)
+        if cor_offset:
+            raise ValueError("half_acquisition chooses the axis itself: cor_offset must be 0, got %r" % (cor_offset,))
+        if n_proj < 2 or n_proj % 2:
+            raise ValueError("half_acquisition needs an even number of projections over 2 pi, got %d" % n_proj)
+        cor_offset = half[2]
     rng = np.random.RandomState(seed)
     nx = ny = nz = size
+    ndx = nx if half is None else half[0]                               # detector columns
     shepp = generate_phantom.shepp3d(nx)
-    geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([nx, nz]), np.ones(2),
+    geom = geometry.Geometry(n_proj, np.array([nx, ny, nz]), np.ones(3), np.array([ndx, nz]), np.ones(2),
                              cor_shift=np.array([cor_offset, 0.0, 0.0]) if cor_offset else None)
-    phi = np.linspace(0.0, np.pi, n_proj)
+    phi = np.linspace(0.0, np.pi, n_proj) if half is None else np.linspace(0.0, 2.0 * np.pi, n_proj, endpoint=False)
     a100, s100 = int(round(100 * ang_deg)), int(round(100 * shift_px))
     jitter = lambda m: rng.randint(-m, m, n_proj) / 100 if m > 0 else np.zeros(n_proj)      # noqa: E731 (m = 0: nominal poses)
     alpha = np.deg2rad(jitter(a100))                                    # examples/generate_data.py:17-18
@@ -178,8 +205,10 @@ def make(size=64, n_proj=90, seed=None, ang_deg=1.0, shift_px=2.0, raw=False, pr
     xyz[:, 2] = jitter(s100)
     proj_obj = projection_operators.ProjectionMatrix(geom, precision=np.float32)
     pmat = proj_obj.projection_matrix(alpha=alpha, beta=beta, phi=phi, xyz_shift=xyz)
-    proj = pmat.dot(shepp.ravel()).reshape(n_proj, nx, nz)              # :29
+    proj = pmat.dot(shepp.ravel()).reshape(n_proj, ndx, nz)             # :29
     d = dict(projections=proj, alpha=alpha, beta=beta, xyz=xyz, phi=phi, phantom=shepp, cor_offset=np.float64(cor_offset))
+    if half is not None:
+        d.update(half_center=np.float64(half[1]), half_overlap=np.int64(half_acquisition))
     if raw:
         d.update(make_raw(proj, seed=None if seed is None else seed + 1, propagate=propagate, dead_columns=dead_columns,
                           gain_columns=gain_columns, zingers=zingers, beam_drift=beam_drift, n_flat=n_flat))
@@ -207,7 +236,16 @@ def parse_args(argv=None):
     ap.add_argument("--beam-drift", type=float, default=0.0, metavar="A",
                     help="with --raw: the beam's centre jitters by +-A px between the frames (preprocess.normalize_dynamic)")
     ap.add_argument("--flats", type=int, default=10, metavar="N", help="with --raw: how many flat frames (default 10)")
+    ap.add_argument("--half-acquisition", type=int, default=None, metavar="OV", help="a half-acquisition scan over 2 pi on a detector of "
+                    "ceil((size + OV) / 2) columns whose halves overlap by OV columns (an even --angles)")
     a = ap.parse_args(argv)
+    if a.half_acquisition is not None:
+        if not 4 <= a.half_acquisition < a.size:
+            ap.error("--half-acquisition must be an overlap of 4 ... size - 1 columns")
+        if a.cor_offset:
+            ap.error("--half-acquisition chooses the axis itself: leave --cor-offset out")
+        if a.angles < 2 or a.angles % 2:
+            ap.error("--half-acquisition needs an even number of --angles")
     if not (0 <= a.beam_drift < float("inf")):
         ap.error("--beam-drift must be finite and >= 0")
     if a.beam_drift and not a.raw:
@@ -230,7 +268,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     d = make(a.size, a.angles, a.seed, ang_deg=a.tilt_deg, shift_px=a.shift_px, raw=a.raw, propagate=a.propagate, dead_columns=a.dead_columns, gain_columns=a.gain_columns,
-             zingers=a.zingers, cor_offset=a.cor_offset, beam_drift=a.beam_drift, n_flat=a.flats)
+             zingers=a.zingers, cor_offset=a.cor_offset, beam_drift=a.beam_drift, n_flat=a.flats, half_acquisition=a.half_acquisition)
     np.savez(a.out, **d)
     print("wrote %s: projections %s, phantom %s" % (a.out, d["projections"].shape, d["phantom"].shape))
 

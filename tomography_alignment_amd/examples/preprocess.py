@@ -32,6 +32,15 @@ the flats' eigenvalues call for -- weighted per projection for the least total v
 ((n, m)).  It takes the place of normalize, before the phase retrieval too, and needs --method mean.  Without it the calls and the
 result are exactly what they were.
 
+`--half-acquisition auto|C` is for half-acquisition (offset-axis) scans over 2 pi (generate_data --half-acquisition): after the stripe
+removal the rotation axis is found on the finished sinogram, where it lies on the device (half_acquisition.find_center_360 on
+--center-rows detector rows, the median), or taken to lie at the detector column C; the series is stitched to the pi series of double
+width (half_acquisition.sino_360_to_180), and the file gets the stitched `projections`, the first half of `phi`, `alpha`, `beta` and
+`xyz`, the axis on the unstitched detector as `half_axis`, and `cor_offset`: the x component of Geometry's cor_shift for the stitched
+series, -(c_out - (W - 1) / 2), the number align_rigid's --cor takes.  The stitch pairs the projections i and i + n / 2, so it assumes
+that they share a pose: it suits data whose jitter is below a pixel, or data aligned beforehand.  It excludes --find-center and
+--prealign, which take pi series (run them on the stitched file).  Without it the calls and the result are exactly what they were.
+
 The counts are uploaded once in their own dtype; the sinogram stays on the device from normalisation through stripe removal, which runs
 on the full stack on one GPU (it needs every angle of a column).
 
@@ -46,7 +55,7 @@ import argparse
 
 import numpy as np
 
-from .. import _lib, preprocess, rotation_axis
+from .. import _lib, half_acquisition as half_acq, preprocess, rotation_axis
 from ..align import consistency
 
 RAW_KEYS = ("counts", "flats", "darks", "mu", "dead_cols", "gain_cols", "zinger_mask")
@@ -64,7 +73,7 @@ def la_size_for(nx, la_size=None):
 
 
 def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, verbose=False, phase=None, stripe="sorting", stripe_snr=3.0,
-        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9, prealign=None, dynamic_flat=None):
+        la_size=None, zinger_dif=None, zinger_size=3, find_center=False, center_rows=9, prealign=None, dynamic_flat=None, half_acquisition=None):
     """The dict of `data` with `projections` ((n_proj, nx, nz) float32) in place of the raw keys.  stripe_size: the window of the stripe
     removal, or 0 / None to skip it.  phase: None, or a dict of preprocess.retrieve_phase's keywords (strength, or pixel_size, dist,
     energy / wavelength, delta_beta; pad, min_ratio, max_scratch_bytes): the phase retrieval before the -log.  stripe: 'sorting' (the
@@ -74,7 +83,20 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
     docstring), searched on center_rows detector rows.  prealign: None, or 'moment' / 'profile': stores consistency.estimate_shifts'
     xyz0, axis_offset and mass_spread of the finished sinogram (module docstring).  dynamic_flat: None, or 'auto' / an integer >= 0:
     preprocess.normalize_dynamic with that many eigen flat fields ('auto': chosen from the flats' eigenvalues) in place of normalize;
-    stores the weights as `flat_weights`."""
+    stores the weights as `flat_weights`.  half_acquisition: None, or 'auto' / the detector column of the rotation axis: the finished
+    series over 2 pi is stitched to the pi series of double width about the axis found ('auto', on center_rows detector rows) or given;
+    stores the stitched projections, the first half of phi, alpha, beta and xyz, `half_axis` and `cor_offset` (module docstring)."""
+    if half_acquisition is not None:
+        if half_acquisition != "auto":
+            if isinstance(half_acquisition, (bool, np.bool_, str)) or not isinstance(half_acquisition, (int, float, np.integer, np.floating)) \
+                    or not (np.isfinite(half_acquisition) and half_acquisition >= 0):
+                raise ValueError("preprocess: half_acquisition must be None, 'auto' or the column of the axis, a number >= 0, got %r"
+                                 % (half_acquisition,))
+        if find_center or prealign is not None:
+            raise ValueError("preprocess: half_acquisition excludes find_center and prealign, which take a series over pi: run them on "
+                             "the stitched data")
+        if "counts" in data:
+            half_acq.angle_span(data.get("phi"), np.shape(data["counts"])[0])
     if dynamic_flat is not None:
         if dynamic_flat != "auto" and (isinstance(dynamic_flat, (bool, np.bool_)) or not isinstance(dynamic_flat, (int, np.integer))
                                        or dynamic_flat < 0):
@@ -140,6 +162,20 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         if prealign is not None:
             with consistency.Consistency(ctx) as c:
                 est = c.estimate_shifts(sino, np.asarray(data["phi"], np.float64), vertical=prealign)
+        half = None
+        if half_acquisition is not None:
+            phi = np.asarray(data["phi"], np.float64) if "phi" in data else None
+            with half_acq.HalfAcquisition(ctx) as ha:
+                if half_acquisition == "auto":
+                    half_found = ha.find_center_360(sino, angles=phi, rows=rotation_axis.spread_rows(sino.shape[2], center_rows))
+                    half_axis = half_found.center
+                else:
+                    half_found, half_axis = None, float(half_acquisition)
+                half = ha.sino_360_to_180(sino, half_axis, angles=phi)
+                stitched = half.projections
+                ctx.sync()                                                                               # before the handle's table goes
+            sino.free()
+            sino = stitched
         proj = sino.download()
     finally:
         for d in (d_frames, sino):
@@ -156,6 +192,12 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
         out["flat_weights"] = flat_weights
     if cor is not None:
         out["cor_offset"] = np.float64(cor)
+    if half is not None:
+        nh = proj.shape[0]
+        for k in ("phi", "alpha", "beta", "xyz"):
+            if k in out:
+                out[k] = np.asarray(out[k])[:nh]
+        out.update(half_axis=np.float64(half_axis), cor_offset=np.float64(-half.cor_offset))
     if est is not None:
         out.update(xyz0=est.xyz0, axis_offset=np.float64(est.axis_offset), mass_spread=np.float64(est.mass_spread))
     if verbose:
@@ -169,6 +211,8 @@ def run(data, stripe_size=21, method="mean", cutoff=None, crop=None, ctx=None, v
             print("preprocess: rotation axis at cor_offset %+.3f px (offsets per row %s)" % (cor, found.offsets.tolist()))
         if est is not None:
             print("preprocess: pre-alignment %r" % (est,))
+        if half is not None:
+            print("preprocess: half acquisition, axis at column %.3f (%s) -> %r" % (half_axis, half_found if half_found is not None else "given", half))
     return out
 
 
@@ -201,7 +245,19 @@ def parse_args(argv=None):
     ap.add_argument("--dynamic-flat", nargs="?", const="auto", default=None, metavar="M",
                     help="a flat per projection from M eigen flat fields of the flats (no number: as many as their eigenvalues call for); "
                     "stores the weights as flat_weights")
+    ap.add_argument("--half-acquisition", default=None, metavar="auto|C",
+                    help="stitch a half-acquisition scan over 2 pi to the pi series of double width about the axis found (auto) or at the "
+                    "detector column C; stores half_axis and cor_offset")
     a = ap.parse_args(argv)
+    if a.half_acquisition is not None and a.half_acquisition != "auto":
+        try:
+            a.half_acquisition = float(a.half_acquisition)
+        except ValueError:
+            ap.error("--half-acquisition takes 'auto' or the detector column of the axis")
+        if not 0 <= a.half_acquisition < float("inf"):
+            ap.error("--half-acquisition must be a finite column >= 0")
+    if a.half_acquisition is not None and (a.find_center or a.prealign is not None):
+        ap.error("--half-acquisition excludes --find-center and --prealign: run them on the stitched file")
     if a.dynamic_flat is not None and a.dynamic_flat != "auto":
         try:
             a.dynamic_flat = int(a.dynamic_flat)
@@ -246,7 +302,8 @@ def main(argv=None):
     a = parse_args(argv)
     d = run(dict(np.load(a.data)), stripe_size=a.stripe_size, method=a.method, cutoff=a.cutoff, crop=a.crop, verbose=True, phase=a.phase,
             stripe=a.stripe, stripe_snr=a.stripe_snr, la_size=a.stripe_la_size, zinger_dif=a.zinger_dif, zinger_size=a.zinger_size,
-            find_center=a.find_center, center_rows=a.center_rows, prealign=a.prealign, dynamic_flat=a.dynamic_flat)
+            find_center=a.find_center, center_rows=a.center_rows, prealign=a.prealign, dynamic_flat=a.dynamic_flat,
+            half_acquisition=a.half_acquisition)
     np.savez(a.out, **d)
     print("wrote %s" % a.out)
 
