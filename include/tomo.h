@@ -93,20 +93,29 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *                  3 as 2 with four gathers per sample: the upper-z corners come from the neighbouring lane (DPP wave
  *                    shift) -- nearly insensitive to tilt, fastest beyond |alpha| + |beta| ~ 1 deg;
  *                  4 (default) each pose of a call takes 2 or 3 by its tilt (two launches)
- *   "tile_flat"   1 (default): untilted projections (alpha = beta = 0, detector-z pitch 1) take the flat tile kernels
+ *   "tile_flat"   1 (default): untilted projections (alpha = beta = 0 and detector-z pitch exactly 1 voxel: the detector-z step is
+ *                 the volume's z axis in 32.32 fixed point; any detector-x pitch and step) take the flat tile kernels
  *   "fwd_flat_ztiles" 2 (default): the flat forward kernel owns two z-adjacent tiles per work-group and builds each detector
  *                 row's sample table once for both; 1: one tile per work-group
  *   "fwd_flat_tab" 1 (default): the flat forward over 16 x 16 x 128-voxel blocks with the two 64-plane images interleaved per plane and
  *                 each row's weights in an LDS table (k_fwd_flat_tab), run over the blocks that hold a non-zero voxel only; 0: the round-2
  *                 kernel (entries broadcast with v_readlane)
- *   "fwd_flat_gather" 1 (default): a whole-volume tomo_forward call ALL of whose poses qualify for the gather adjoint with step >= 0.95
- *                 voxel (untilted, detector pitch = voxel), on a volume of at most 4 GiB with nx, ny <= 8192, takes the gather-form forward (k_fwd_gather_flat:
- *                 rays keep their sums in registers, no atomics, the same bits on every run).  Calls that do not qualify, tomo_forward_xslab
- *                 and value 0 keep k_fwd_flat_tab; needs "adj_flat_gather" 1 (the two kernels share their per-projection constants)
+ *   "fwd_flat_gather" 1 (default): a whole-volume tomo_forward call ALL of whose poses qualify for the gather adjoint (below) with
+ *                 (|cos phi| + |sin phi|) / step < 1.49, step * max(|cos phi|, |sin phi|) >= 0.67 and step * min(|cos phi|, |sin phi|) < 0.999
+ *                 voxel -- at every phi for 0.95 <= step <= 1.41 -- on a volume of at most 4 GiB with nx, ny <= 8192, takes the gather-form
+ *                 forward (k_fwd_gather_flat: rays keep their sums in registers, no atomics, the same bits on every run).  The detector-x
+ *                 pitch enters only through the gather adjoint's rule: every ray is walked on its own, and rows that lie further apart only
+ *                 spread a wave over more windows of volume lines.
+ *                 Calls that do not qualify, tomo_forward_xslab and value 0 keep k_fwd_flat_tab; needs "adj_flat_gather" 1 (the two
+ *                 kernels share their per-projection constants)
  *   "fwd_flat_wide" 0 (default); 1: measurement variant of the flat forward with a 32 x 16 x 63 tile footprint and one image
  *                 per work-group (half the tile crossings, hence half the sinogram atomics; whole-volume calls only)
- *   "adj_flat_gather" 1 (default): untilted projections on a unit lattice (detector pitch = step = voxel) take the gather-form
- *                 adjoint (accumulators in registers, no atomics) instead of the LDS-atomic flat tile kernel
+ *   "adj_flat_gather" 1 (default): untilted projections (as for "tile_flat") whose x-y lattice is coarse enough take the gather-form
+ *                 adjoint (accumulators in registers, no atomics) instead of the LDS-atomic flat tile kernel: three consecutive detector
+ *                 rows must cover a voxel's footprint, (|cos phi| + |sin phi|) / det_dx < 1.45, and six consecutive samples,
+ *                 (|cos phi| + |sin phi|) / step < 2.99.  Detector-x pitch = step = voxel meets both at any phi (sum <= sqrt 2); so does
+ *                 every COARSER detector (pitch 1.25, 2, ...).  A finer one qualifies per pose: at det_dx = 0.8 only within 10 degrees of
+ *                 an axis, so one call can run both kernels; at det_dx < 0.69 never
  *   "reuse_staged_volume" 1: the caller vouches that the volume passed to tomo_proj_grad / tomo_cost_grad / the ray-driven
  *                 forward has not changed since the previous such call with the same pointer, so its zero-padded staging
  *                 copy is reused (alignment loops evaluate hundreds of poses against one volume); default 0

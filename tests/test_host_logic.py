@@ -58,12 +58,12 @@ def test_no_gpu_means_loud_failure(built_lib):
 def test_geometry_check_guards_without_a_gpu(built_lib):
     """tomo_check_geometry (the validation inside tomo_set_geometry) runs on the host: bad shapes, the 2^31-voxel limit, and
     the wide-row flag that keeps the 24-bit-multiply kernels away from slabs whose x-row pitch is >= 2^23 bytes."""
-    def check(shape, ndet=(8, 8), step=1.0):
+    def check(shape, ndet=(8, 8), step=1.0, det_dx=1.0, det_dz=1.0):
         g = _lib.TomoGeom()
         g.nx, g.ny, g.nz = shape
         g.ndx, g.ndz = ndet
         g.src_y, g.det_y, g.step = -10.0, 10.0, step
-        g.det_dx = g.det_dz = 1.0
+        g.det_dx, g.det_dz = det_dx, det_dz
         flags = ctypes.c_int(-1)
         return built_lib.tomo_check_geometry(ctypes.byref(g), ctypes.byref(flags)), flags.value
     assert check((64, 64, 64)) == (0, 0)
@@ -76,6 +76,13 @@ def test_geometry_check_guards_without_a_gpu(built_lib):
     g.src_y, g.det_y, g.step, g.det_dx, g.det_dz = -32.0, 32.0, 1.0, 1.0, 1.5      # detector-z pitch > 1 voxel: plain kernels too
     fl = ctypes.c_int(0)
     assert built_lib.tomo_check_geometry(ctypes.byref(g), ctypes.byref(fl)) == 0 and fl.value == _lib.GEOM_WIDE_ROWS
+    # ... and only that: a finer detector, or one whose pitch is 1 up to the rounding of a difference of linspace values, keeps the 24-bit kernels;
+    # the detector-x pitch never matters here
+    for dz in (0.5, 1.0, 1.0 + 1e-12):
+        assert check((64, 64, 64), det_dz=dz) == (0, 0), dz
+    for dz in (1.25, 2.0):
+        assert check((64, 64, 64), det_dz=dz) == (0, _lib.GEOM_WIDE_ROWS), dz
+    assert check((64, 64, 64), det_dx=2.0) == (0, 0) and check((64, 64, 64), det_dx=0.5, det_dz=0.5) == (0, 0)
     # sample step > 1 voxel: in-block cells leave the +-17 range the biased unsigned offsets of the SGPR-base kernels cover
     assert check((64, 64, 64), step=1.0) == (0, 0) and check((64, 64, 64), step=0.5) == (0, 0)
     assert check((64, 64, 64), step=1.3) == (0, _lib.GEOM_WIDE_ROWS) and check((64, 64, 64), step=6.0) == (0, _lib.GEOM_WIDE_ROWS)

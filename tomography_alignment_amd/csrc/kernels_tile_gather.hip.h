@@ -1,9 +1,15 @@
-// kernels_tile_gather.hip.h -- the GATHER-form adjoint for untilted unit lattices (k_adj_gather_flat<NJ>): no atomics, each voxel
+// kernels_tile_gather.hip.h -- the GATHER-form adjoint for untilted, coarse enough lattices (k_adj_gather_flat<NJ>): no atomics, each voxel
 // written once.  Needs kernels_tile.hip.h (helpers) before it; part of the translation unit tomo_project.hip.
 
 // ------------------------------------------------------------------------------------------------
-// GATHER-form adjoint for untilted unit lattices (the poses of a plain parallel-beam scan: alpha = beta = 0, detector pitch =
-// step = voxel; any phi, translation, COR shift).  For such a lattice the adjoint separates:
+// GATHER-form adjoint for untilted poses (alpha = beta = 0 and detector-z pitch exactly one voxel: every sample has z = iz + zc + tau;
+// any phi, translation, COR shift) whose x-y lattice p = p0 + ix u + j d, with (ix, j) = M ((x, y) - p0), meets the rule of
+// stage_tile_consts (tomo_project.hip):
+//     |m00| + |m01| = (|cos phi| + |sin phi|) / det_dx < 1.45     three consecutive rows cover a voxel's footprint; a tile touches <= GROWS rows
+//     |m10| + |m11| = (|cos phi| + |sin phi|) / step   < 2.99     NJ = 6 consecutive samples of a row cover it (< 1.49: NJ = 3)
+// The plain parallel-beam scan (detector pitch = step = voxel) meets it at any phi; so does any coarser detector (tested at pitch 1.25
+// and 2), a finer one only near the axes (pitch 0.8: within 10 degrees).  Nothing below assumes more than that rule: positions and
+// tents come from the lattice constants.  For such a lattice the adjoint separates:
 //     (A^T y)(X, Y, Z) = sum_ix  W(X, Y, ix) * Yz(ix, Z)
 //     Yz(ix, Z)   = (1 - tau) y[ix, Z - zc] + tau y[ix, Z - zc - 1]                 (every sample has z = iz + zc + tau)
 //     W(X, Y, ix) = sum_{j in [0, n)} tent(px(ix, j) - X) * tent(py(ix, j) - Y)       (tent(r) = 1 - |r| on [-1, 1))
@@ -452,7 +458,12 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
 //   3. lane = RAY again: per four planes NW ds_read_b128 at row(lane) + immediate and 2 NW v_pk_fma_f32.
 // Rays of eight different projections drift apart with the distance from the rotation centre (tools/fwd_gather_model.py): a slab whose
 // lanes span more than FGROWS lines is done in WINDOWS of FGROWS lines advancing by FGROWS - NW + 1 (a lane's NW lines lie in exactly
-// one window); the first window rides the pipelined loads, the others (rare at FGROWS = 24) load on the spot.
+// one window); the first window rides the pipelined loads, the others (rare at FGROWS = 24 and detector pitch 1) load on the spot.
+// Which calls come here is forward_tiles' rule (tomo_project.hip): every pose takes the gather adjoint (above: that is where the detector-x
+// pitch enters), 2 / |d_S| + slack < 3 and |d_L| < 1 with d the sample step along the walked and the other axis, i.e.
+// step max(|cos|, |sin|) >= 0.67 and step min(|cos|, |sin|) < 0.999, and (|cos| + |sin|) / step < 1.49.  The detector-x pitch itself is
+// free: a ray is walked on its own; with rows det_dx voxels apart a wave's eight rows spread over det_dx times as many lines and more
+// steps take a second or third window (pitch 2: 7 steps in 10 on the second-window case of tests/test_gpu_pitch.py).
 // The z lerp comes last, once per ray.  The sinogram is zero-filled by the caller: a wave stores its rays' 63 (tau != 0) or 64 values
 // with plain stores; the value that also needs the next chunk's first plane is completed by one atomic from each of the two waves
 // (0 + a + b = 0 + b + a: still the same bits on every run).
