@@ -95,11 +95,10 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *                  4 (default) each pose of a call takes 2 or 3 by its tilt (two launches)
  *   "tile_flat"   1 (default): untilted projections (alpha = beta = 0 and detector-z pitch exactly 1 voxel: the detector-z step is
  *                 the volume's z axis in 32.32 fixed point; any detector-x pitch and step) take the flat tile kernels
- *   "fwd_flat_ztiles" 2 (default): the flat forward kernel owns two z-adjacent tiles per work-group and builds each detector
- *                 row's sample table once for both; 1: one tile per work-group
- *   "fwd_flat_tab" 1 (default): the flat forward over 16 x 16 x 128-voxel blocks with the two 64-plane images interleaved per plane and
- *                 each row's weights in an LDS table (k_fwd_flat_tab), run over the blocks that hold a non-zero voxel only; 0: the round-2
- *                 kernel (entries broadcast with v_readlane)
+ *   "fwd_flat_ztiles" 2 (default): on a volume of two or more z tiles (more than 62 planes) the flat forward runs over 16 x 16 x 128-voxel
+ *                 blocks -- two 64-plane images interleaved per plane, each detector row's weights built once for both in an LDS table
+ *                 (k_fwd_flat_tab) -- and over the blocks that hold a non-zero voxel only; 1, and smaller volumes: one tile per
+ *                 work-group (k_tile_flat)
  *   "fwd_flat_gather" 1 (default): a whole-volume tomo_forward call ALL of whose poses qualify for the gather adjoint (below) with
  *                 (|cos phi| + |sin phi|) / step < 1.49, step * max(|cos phi|, |sin phi|) >= 0.67 and step * min(|cos phi|, |sin phi|) < 0.999
  *                 voxel -- at every phi for 0.95 <= step <= 1.41 -- on a volume of at most 4 GiB with nx, ny <= 8192, takes the gather-form
@@ -108,8 +107,6 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *                 spread a wave over more windows of volume lines.
  *                 Calls that do not qualify, tomo_forward_xslab and value 0 keep k_fwd_flat_tab; needs "adj_flat_gather" 1 (the two
  *                 kernels share their per-projection constants)
- *   "fwd_flat_wide" 0 (default); 1: measurement variant of the flat forward with a 32 x 16 x 63 tile footprint and one image
- *                 per work-group (half the tile crossings, hence half the sinogram atomics; whole-volume calls only)
  *   "adj_flat_gather" 1 (default): untilted projections (as for "tile_flat") whose x-y lattice is coarse enough take the gather-form
  *                 adjoint (accumulators in registers, no atomics) instead of the LDS-atomic flat tile kernel: three consecutive detector
  *                 rows must cover a voxel's footprint, (|cos phi| + |sin phi|) / det_dx < 1.45, and six consecutive samples,

@@ -10,7 +10,6 @@ from conftest import golden, rel_max, rel_l2, g10_case, grad_dev_per_ray, FACE_T
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-TAB_DEFAULT = 1      # the library's default for option fwd_flat_tab
 
 
 def geo_pair(n_proj, N, cor_shift=None, step=1.0, ndet=None, shape=None):
@@ -422,12 +421,13 @@ def test_untilted_poses_take_the_flat_tile_kernels(PM, orc, shape, ndet):
 @pytest.mark.parametrize("shape,ndet,step", [((40, 36, 130), (44, 150), 1.0), ((70, 33, 64), (70, 64), 1.0), ((33, 20, 70), (30, 80), 1.0),
                                              ((40, 36, 130), (44, 150), 0.5), ((20, 24, 200), (20, 190), 0.75), ((24, 20, 300), (24, 310), 1.0)])
 def test_flat_forward_kernel_variants(PM, orc, shape, ndet, step):
-    """The variants of the flat forward -- the round-2 kernel (entries broadcast with v_readlane, option fwd_flat_tab = 0), the round-3
-    kernel (sample table in LDS, the two images interleaved per plane: fwd_flat_tab = 1) and the 32 x 16-footprint measurement variant
-    (fwd_flat_wide, HISTORY.md section 4 "forward write amplification") -- compute the same projections as each other and as the
-    oracle: volumes whose x extent is not a multiple of 32, exactly degenerate angles, translations, COR shifts, and steps below a
-    voxel (rows with more samples in a tile than one pass of the table holds); z extents of one to three of the round-3 kernel's
-    128-plane work-groups with fractional z translations (the ray between two work-groups receives a part from each)."""
+    """The kernels an untilted forward projection can take, each pinned by its options -- "tab": k_fwd_flat_tab (blocks of two z-adjacent
+    64-plane images, sample table in LDS; fwd_flat_gather = 0), "one tile": k_tile_flat<true> (fwd_flat_gather = 0, fwd_flat_ztiles = 1),
+    "default": the gather forward where all poses qualify (the four shapes at step 1), else k_fwd_flat_tab -- compute the same projections
+    as each other and as the oracle: volumes whose x extent is not a multiple of 32, exactly degenerate angles, translations, COR shifts,
+    and steps below a voxel (rows with more samples in a tile than one pass of the table holds); z extents of one to three of
+    k_fwd_flat_tab's 128-plane work-groups with fractional z translations (the ray between two work-groups receives a part from each)."""
+    from tomography_alignment_amd import _lib
     rng = np.random.default_rng(7)
     n_proj = 5
     phi = np.array([0.0, 0.37, np.pi / 2, 2.2, np.pi])
@@ -436,43 +436,44 @@ def test_flat_forward_kernel_variants(PM, orc, shape, ndet, step):
     cor[:, 0] = rng.uniform(-1.5, 1.5, n_proj)
     geo, og = geo_pair(n_proj, None, shape=shape, ndet=ndet, cor_shift=cor, step=step)
     x = rng.uniform(0.1, 1.0, shape).astype(np.float32)
-    P = PM(geo)
-    A = P.projection_matrix(phi=phi, xyz_shift=xyz)
-    ctx = P.backend.ctx
-    want = orc.forward(og, x, phi=phi, xyz_shift=xyz).ravel()
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    res = {}
-    for tab in (0, 1):
-        ctx.set_option("fwd_flat_tab", tab)
-        res[tab] = A.dot(x.ravel())
-    # the 32 x 16-footprint variant exists only in measurement builds (make EXTRA=-DTOMO_MEASUREMENT_VARIANTS, round 5): the product library
-    # refuses the option by name
-    from tomography_alignment_amd import _lib
-    n_variants = 2
-    try:
-        ctx.set_option("fwd_flat_wide", 1)
-        f_wide = A.dot(x.ravel())
-        ctx.set_option("fwd_flat_wide", 0)
-        n_variants = 3
-    except _lib.TomoError as e:
-        assert "measurement variant" in str(e)
-        f_wide = res[1]
-    ctx.set_option("fwd_flat_tab", TAB_DEFAULT)
-    ctx.profile_enable(False)
-    assert ctx.profile_get("k_fwd_tile_flat")[0] == n_variants and ctx.profile_get("k_fwd_tile")[0] == 0
-    assert rel_max(res[0], want) < TOL and rel_max(res[1], want) < TOL and rel_max(f_wide, want) < TOL
-    assert rel_max(res[1], res[0]) < 2e-6 and rel_max(f_wide, res[0]) < 2e-6
-    # all-zero images beside non-zero ones (the kernels skip them): the ray between two images / two work-groups of the round-3 kernel
+    # all-zero images beside non-zero ones (the kernels skip them): the ray between two images / two work-groups of k_fwd_flat_tab
     # must still receive the part of the one that is not zero (planes 0..63 empty, 64..99 full, 100..127 empty, 128.. full)
     xs = x.copy()
     xs[:, :, :64] = 0
     xs[:, :, 100:128] = 0
-    want_s = orc.forward(og, xs, phi=phi, xyz_shift=xyz).ravel()
-    for tab in (0, 1):
-        ctx.set_option("fwd_flat_tab", tab)
-        assert rel_max(A.dot(xs.ravel()), want_s) < TOL, tab
-    ctx.set_option("fwd_flat_tab", TAB_DEFAULT)
+    P = PM(geo)
+    A = P.projection_matrix(phi=phi, xyz_shift=xyz)
+    ctx = P.backend.ctx
+    variants = {"tab": {"fwd_flat_gather": 0, "fwd_flat_ztiles": 2}, "one tile": {"fwd_flat_gather": 0, "fwd_flat_ztiles": 1},
+                "default": {"fwd_flat_gather": 1, "fwd_flat_ztiles": 2}}
+    ctx.profile_reset()
+    ctx.profile_enable(True)
+    n_calls = 0
+    try:
+        for vol in (x, xs):
+            want = orc.forward(og, vol, phi=phi, xyz_shift=xyz).ravel()
+            res = {}
+            for name, opts in variants.items():
+                for key, value in opts.items():
+                    ctx.set_option(key, value)
+                res[name] = A.dot(vol.ravel())
+                n_calls += 1
+            for name in variants:
+                err = rel_max(res[name], want)
+                print("%s, %s volume: vs oracle %.2e, vs tab %.2e" % (name, "dense" if vol is x else "sparse", err, rel_max(res[name], res["tab"])))
+                assert err < TOL, name
+            assert rel_max(res["one tile"], res["tab"]) < 2e-6 and rel_max(res["default"], res["tab"]) < 2e-6
+            assert rel_max(res["default"], res["one tile"]) < 2e-6
+    finally:
+        for key, value in variants["default"].items():      # the library's defaults
+            ctx.set_option(key, value)
+        ctx.profile_enable(False)
+    assert ctx.profile_get("k_fwd_tile_flat")[0] == n_calls == 6 and ctx.profile_get("k_fwd_tile")[0] == 0
+    # the options of the kernel generation that k_fwd_flat_tab replaced are gone: unknown keys are an error
+    with pytest.raises(_lib.TomoError):
+        ctx.set_option("fwd_flat_tab", 1)
+    with pytest.raises(_lib.TomoError):
+        ctx.set_option("fwd_flat_wide", 0)
 
 
 @pytest.mark.parametrize("tilted", [False, True])

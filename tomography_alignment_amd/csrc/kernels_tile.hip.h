@@ -102,13 +102,6 @@ __device__ __forceinline__ float select_lanes(float v, unsigned long long m)
     return r;
 }
 
-__device__ __forceinline__ unsigned select_lanes_u(unsigned v, unsigned long long m)
-{
-    unsigned r;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(v), "s"(m));
-    return r;
-}
-
 // acc + v in the lanes whose bit is set in the wave-uniform mask m, acc unchanged in the others: the add runs under EXEC & m (three
 // scalar instructions, no branch) instead of a v_cndmask + v_add pair -- one VALU instruction less per sample in a VALU-bound loop
 __device__ __forceinline__ float add_lanes(float acc, float v, unsigned long long m)

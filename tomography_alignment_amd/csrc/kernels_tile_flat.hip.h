@@ -1,5 +1,7 @@
 // kernels_tile_flat.hip.h -- the FLAT tile kernels for untilted poses: k_tile_flat<FWD> (one tile per work-group; the adjoint form
-// scatters with LDS atomics) and k_fwd_flat_z<NZT> (forward over NZT z-adjacent tiles per work-group, the default forward).
+// scatters with LDS atomics; the forward form serves volumes of one z tile) and k_fwd_flat_tab (forward over two z-adjacent 64-plane
+// images per work-group, live blocks only: k_fwd_live, k_fwd_compact).  The gather-form kernels that take the whole-volume calls of
+// unit lattices are in kernels_tile_gather.hip.h.
 // Needs kernels_tile.hip.h (tile shape, AdjC, helpers) before it; part of the translation unit tomo_project.hip.
 
 // ------------------------------------------------------------------------------------------------
@@ -230,235 +232,24 @@ __global__ __launch_bounds__(ADJ_WAVES * 64) void k_tile_flat(const AdjC *__rest
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Forward flat kernel over NZT z-adjacent tiles per work-group.  60 % of k_tile_flat<true>'s time is per-row set-up (sample
-// table, row bases, compaction: ~115 issue slots per row against ~130 for the row's samples) and that set-up does not depend on
-// z: here a work-group of FZ_WAVES waves holds the LDS images of NZT tiles stacked in z, builds each row's table once and runs
-// the sample loop against every image.  NZT = 2 with 16 waves uses 148 KB of the 160 KB LDS for the two images, with the same
-// number of waves per CU as two 8-wave work-groups of the one-image kernel.
-// ------------------------------------------------------------------------------------------------
 #ifndef FZ_WAVES
 #define FZ_WAVES 16
 #endif
-// TX = x width of the tile footprint: 16 (with NZT = 2 z-stacked images: the default) or 32 (with NZT = 1: the "32 x 16 footprint"
-// of DESIGN.md section 4, built in round 3 to MEASURE what halving the tile crossings -- hence the float atomics -- costs in the
-// sample loop, whose per-entry broadcasts then serve one image instead of two; option fwd_flat_wide).
-template <int NZT, int TX = ATX>
-__global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_z(const AdjC *__restrict__ pcs, int n_proj, float *__restrict__ proj,
-                                                              const float *__restrict__ vol, TomoGeomC g, int tile_x0)
-{
-    // the images of the NZT stacked tiles are INTERLEAVED per (x, y) cell: [x][y][tile][64 planes] -- every corner of every image of a
-    // sample then lies within ds_read2st64_b32's offset range (units of 256 B, < 256) of ONE address register
-    static_assert((TX + 1) * ALY * NZT * FLZ * 4 <= 160 * 1024, "LDS");
-    __shared__ float img[(TX + 1) * ALY * NZT * FLZ];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int z0 = -1 + (int)blockIdx.x * (NZT * FTZ), y0 = -1 + (int)blockIdx.y * ATY, x0 = -1 + ((int)blockIdx.z + tile_x0) * TX;
-    bool live[NZT];
-    bool any_live = false;
-#pragma unroll
-    for (int k = 0; k < NZT; ++k) {
-        bool any_nz = false;
-        for (int e = threadIdx.x; e < (TX + 1) * ALY * FLZ; e += FZ_WAVES * 64) {
-            const int lz = e % FLZ, t2 = e / FLZ, ly = t2 % ALY, lx = t2 / ALY;
-            const int gx = x0 + lx, gy = y0 + ly, gz = z0 + k * FTZ + lz;
-            float v = 0.f;
-            if (gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny && gz >= 0 && gz < g.nz) v = vol[((size_t)gx * g.ny + gy) * g.nz + gz];
-            img[(t2 * NZT + k) * FLZ + lz] = v;
-            any_nz |= (v != 0.f);
-        }
-        live[k] = __syncthreads_or(any_nz) != 0;                      // an all-zero tile contributes nothing to any ray
-        any_live |= live[k];
-    }
-    if (!any_live) return;
-    const float bcx = (float)x0 + 0.5f * TX, bcy = (float)y0 + 0.5f * ATY;
-    const int64_t orgx = (int64_t)x0 << 32, orgy = (int64_t)y0 << 32;
-    const size_t n_det = (size_t)g.ndx * g.ndz;
-    const float two_m32 = 2.3283064365386963e-10f;
-    const unsigned lane4 = (unsigned)min(lane, FLZ - 1) * 4u;      // lanes 61..63 alias the halo plane with zero weight
-
-    for (int ip = wv; ip < n_proj; ip += FZ_WAVES) {               // one wave owns a whole (tile stack, projection)
-        const AdjC &c = pcs[ip];
-        // z: ray iz sits in plane lz = floor(p0z) + iz - z0 with the same fraction for every ray
-        const int p0z_i = (int)(c.fp0[2] >> 32);
-        const float wcz = (float)(unsigned)c.fp0[2] * two_m32, wfz = 1.f - wcz;
-        bool zuse[NZT], ray_ok[NZT];
-        bool any_use = false;
-        const int iz0 = z0 - p0z_i + lane;                             // this lane's ray in the lowest tile; + FTZ per tile
-#pragma unroll
-        for (int k = 0; k < NZT; ++k) {
-            const int izoff = z0 + k * FTZ - p0z_i;
-            zuse[k] = live[k] && !(izoff + FTZ <= 0 || izoff >= g.ndz);   // some ray of this projection floors into the tile's z range
-            any_use |= zuse[k];
-            const int iz = iz0 + k * FTZ;
-            ray_ok[k] = zuse[k] && lane < FTZ && iz >= 0 && iz < g.ndz;     // the last plane of an image is halo only
-        }
-        if (!any_use) continue;
-        // detector rows crossing the tile's x,y footprint (2-D: a linear functional over a rectangle)
-        const float qx = bcx - (float)c.p0[0], qy = bcy - (float)c.p0[1];
-        const float m00 = (float)c.minv[0][0], m01 = (float)c.minv[0][1];
-        const float ixc = m00 * qx + m01 * qy;
-        const float ixr = fabsf(m00) * (0.5f * TX) + fabsf(m01) * (0.5f * ATY) + 2e-2f;
-        const int ix_lo = max(0, (int)ceilf(fmaxf(ixc - ixr, -1.f)));
-        const int ix_hi = min(g.ndx - 1, (int)floorf(fminf(ixc + ixr, (float)g.ndx)));
-        if (ix_lo > ix_hi) continue;
-        const int n_rows_w = ix_hi - ix_lo + 1;
-        const float fp0x = (float)c.p0[0] - (float)x0, fp0y = (float)c.p0[1] - (float)y0;
-        const float fux = (float)c.u[0], fuy = (float)c.u[1], fdx = (float)c.d[0], fdy = (float)c.d[1];
-        int64_t ldx = (int64_t)lane * c.fd[0], ldy = (int64_t)lane * c.fd[1];   // sample `lane` of a chunk, relative to its first
-        int64_t k_fux = c.fu[0], k_fuy = c.fu[1], k_fdx = c.fd[0], k_fdy = c.fd[1];
-        asm volatile("" : "+v"(ldx), "+v"(ldy));                       // see k_tile_flat: keep the row loop's inputs in registers
-        asm volatile("" : "+s"(k_fux), "+s"(k_fuy), "+s"(k_fdx), "+s"(k_fdy));
-        float *const proj_c = proj + (size_t)c.slot * n_det + iz0;
-
-        for (int r0 = 0; r0 < n_rows_w; r0 += 64) {
-            int v_jlo, v_jhi;
-            {
-                const int rix = ix_lo + r0 + lane;
-                flat_row_range(fp0x + (float)rix * fux, fp0y + (float)rix * fuy, fdx, fdy, c.n, rix <= ix_hi, v_jlo, v_jhi, (float)TX);
-            }
-            const int r_end = min(64, n_rows_w - r0);
-            int64_t rbx = c.fp0[0] + (int64_t)(ix_lo + r0) * k_fux - orgx, rby = c.fp0[1] + (int64_t)(ix_lo + r0) * k_fuy - orgy;
-            float *pr = proj_c + (size_t)(ix_lo + r0) * g.ndz;
-            for (int r = 0; r < r_end; ++r, rbx += k_fux, rby += k_fuy, pr += g.ndz) {
-                const int jlo = __builtin_amdgcn_readlane(v_jlo, r), jhi = __builtin_amdgcn_readlane(v_jhi, r);
-                if (jhi <= jlo) continue;
-                float S[NZT];
-#pragma unroll
-                for (int k = 0; k < NZT; ++k) S[k] = 0.f;
-                for (int jc = jlo; jc < jhi; jc += 60) {
-                    // one lane per SAMPLE: cell, ownership in x,y and the four x,y weights of sample jc + lane.  The uniform part of
-                    // the position (row base + jc steps) is formed on the scalar unit and kept opaque -- the compiler otherwise
-                    // folds it into two per-lane 64-bit multiply-adds (v_mad_u64_u32)
-                    int64_t ux = rbx + (int64_t)jc * k_fdx, uy = rby + (int64_t)jc * k_fdy;
-                    asm volatile("" : "+s"(ux), "+s"(uy));
-                    const int64_t px = add64_vs(ldx, ux), py = add64_vs(ldy, uy);
-                    const unsigned lx = (unsigned)(px >> 32), ly = (unsigned)(py >> 32);
-                    const unsigned long long own_m = (TX == ATY ? __builtin_amdgcn_ballot_w64((lx | ly) < (unsigned)ATY) : (__builtin_amdgcn_ballot_w64(lx < (unsigned)TX) & __builtin_amdgcn_ballot_w64(ly < (unsigned)ATY))) &
-                                                     __builtin_amdgcn_ballot_w64(jc + lane < min(jhi, jc + 60));
-                    const unsigned t_e = (__umul24(lx, ALY * NZT * FLZ) + __umul24(ly, NZT * FLZ)) * 4u;
-                    const float wx = (float)(unsigned)px * two_m32, wy = (float)(unsigned)py * two_m32;
-                    const float t_w11 = wx * wy, t_w10 = wx - t_w11, t_w01 = wy - t_w11, t_w00 = 1.f - wx - t_w01;
-                    // NO compaction: the owned samples of a row are CONTIGUOUS lanes (a line meets the tile's convex footprint in one
-                    // interval of j, and the cells come from exact fixed-point positions), so the sample loop simply broadcasts lanes
-                    // first .. first + n_own - 1 with v_readlane.  (Until round 2 the entries were compacted to lanes 0.. with five
-                    // ds_permute per row -- an LDS round trip in front of every row's loop; an ablation without the sample loop still took
-                    // 71 % of the kernel's time: the row set-up, not the samples, was the cost.)  Lanes that own nothing carry address 0 and
-                    // weights 0: the loop's look-ahead may read one or two of them.
-                    const unsigned long long om = own_m;
-                    const int n_own = (int)__builtin_popcountll(om);
-                    const int first = om ? (int)__builtin_ctzll(om) : 0;
-                    const int c_e = (int)select_lanes_u(t_e, om);
-                    const int c_w00 = __float_as_int(select_lanes(t_w00, om)), c_w01 = __float_as_int(select_lanes(t_w01, om));
-                    const int c_w10 = __float_as_int(select_lanes(t_w10, om)), c_w11 = __float_as_int(select_lanes(t_w11, om));
-                    f32x2 Sa[NZT], Sb[NZT];
-#pragma unroll
-                    for (int k = 0; k < NZT; ++k) { Sa[k] = (f32x2){0.f, 0.f}; Sb[k] = (f32x2){0.f, 0.f}; }
-                    // an entry's five readlanes serve every image.  One image in use: (y, y + 1) corners arrive as a register pair from
-                    // one ds_read2st64 and the weights as SGPR pairs, two packed FMAs per sample.  Both in use: see below.  Which images
-                    // take part is decided outside the loop (an all-zero or out-of-range image is skipped).
-                    // SOFTWARE-PIPELINED (round 2): the reads of entry jj + 1 are issued before entry jj's values are used.  The
-                    // one-entry-per-trip loop drained the LDS queue (s_waitcnt lgkmcnt(0)) before its last FMA, so every entry cost
-                    // a wave a full LDS round trip, and with 4 waves per SIMD the kernel sat at 56 % LDS / ~30 % VALU utilisation:
-                    // latency-bound.  Entries past n_own exist (ds_permute leaves 0 in lanes nobody wrote: address 0, weights 0), so
-                    // the look-ahead needs no guard.  (The images used to lie one behind the other, 73 984 B apart -- beyond the DS offset
-                    // fields, a second address register per entry; interleaved per cell, one register reaches all eight corners.)
-                    {
-                        int r_e = c_e, r_w00 = c_w00, r_w01 = c_w01, r_w10 = c_w10, r_w11 = c_w11;
-#define FZ_LOAD(T, J, K0, K1)                                                                                               \
-                        {                                                                                                   \
-                            const unsigned e_ = (unsigned)__builtin_amdgcn_readlane(r_e, first + (J)) + lane4;                      \
-                            const float *q_ = (const float *)((const char *)&img[0] + e_);                                  \
-                            _Pragma("unroll") for (int k = (K0); k < (K1); ++k) {                                           \
-                                T##v0[k] = (f32x2){q_[k * FLZ], q_[(NZT + k) * FLZ]};                                       \
-                                T##v1[k] = (f32x2){q_[(ALY * NZT + k) * FLZ], q_[(ALY * NZT + NZT + k) * FLZ]};             \
-                            }                                                                                               \
-                        }
-#define FZ_USE(T, J, K0, K1)                                                                                                \
-                        {                                                                                                   \
-                            const f32x2 w0_ = {__int_as_float(__builtin_amdgcn_readlane(r_w00, first + (J))), __int_as_float(__builtin_amdgcn_readlane(r_w01, first + (J)))}; \
-                            const f32x2 w1_ = {__int_as_float(__builtin_amdgcn_readlane(r_w10, first + (J))), __int_as_float(__builtin_amdgcn_readlane(r_w11, first + (J)))}; \
-                            _Pragma("unroll") for (int k = (K0); k < (K1); ++k) { Sa[k] += w0_ * T##v0[k]; Sb[k] += w1_ * T##v1[k]; } \
-                        }
-#define FZ_SAMPLE_LOOP(K0, K1)                                                                                              \
-                        {                                                                                                   \
-                            f32x2 A_v0[NZT], A_v1[NZT], B_v0[NZT], B_v1[NZT];                                               \
-                            FZ_LOAD(A_, 0, K0, K1)                                                                          \
-                            for (int jj = 0; jj < n_own; jj += 2) {                                                         \
-                                FZ_LOAD(B_, jj + 1, K0, K1)                                                                 \
-                                FZ_USE(A_, jj, K0, K1)                                                                      \
-                                FZ_LOAD(A_, jj + 2, K0, K1)                                                                 \
-                                FZ_USE(B_, jj + 1, K0, K1)                                                                  \
-                            }                                                                                               \
-                        }
-                        if (NZT == 2 && zuse[0] && zuse[NZT - 1]) {
-                            // both images: a register pair = the SAME corner of image 0 and image 1 (adjacent 256-B units of the interleaved
-                            // layout, one ds_read2st64_b32), the weight a scalar for both halves: 4 reads + 4 packed FMAs per sample on one
-                            // address register
-                            f32x2 Pa = {0.f, 0.f}, Pb = {0.f, 0.f};
-                            f32x2 A_00, A_01, A_10, A_11, B_00, B_01, B_10, B_11;
-#define FB_LOAD(T, J)                                                                                                      \
-                            {                                                                                                   \
-                                const float *q_ = (const float *)((const char *)&img[0] + ((unsigned)__builtin_amdgcn_readlane(r_e, first + (J)) + lane4)); \
-                                T##00 = (f32x2){q_[0], q_[FLZ]}; T##01 = (f32x2){q_[2 * FLZ], q_[3 * FLZ]};                     \
-                                T##10 = (f32x2){q_[2 * ALY * FLZ], q_[(2 * ALY + 1) * FLZ]};                                    \
-                                T##11 = (f32x2){q_[(2 * ALY + 2) * FLZ], q_[(2 * ALY + 3) * FLZ]};                              \
-                            }
-#define FB_USE(T, J)                                                                                                       \
-                            {                                                                                                   \
-                                Pa += __int_as_float(__builtin_amdgcn_readlane(r_w00, first + (J))) * T##00;                            \
-                                Pb += __int_as_float(__builtin_amdgcn_readlane(r_w10, first + (J))) * T##10;                            \
-                                Pa += __int_as_float(__builtin_amdgcn_readlane(r_w01, first + (J))) * T##01;                            \
-                                Pb += __int_as_float(__builtin_amdgcn_readlane(r_w11, first + (J))) * T##11;                            \
-                            }
-                            static_assert(NZT <= 2, "the pair layout is written for two images");
-                            FB_LOAD(A_, 0)
-                            for (int jj = 0; jj < n_own; jj += 2) {
-                                FB_LOAD(B_, jj + 1)
-                                FB_USE(A_, jj)
-                                FB_LOAD(A_, jj + 2)
-                                FB_USE(B_, jj + 1)
-                            }
-#undef FB_LOAD
-#undef FB_USE
-                            const f32x2 Pt = Pa + Pb;
-                            Sa[0] = (f32x2){Pt.x, 0.f}; Sa[NZT - 1] = (f32x2){Sa[NZT - 1].x + (NZT == 2 ? Pt.y : 0.f), 0.f};
-                        }
-                        else if (zuse[0]) { FZ_SAMPLE_LOOP(0, 1) }
-                        else { FZ_SAMPLE_LOOP(NZT - 1, NZT) }
-#undef FZ_SAMPLE_LOOP
-#undef FZ_USE
-#undef FZ_LOAD
-                    }
-#pragma unroll
-                    for (int k = 0; k < NZT; ++k) {
-                        const f32x2 St = Sa[k] + Sb[k];
-                        S[k] += St.x + St.y;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < NZT; ++k) {
-                    if (!zuse[k]) continue;
-                    const float Sp1 = __shfl_down(S[k], 1, 64);                // plane lane+1
-                    if (ray_ok[k]) atomicAdd(pr + k * FTZ, wfz * S[k] + wcz * Sp1);
-                }
-            }
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
-// Forward flat kernel, round-3 form: sample table in LDS + image PAIRS.
-// Round 2 measured two halves of this separately and each moved the bound to the other unit: (a) the per-row sample table in a
-// wave-private LDS table (no v_readlane): 0.523 ms/angle, LDS-bound at 5 + 16 LDS clk per entry; (b) data reads as ds_read_b64
-// (half the LDS cycles) with the table still broadcast by five v_readlane per entry: 0.444 vs 0.448, VALU-bound.  Together:
+// Forward flat kernel over TWO z-adjacent 64-plane images per work-group: sample table in LDS + image PAIRS.
+// 60 % of k_tile_flat<true>'s time is per-row set-up (sample table, row bases, compaction: ~115 issue slots per row against ~130 for
+// the row's samples) and that set-up does not depend on z: here a work-group of FZ_WAVES waves holds the LDS images of two blocks
+// stacked in z, builds each row's table once and runs the sample loop against both.  With 16 waves the two images and the tables take
+// 157 KB of the 160 KB LDS, with the same number of waves per CU as two 8-wave work-groups of the one-image kernel.
 //   * the two z-stacked images are interleaved per PLANE, [x][y][64 planes][image]: the values a lane needs from both images for a
 //     corner are one aligned 8-byte word -> 4 ds_read_b64 per entry at immediate offsets of ONE address (y + 1: +512 B, x + 1:
 //     +8704 B), 2 LDS clk each, the register pair (image 0, image 1) feeds v_pk_fma_f32 directly;
 //   * an entry's four weights come back from a wave-private LDS table by broadcast ds_read_b128 (4 LDS clk), its cell address by one
-//     v_readlane: 4 v_pk_fma_f32 + 1 v_add_u32 + 1 v_readlane per entry.
-// LDS 12 clk and VALU ~6.3 instructions per entry against 17.6 / ~12 (+ set-up) of k_fwd_flat_z<2>.
-// Same sums as k_fwd_flat_z<2>, in the same order per row (entries ascending, four accumulator pairs -> two).
+//     v_readlane: 4 v_pk_fma_f32 + 1 v_add_u32 + 1 v_readlane per entry: LDS 12 clk and VALU ~6.3 instructions per entry;
+//   * a row's sums are added entries ascending, in two accumulator pairs.
+// (This kernel replaced a form that broadcast every table entry with five v_readlane and read the images with ds_read2st64_b32: 0.434
+// ms/angle on a dense 1024^3 volume against 0.329 here; that kernel, and the two half-steps measured between them, are in git history.)
 //   * NO HALO PLANE (second half of round 3): an image is 64 owned planes, a work-group owns planes [128 b, 128 b + 128) and all 64 lanes
 //     of both images carry a ray.  The plane above a lane's own (the z-lerp's upper neighbour) is the next lane's sum (DPP shift), for
 //     lane 63 of image 0 it is image 1's lane 0, for lane 63 of image 1 it belongs to the NEXT work-group in z -- which adds its
@@ -636,9 +427,10 @@ __global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_tab(const AdjC *__re
                     const unsigned t_e = (__umul24(lx, ALY * FLZ * 2) + __umul24(ly, FLZ * 2)) * 4u;      // byte offset of cell (lx, ly), plane 0, image 0
                     const float wx = (float)(unsigned)px * two_m32, wy = (float)(unsigned)py * two_m32;
                     const float t_w11 = wx * wy, t_w10 = wx - t_w11, t_w01 = wy - t_w11, t_w00 = 1.f - wx - t_w01;
-                    // the owned samples of a row are CONTIGUOUS lanes first .. first + n_own - 1 (see k_fwd_flat_z): entry i of the table =
-                    // lane first + i.  LDS operations of one wave execute in order: no barrier between these writes and the reads below,
-                    // nor against the previous chunk's.
+                    // NO compaction: the owned samples of a row are CONTIGUOUS lanes first .. first + n_own - 1 (a line meets the tile's convex
+                    // footprint in one interval of j, and the cells come from exact fixed-point positions), so entry i of the table = lane
+                    // first + i.  LDS operations of one wave execute in order: no barrier between these writes and the reads below, nor
+                    // against the previous chunk's.
                     const int n_own = (int)__builtin_popcountll(om);
                     const int first = (int)__builtin_ctzll(om);
                     const unsigned slot = (unsigned)(lane - first);
@@ -651,7 +443,7 @@ __global__ __launch_bounds__(FZ_WAVES * 64) void k_fwd_flat_tab(const AdjC *__re
                     // Variants measured in round 3 on a dense 1024^3 volume, ms per angle (profiles/round3_fwd_tab_variants.md): addresses in the
                     // LDS table too, zero-padded groups of four 0.352; this form with zero-padded groups of four 0.345, of eight 0.388, of
                     // two 0.336, one by one 0.335; groups of four + tail (this code) 0.329; eight + four + tail 0.333; the next group's table
-                    // words fetched ahead 0.375; hand software-pipelined with two register sets 0.355.  Round 2's kernel: 0.434.
+                    // words fetched ahead 0.375; hand software-pipelined with two register sets 0.355.  The kernel this one replaced: 0.434.
 #define FT2_ENTRY(J, W)                                                                                                    \
                         {                                                                                                   \
                             /* explicit LDS pointer; volatile keeps four ds_read_b64 (2 LDS clk each): merged into ds_read2st64_b64 */ \

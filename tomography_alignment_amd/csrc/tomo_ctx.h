@@ -21,6 +21,37 @@ struct BpC {   // voxel-driven back-projector constants of one projection: the r
 struct ProfRec { int64_t n = 0; double ms = 0.0; };
 struct ProfPending { std::string name; hipEvent_t e0, e1; };
 
+// What stage_tile_consts (tomo_project.hip) staged last for the tile kernels, kept while the same poses come again and nobody else has
+// used the staging buffers -- the x-slab calls of one pipelined back-projection, forward + back-projection of a solver iteration, every
+// iteration of a solver (a re-stage drains the stream: the GPU would idle between slab kernels).  The staging buffer holds, from offset
+// 0: the AdjC array [gather-eligible flat ..., other flat ..., general ...]; at gf_off one GfC per gather-eligible projection; at fg_off
+// the gather forward's projection lists (indices into the GfC array): [x walk NW 3 | x walk NW 4 | y walk NW 3 | y walk NW 4], each in
+// pose order, fg_n[] entries each.
+struct TilePlan {
+    bool valid = false;                 // the staging buffers still hold what this plan describes (tomo_ensure_stage clears it)
+    bool ok = false;                    // the tile kernels take these poses (a pose set they decline is never kept: valid implies ok)
+    std::vector<double> poses;          // key: the poses ...
+    int opts = 0;                       // ... and the options "tile_flat" (bit 0) and "adj_flat_gather" (bit 1) it was staged under
+    double weight_bound = 2.0;          // bound of the tent weights a voxel collects from one projection (fixed-point scale of the LDS adjoints)
+    int n_flat = 0, n_gather = 0;       // untilted projections, and how many of them are gather-eligible
+    double eb_max = 0.0;                // largest |m10| + |m11| of the gather-eligible projections (picks NJ)
+    int zc_lo = 0, zc_hi = 0;           // range of the gather-eligible projections' integer z offsets (GfC::zc)
+    size_t gf_off = 0, fg_off = 0;      // byte offsets into the staging buffer
+    int fg_n[4] = {0, 0, 0, 0};
+    bool fg_ok = false;                 // every gather-eligible projection also meets the gather forward's bounds
+};
+
+// Key of the sinogram plane flags cached in d_blk: everything the cached words depend on -- the sinogram and its shape (layout of the
+// flags and their prefix counts), and the volume height and the poses' integer z offsets the chunk shift was computed from.
+struct ZfKey {
+    const void *src = nullptr;
+    int nproj = 0, ndz = 0, ndx = 0, nz = 0, zc_lo = 0, zc_hi = 0;
+    bool operator==(const ZfKey &o) const
+    {
+        return src == o.src && nproj == o.nproj && ndz == o.ndz && ndx == o.ndx && nz == o.nz && zc_lo == o.zc_lo && zc_hi == o.zc_hi;
+    }
+};
+
 struct tomo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -39,22 +70,8 @@ struct tomo_ctx {
     void *h_stage = nullptr;
     void *d_stage = nullptr;
     size_t stage_bytes = 0;
-    // the tile kernels' constants staged last (stage_tile_consts): reused while the same poses come again and nobody else has
-    // used the staging buffers -- the x-slab calls of one pipelined back-projection, forward + back-projection of a solver
-    // iteration, every iteration of a solver (a re-stage drains the stream: the GPU would idle between slab kernels)
-    bool tile_cache_valid = false;
-    std::vector<double> tile_cache_poses;
-    int tile_cache_opts = 0, tile_cache_nflat = 0, tile_cache_ngather = 0;
-    bool tile_cache_ok = false;
-    double tile_cache_wb = 2.0;
-    int tile_cache_zc_lo = 0, tile_cache_zc_hi = 0;   // range of the gather-eligible projections' integer z offsets (GfC::zc)
-    double tile_cache_eb_max = 0.0;     // largest |m10| + |m11| of the gather-eligible projections staged (picks NJ)
-    size_t tile_cache_gfoff = 0;
-    // the gather forward's projection lists (indices into the GfC array), staged behind the GfC array: [x walk NW 3 | x walk NW 4 | y walk NW 3 |
-    // y walk NW 4], each in pose order; tile_cache_fg_ok: every gather-eligible projection also meets the forward kernel's bounds
-    size_t tile_cache_fgoff = 0;
-    int tile_cache_fg_n[4] = {0, 0, 0, 0};
-    bool tile_cache_fg_ok = false;
+    // the tile kernels' constants staged last (stage_tile_consts)
+    TilePlan plan;
     // reduction scratch
     double *d_red = nullptr;
     double *h_red = nullptr;
@@ -70,20 +87,18 @@ struct tomo_ctx {
     // TOMO_N_ACC double accumulators (tomo_acc_zero / tomo_vec_dot_acc / tomo_acc_fetch) + their pinned host mirror
     double *d_acc = nullptr;
     double *h_acc = nullptr;
-    // live-block list of the flat forward (grow-only): [0] = number of live blocks, [1 ..] their ids in launch order, then one flag byte per block
+    // block buffer (grow-only).  A forward call keeps its live lists here (LiveList), a back-projection the plane flags of its sinogram
+    // (BlkHead) and the general kernel's live list behind them
     int *d_blk = nullptr;
     size_t blk_ints = 0;
     int reuse_sino_flags = 0;           // option: the caller vouches the sinogram of the previous back-projection call is unchanged
-    const void *zf_src = nullptr;       // sinogram whose plane flags (+ prefix counts when zf_has_cum) d_blk currently holds; nullptr: none
-    int zf_nproj = 0;
-    bool zf_has_cum = false, zf_has_shift = false;
-    int zf_ndz = 0, zf_ndx = 0, zf_nz = 0, zf_zc_lo = 0, zf_zc_hi = 0;   // ... and the geometry / pose z offsets they were computed for
-    // true: the flags of zf_src were recorded by the pass that WROTE that sinogram (tomo_vec_residual_scale_flags) and nothing has been
-    // launched, copied or reduced on this context since -- the next back-projection of zf_src takes them without the caller's word
+    ZfKey zf_key;                       // what the plane flags in d_blk were computed for; src == nullptr: d_blk holds none
+    bool zf_has_cum = false, zf_has_shift = false;      // ... with their prefix counts / chunk shift
+    // true: the flags of zf_key.src were recorded by the pass that WROTE that sinogram (tomo_vec_residual_scale_flags) and nothing has been
+    // launched, copied or reduced on this context since -- the next back-projection of it takes them without the caller's word
     // (reuse_sino_flags) and without its own scan.  Dropped by every launch (TOMO_LAUNCH) and by the copies, fills, frees and collectives
     // that can write a caller's buffer (tomo_ctx.hip): recorded flags serve exactly the call that follows their recording.
     bool zf_recorded = false;
-    size_t fwd_blk_flat_ints = 0;       // ints of d_blk the flat forward of the current call uses (the general kernel's tile list follows)
     // general float workspace (grow-only): the TV-FISTA proximal step keeps its 7 fields here across calls
     float *d_ws = nullptr;
     size_t ws_elems = 0;
@@ -99,10 +114,8 @@ struct tomo_ctx {
     int tile_flat = 1;      // 1: untilted projections take the flat tile kernels
     int fused_update = 1;     // 1: tomo_adjoint_update folds the SIRT update into the gather adjoint's store when all its poses take that kernel; 0: it always declines (the caller's two calls)
     int adj_flat_gather = 1;  // 1: untilted unit lattices take the gather-form adjoint (k_adj_gather_flat) instead of the LDS-atomic flat kernel
-    int fwd_flat_gather = 1;  // 1 (default): whole-volume forward calls ALL of whose poses take the gather adjoint (three samples per row) take the gather-form forward (k_fwd_gather_flat: no atomics, same bits every run); other calls, and 0: k_fwd_flat_tab
-    int fwd_flat_tab = 1;     // 1 (default): the flat forward with the sample table in LDS and the two images interleaved per plane (k_fwd_flat_tab); 0: the round-2 kernel (k_fwd_flat_z<2>: entries broadcast with v_readlane)
-    int fwd_flat_wide = 0;    // 1: measurement variant of the flat forward -- 32 x 16 x 63 footprint, one image per work-group (k_fwd_flat_z<1, 32>); only in builds with -DTOMO_MEASUREMENT_VARIANTS
-    int fwd_flat_ztiles = 2;  // 2: the flat forward processes two z-adjacent tiles per work-group (k_fwd_flat_z<2>); 1: one tile (k_tile_flat<true>)
+    int fwd_flat_gather = 1;  // 1 (default): whole-volume forward calls ALL of whose poses take the gather adjoint (three samples per row) take the gather-form forward (k_fwd_gather_flat: no atomics, same bits every run); other calls, and 0: the flat forward below
+    int fwd_flat_ztiles = 2;  // 2 (default): the flat forward of a volume of two or more z tiles runs over blocks of two z-adjacent 64-plane images, live blocks only (k_fwd_flat_tab); 1, and volumes of one z tile: one tile per work-group (k_tile_flat<true>)
     // timing / profiling
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool profile_on = false;
@@ -140,9 +153,35 @@ int tomo_ensure_red(tomo_ctx *ctx, size_t n_doubles);
 int tomo_ensure_red_part(tomo_ctx *ctx, size_t n_doubles);
 int tomo_ensure_ws(tomo_ctx *ctx, size_t n_floats);
 int tomo_ensure_blk(tomo_ctx *ctx, size_t n_ints);
+// Head of d_blk during a back-projection: one flag byte per detector-z plane of the sinogram (ndz bytes, padded to ints), their ndz + 1
+// prefix counts, the z chunk shift (one int).  tomo_blk_head makes d_blk hold the head and `extra_ints` behind it.
+struct BlkHead {
+    unsigned char *zf;
+    int *zcum, *zshift;
+    size_t ints;
+};
+static inline int tomo_blk_head(tomo_ctx *ctx, size_t extra_ints, BlkHead *h)
+{
+    const size_t zf_ints = ((size_t)ctx->g.ndz + 3) / 4;
+    h->ints = zf_ints + (size_t)ctx->g.ndz + 2;
+    const int rc = tomo_ensure_blk(ctx, h->ints + extra_ints);
+    if (rc) return rc;
+    h->zf = (unsigned char *)ctx->d_blk;
+    h->zcum = ctx->d_blk + zf_ints;
+    h->zshift = h->zcum + ctx->g.ndz + 1;
+    return TOMO_OK;
+}
+// A live list of n blocks (or tiles) at int offset `at` of d_blk: list[0] = number of live blocks, list[1 ..] their ids in launch order,
+// then one flag byte per block.
+struct LiveList {
+    int *list;
+    unsigned char *flags;
+    static size_t ints(size_t n) { return 1 + n + (n + 3) / 4; }
+    LiveList(int *d_blk, size_t at, size_t n) : list(d_blk + at), flags((unsigned char *)(list + 1 + n)) {}
+};
 // the passes and the cache key that go with freshly written sinogram plane flags (tomo_project.hip)
-int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, unsigned char *d_zf, int *d_zcum, int *d_zshift,
-                       const char *prof_name, bool recorded);
+int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, const BlkHead &head, const char *prof_name,
+                       bool recorded);
 void tomo_csr_release(tomo_ctx *ctx);
 void tomo_prof_begin(tomo_ctx *ctx, const char *name);
 void tomo_prof_end(tomo_ctx *ctx);

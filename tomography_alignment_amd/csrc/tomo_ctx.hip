@@ -195,14 +195,6 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
     else if (!strcmp(key, "adj_flat_gather")) ctx->adj_flat_gather = value;
     else if (!strcmp(key, "fused_update")) ctx->fused_update = value;
     else if (!strcmp(key, "fwd_flat_ztiles")) ctx->fwd_flat_ztiles = value;
-    else if (!strcmp(key, "fwd_flat_wide")) {
-#ifdef TOMO_MEASUREMENT_VARIANTS
-        ctx->fwd_flat_wide = value;
-#else
-        if (value) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "fwd_flat_wide is a measurement variant: build with EXTRA=-DTOMO_MEASUREMENT_VARIANTS (csrc/Makefile)");
-#endif
-    }
-    else if (!strcmp(key, "fwd_flat_tab")) ctx->fwd_flat_tab = value;
     else if (!strcmp(key, "fwd_flat_gather")) ctx->fwd_flat_gather = value;
     else if (!strcmp(key, "reuse_staged_volume")) ctx->reuse_staged = value;
     else if (!strcmp(key, "reuse_sino_flags")) ctx->reuse_sino_flags = value;
@@ -215,7 +207,7 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
 
 int tomo_ensure_stage(tomo_ctx *ctx, size_t bytes)
 {
-    ctx->tile_cache_valid = false;                       // whoever asks for the staging buffers is about to overwrite them
+    ctx->plan.valid = false;                            // whoever asks for the staging buffers is about to overwrite them
     if (bytes <= ctx->stage_bytes) return TOMO_OK;
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
@@ -287,7 +279,7 @@ int tomo_ensure_ws(tomo_ctx *ctx, size_t n)
 int tomo_ensure_blk(tomo_ctx *ctx, size_t n)
 {
     if (n <= ctx->blk_ints) return TOMO_OK;
-    ctx->zf_src = nullptr;                              // the buffer is replaced: cached plane flags go with it
+    ctx->zf_key.src = nullptr;                          // the buffer is replaced: cached plane flags go with it
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->d_blk) (void)hipFree(ctx->d_blk);
     ctx->d_blk = nullptr;
@@ -322,7 +314,7 @@ extern "C" int tomo_set_geometry(tomo_ctx *ctx, const tomo_geom *g)
     int gflags = 0;
     int grc = tomo_check_geometry(g, &gflags);
     if (grc) return tomo_fail(ctx, grc, tomo_last_error(nullptr));
-    ctx->tile_cache_valid = false;
+    ctx->plan.valid = false;
     TomoGeomC c{};
     c.nx = g->nx; c.ny = g->ny; c.nz = g->nz; c.ndx = g->ndx; c.ndz = g->ndz;
     c.nxp = g->nx + 2 * TOMO_HALO; c.nyp = g->ny + 2 * TOMO_HALO; c.nzp = g->nz + 2 * TOMO_HALO;
@@ -344,7 +336,7 @@ extern "C" int tomo_set_geometry(tomo_ctx *ctx, const tomo_geom *g)
     }
     ctx->halo_dirty = true;
     ctx->staged_src = nullptr;
-    ctx->zf_src = nullptr;                  // cached sinogram plane flags belong to the geometry they were scanned under
+    ctx->zf_key.src = nullptr;              // cached sinogram plane flags belong to the geometry they were scanned under
     ctx->g = c;
     for (int a = 0; a < 3; ++a) ctx->vox_pitch[a] = g->vox_pitch[a];
     ctx->has_geom = true;
@@ -670,28 +662,23 @@ extern "C" int tomo_vec_residual_scale_flags(tomo_ctx *ctx, const float *b, cons
     if (rc) return rc;
     const TomoGeomC &g = ctx->g;
     const int grid = vec_grid(n);
+    const TilePlan &plan = ctx->plan;
     bool record = ctx->has_geom && n_proj > 0 && g.ndz > 0 && n == (int64_t)n_proj * g.ndx * g.ndz && ((int64_t)grid * 256) % g.ndz == 0 &&
-                  ctx->tile_cache_valid && ctx->tile_cache_ok && ctx->tile_cache_poses.size() == (size_t)n_proj * TOMO_POSE_STRIDE &&
-                  ctx->adj_variant != 1;
-    unsigned char *d_zf = nullptr;
-    int *d_zcum = nullptr, *d_zshift = nullptr;
+                  plan.valid && plan.ok && plan.poses.size() == (size_t)n_proj * TOMO_POSE_STRIDE && ctx->adj_variant != 1;
+    BlkHead head{};
     if (record) {
-        const size_t zf_ints = ((size_t)g.ndz + 3) / 4;                 // layout of the head of d_blk: as adjoint_tiles (tomo_project.hip)
-        rc = tomo_ensure_blk(ctx, zf_ints + (size_t)g.ndz + 2);
+        rc = tomo_blk_head(ctx, 0, &head);
         if (rc) return rc;
-        d_zf = (unsigned char *)ctx->d_blk;
-        d_zcum = ctx->d_blk + zf_ints;
-        d_zshift = d_zcum + g.ndz + 1;
     }
-    ctx->zf_src = nullptr;                                              // `out` is rewritten: whatever was cached for it is void
+    ctx->zf_key.src = nullptr;                                          // `out` is rewritten: whatever was cached for it is void
     TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));
     if (!record)
         TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale, dim3(grid), dim3(256), 0, b, ax, w, out, n, ctx->d_red);
     else {
-        const bool want_cum = n_proj > ctx->tile_cache_nflat, want_shift = ctx->tile_cache_ngather > 0;
-        TOMO_HIP(ctx, hipMemsetAsync(d_zf, 0, (size_t)g.ndz, ctx->stream));
-        TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale_flags, dim3(grid), dim3(256), 0, b, ax, w, out, n, ctx->d_red, g.ndz, d_zf);
-        rc = tomo_record_zflags(ctx, out, n_proj, want_cum, want_shift, d_zf, d_zcum, d_zshift, "k_residual_scale", true);
+        const bool want_cum = n_proj > plan.n_flat, want_shift = plan.n_gather > 0;
+        TOMO_HIP(ctx, hipMemsetAsync(head.zf, 0, (size_t)g.ndz, ctx->stream));
+        TOMO_LAUNCH(ctx, "k_residual_scale", k_residual_scale_flags, dim3(grid), dim3(256), 0, b, ax, w, out, n, ctx->d_red, g.ndz, head.zf);
+        rc = tomo_record_zflags(ctx, out, n_proj, want_cum, want_shift, head, "k_residual_scale", true);
         if (rc) return rc;
     }
     return h_sumsq ? red_fetch(ctx, h_sumsq) : TOMO_OK;

@@ -17,7 +17,7 @@
 //
 // The kernels live in five included files (one translation unit): kernels_ray.hip.h (k_pad/k_unpad, k_fwd_v1/v2, k_adj_v1,
 // k_bp_voxel), kernels_tile.hip.h (tile shape, AdjC, helpers, k_absmax, the general k_tile), kernels_tile_flat.hip.h (k_tile_flat,
-// k_fwd_flat_z), kernels_tile_gather.hip.h (k_adj_gather_flat), kernels_grad.hip.h (k_proj_grad, k_proj_grad_v2, k_proj_grad_v3);
+// k_fwd_flat_tab), kernels_tile_gather.hip.h (k_adj_gather_flat, k_fwd_gather_flat), kernels_grad.hip.h (k_proj_grad, k_proj_grad_v2, k_proj_grad_v3);
 // this file holds the host side of the C-ABI and the small-N kernels (k_triplets, k_vox_splat).
 #include <limits.h>
 #include <string.h>
@@ -114,41 +114,31 @@ static bool invert3(const double m[3][3], double inv[3][3], double *det_out)
     return true;
 }
 
-// Per-projection constants of the tile kernels, staged to the device as [flat projections..., general projections...].
-// all_ok = false (nothing staged) when some projection's detector-z axis does not map mostly onto volume z (tilt beyond
-// ~45 deg) or its lattice is singular / out of fixed-point range: those calls take the ray-driven / atomic kernels.
-// Stage the tile kernels' constants in the order [gather-eligible flat ..., other flat ..., general ...]; the first *n_gather
-// also get a GfC record (for k_adj_gather_flat) in a second array behind the AdjC array (*d_gfc).
-static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, bool *all_ok, double *weight_bound, int *n_flat,
-                             int *n_gather = nullptr, const GfC **d_gfc = nullptr)
+// Stage the per-projection constants of the tile kernels and describe them in ctx->plan (layout: TilePlan, tomo_ctx.h), or find them
+// staged already.  (*plan)->ok = false, nothing staged and nothing kept, when some projection's detector-z axis does not map mostly onto
+// volume z (tilt beyond ~45 deg) or its lattice is singular / out of fixed-point range: those calls take the ray-driven / atomic kernels.
+static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, const TilePlan **plan)
 {
     const TomoGeomC &g = ctx->g;
-    *all_ok = false;
-    *weight_bound = 2.0;
-    *n_flat = 0;
-    if (n_gather) *n_gather = 0;
+    TilePlan &p = ctx->plan;
+    *plan = &p;
     const int opts = (ctx->tile_flat != 0 ? 1 : 0) | (ctx->adj_flat_gather != 0 ? 2 : 0);
     const size_t n_pose_doubles = (size_t)n_proj * TOMO_POSE_STRIDE;
-    if (ctx->tile_cache_valid && ctx->tile_cache_opts == opts && ctx->tile_cache_poses.size() == n_pose_doubles && n_proj > 0 &&
-        memcmp(ctx->tile_cache_poses.data(), h_poses, n_pose_doubles * sizeof(double)) == 0) {
-        *all_ok = ctx->tile_cache_ok;                    // same poses, staging buffers untouched since: nothing to do
-        *weight_bound = ctx->tile_cache_wb;
-        *n_flat = ctx->tile_cache_nflat;
-        if (n_gather) *n_gather = ctx->tile_cache_ngather;
-        if (d_gfc) *d_gfc = (const GfC *)((char *)ctx->d_stage + ctx->tile_cache_gfoff);
-        return TOMO_OK;
-    }
+    if (p.valid && p.opts == opts && p.poses.size() == n_pose_doubles && n_proj > 0 &&
+        memcmp(p.poses.data(), h_poses, n_pose_doubles * sizeof(double)) == 0)
+        return TOMO_OK;                                  // same poses, staging buffers untouched since: nothing to do
+    p = TilePlan();
     TOMO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t gf_off = (sizeof(AdjC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;
-    const size_t fg_off = (gf_off + sizeof(GfC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;      // the gather forward's projection lists (+ padding)
-    int rc = tomo_ensure_stage(ctx, fg_off + sizeof(int) * 8 * ((size_t)std::max(n_proj, 1) + 4));
+    p.gf_off = (sizeof(AdjC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;
+    p.fg_off = (p.gf_off + sizeof(GfC) * (size_t)std::max(n_proj, 1) + 255) & ~(size_t)255;      // the gather forward's projection lists (+ padding)
+    int rc = tomo_ensure_stage(ctx, p.fg_off + sizeof(int) * 8 * ((size_t)std::max(n_proj, 1) + 4));
     if (rc) return rc;
     std::vector<AdjC> gath, flat, gen;
     std::vector<GfC> gfc;
     std::vector<int> fg_list[4];                   // k_fwd_gather_flat: [2 * walk + (NW == 4)] -> indices into gfc, pose order
-    bool fg_ok = true;
-    double eb_max = 0.0;
-    int zc_lo = INT_MAX, zc_hi = INT_MIN;          // range of the gather projections' integer z offsets (k_sino_zflags / zlive in the kernel)
+    p.fg_ok = true;
+    p.zc_lo = INT_MAX;                             // range of the gather projections' integer z offsets (k_sino_zflags / zlive in the kernel)
+    p.zc_hi = INT_MIN;
     for (int i = 0; i < n_proj; ++i) {
         ProjC pc;
         tomo_make_projc(g, h_poses + (size_t)i * TOMO_POSE_STRIDE, pc, nullptr);
@@ -172,7 +162,7 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
         if (!(pc.w[2] > 0.7 * sqrt(pc.w[0] * pc.w[0] + pc.w[1] * pc.w[1] + pc.w[2] * pc.w[2]))) return TOMO_OK;
         // samples per unit volume = 1/|det[u w d]|; the tent weights a voxel collects from one projection sum to about
         // that density (exactly 1 for an axis-aligned unit lattice); x2 head-room for the fixed-point image
-        *weight_bound = std::max(*weight_bound, 2.0 / fabs(det));
+        p.weight_bound = std::max(p.weight_bound, 2.0 / fabs(det));
         const bool untilted = a.fw[0] == 0 && a.fw[1] == 0 && a.fw[2] == ((int64_t)1 << 32) && a.fu[2] == 0 && a.fd[2] == 0 &&
                               ctx->tile_flat != 0;
         // gather-form adjoint: additionally the x-y lattice must be (close to) a unit lattice, so that three consecutive rows
@@ -194,7 +184,7 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
             {
                 const bool walky = llabs(q.fdx) < llabs(q.fdy);
                 const int64_t ads = llabs(walky ? q.fdy : q.fdx), adl = llabs(walky ? q.fdx : q.fdy);
-                fg_ok = fg_ok && (double)ads >= 0.67 * 4294967296.0 && (double)adl < 0.999 * 4294967296.0;
+                p.fg_ok = p.fg_ok && (double)ads >= 0.67 * 4294967296.0 && (double)adl < 0.999 * 4294967296.0;
                 std::vector<int> &fl = fg_list[2 * (walky ? 1 : 0) + (2 * adl <= ads ? 0 : 1)];
                 // groups are eight consecutive entries: where the list jumps to another range of poses, pad to the next group (-1 = no ray)
                 if (!fl.empty() && fl.back() != (int)gfc.size() - 1)
@@ -203,9 +193,9 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
             }
             gath.push_back(a);
             gfc.push_back(q);
-            eb_max = std::max(eb_max, eb);
-            zc_lo = std::min(zc_lo, (int)q.zc);
-            zc_hi = std::max(zc_hi, (int)q.zc);
+            p.eb_max = std::max(p.eb_max, eb);
+            p.zc_lo = std::min(p.zc_lo, (int)q.zc);
+            p.zc_hi = std::max(p.zc_hi, (int)q.zc);
         } else
             (untilted ? flat : gen).push_back(a);
     }
@@ -214,34 +204,27 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, b
     for (const AdjC &a : gath) h[k++] = a;
     for (const AdjC &a : flat) h[k++] = a;
     for (const AdjC &a : gen) h[k++] = a;
-    GfC *hg = (GfC *)((char *)ctx->h_stage + gf_off);
+    GfC *hg = (GfC *)((char *)ctx->h_stage + p.gf_off);
     for (size_t i = 0; i < gfc.size(); ++i) hg[i] = gfc[i];
-    int *hf = (int *)((char *)ctx->h_stage + fg_off);
+    int *hf = (int *)((char *)ctx->h_stage + p.fg_off);
     size_t fg_total = 0;
     for (int l = 0; l < 4; ++l) {
         for (int v : fg_list[l]) hf[fg_total++] = v;
-        ctx->tile_cache_fg_n[l] = (int)fg_list[l].size();
+        p.fg_n[l] = (int)fg_list[l].size();
     }
-    ctx->tile_cache_fgoff = fg_off;
-    ctx->tile_cache_fg_ok = fg_ok;
-    *n_flat = (int)(gath.size() + flat.size());
-    if (n_gather) *n_gather = (int)gath.size();
-    if (d_gfc) *d_gfc = (const GfC *)((char *)ctx->d_stage + gf_off);
-    if (n_proj) TOMO_HIP(ctx, hipMemcpyAsync(ctx->d_stage, h, fg_off + sizeof(int) * fg_total, hipMemcpyHostToDevice, ctx->stream));
-    *all_ok = true;
-    ctx->tile_cache_poses.assign(h_poses, h_poses + n_pose_doubles);
-    ctx->tile_cache_opts = opts;
-    ctx->tile_cache_ok = true;
-    ctx->tile_cache_wb = *weight_bound;
-    ctx->tile_cache_nflat = *n_flat;
-    ctx->tile_cache_ngather = (int)gath.size();
-    ctx->tile_cache_gfoff = gf_off;
-    ctx->tile_cache_eb_max = eb_max;
-    ctx->tile_cache_zc_lo = zc_lo;
-    ctx->tile_cache_zc_hi = zc_hi;
-    ctx->tile_cache_valid = true;
+    if (n_proj) TOMO_HIP(ctx, hipMemcpyAsync(ctx->d_stage, h, p.fg_off + sizeof(int) * fg_total, hipMemcpyHostToDevice, ctx->stream));
+    p.n_gather = (int)gath.size();
+    p.n_flat = (int)(gath.size() + flat.size());
+    p.poses.assign(h_poses, h_poses + n_pose_doubles);
+    p.opts = opts;
+    p.ok = p.valid = true;
     return TOMO_OK;
 }
+
+// what a plan's offsets point at on the device
+static inline const AdjC *plan_adjc(const tomo_ctx *ctx) { return (const AdjC *)ctx->d_stage; }
+static inline const GfC *plan_gfc(const tomo_ctx *ctx, const TilePlan &p) { return (const GfC *)((const char *)ctx->d_stage + p.gf_off); }
+static inline const int *plan_fwd_lists(const tomo_ctx *ctx, const TilePlan &p) { return (const int *)((const char *)ctx->d_stage + p.fg_off); }
 
 static inline dim3 tile_grid(const TomoGeomC &g, int tz = ATZ) { return dim3((g.nz + 1 + tz - 1) / tz, (g.ny + 1 + ATY - 1) / ATY, (g.nx + 1 + ATX - 1) / ATX); }
 
@@ -255,26 +238,25 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     if (ctx->fwd_variant != 3 || n_proj <= 0) return TOMO_OK;
     dim3 grid = tile_grid(g);
     if (grid.y > 65535 || grid.z > 65535) return TOMO_OK;
-    bool ok = false;
-    double wb = 2.0;
-    int n_flat = 0;
-    int rc = stage_tile_consts(ctx, h_poses, n_proj, &ok, &wb, &n_flat);
+    const TilePlan *plan = nullptr;
+    int rc = stage_tile_consts(ctx, h_poses, n_proj, &plan);
     if (rc) return rc;
-    if (!ok) return TOMO_OK;
+    if (!plan->ok) return TOMO_OK;
     *done = true;
     xt0 = std::max(xt0, 0);
     xt1 = std::min(xt1, (int)grid.z);
     if (xt1 <= xt0) return TOMO_OK;
     grid.z = (unsigned)(xt1 - xt0);
-    const AdjC *d_c = (const AdjC *)ctx->d_stage;
-    ctx->fwd_blk_flat_ints = 0;
-    ctx->zf_src = nullptr;                  // the block lists below overwrite the back-projection's cached plane flags in d_blk
+    const AdjC *d_c = plan_adjc(ctx);
+    const int n_flat = plan->n_flat;
+    size_t flat_ints = 0;                   // ints of d_blk the flat forward's block list takes (the general kernel's tile list follows)
+    ctx->zf_key.src = nullptr;              // the block lists below overwrite the back-projection's cached plane flags in d_blk
     // Gather-form forward (option "fwd_flat_gather"): whole-volume calls ALL of whose poses take the gather adjoint with three samples per
     // row (step >= 0.95 voxel) and meet the kernel's bounds, on a volume its 32-bit line offsets can address.  Everything else -- the x-slab
     // calls of the sharded solvers included -- keeps k_fwd_flat_tab below.  nx, ny <= 8192: the kernel finds a slab's first candidate sample
     // from float32 positions (|p| about the plane's diagonal, ulp 1e-3 there) with a slack of 5e-3; wider planes would bring the rounding up
     // to the slack.
-    if (whole && ctx->fwd_flat_gather && ctx->tile_cache_ngather == n_proj && ctx->tile_cache_fg_ok && ctx->tile_cache_eb_max < 1.49 &&
+    if (whole && ctx->fwd_flat_gather && plan->n_gather == n_proj && plan->fg_ok && plan->eb_max < 1.49 &&
         std::max(g.nx, g.ny) <= 8192 && (unsigned long long)g.nx * g.ny * g.nz * 4ull <= (1ull << 32)) {
         const size_t zf_ints = ((size_t)g.nz + 3) / 4;
         rc = tomo_ensure_blk(ctx, zf_ints + 1);
@@ -287,11 +269,11 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
         TOMO_LAUNCH(ctx, "k_fwd_live", k_sino_zflags, dim3((unsigned)((g.nz + 255) / 256), (unsigned)std::min<long long>(n_lines, 4096)), dim3(256), 0,
                     d_vol, n_lines, g.nz, d_vf);
         TOMO_LAUNCH(ctx, "k_fwd_live", k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)d_vf, g.nz, g.nz, 0, -1, d_shift);
-        const GfC *d_gfc = (const GfC *)((char *)ctx->d_stage + ctx->tile_cache_gfoff);
-        const int *d_perm = (const int *)((char *)ctx->d_stage + ctx->tile_cache_fgoff);
+        const GfC *d_gfc = plan_gfc(ctx, *plan);
+        const int *d_perm = plan_fwd_lists(ctx, *plan);
         const int nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
         // one launch: the four lists' work-groups follow each other in the grid (an empty list has none)
-        const int *fn = ctx->tile_cache_fg_n;
+        const int *fn = plan->fg_n;
         long long n_wg = 0;
         for (int l = 0; l < 4; ++l) n_wg += 8 * (((long long)((fn[l] + 7) / 8) * nrt + 7) / 8) * nzq;
         if (n_wg >= ((long long)1 << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather forward: grid too large");
@@ -302,29 +284,19 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     if (n_flat > 0) {
         dim3 fg = tile_grid(g, FTZ);
         fg.z = grid.z;
-#ifdef TOMO_MEASUREMENT_VARIANTS
-        if (ctx->fwd_flat_wide && xt0 == 0 && xt1 == (int)tile_grid(g).z)    // measurement variant: 32 x 16 footprint, one image (whole-volume calls only)
-            TOMO_LAUNCH(ctx, "k_fwd_tile_flat", (k_fwd_flat_z<1, 32>), dim3(fg.x, fg.y, (g.nx + 1 + 31) / 32), dim3(FZ_WAVES * 64), 0, d_c, n_flat,
-                        d_proj, d_vol, g, 0);
-        else
-#endif
-        if (fg.x >= 2 && ctx->fwd_flat_ztiles >= 2 && ctx->fwd_flat_tab) {    // round 3: LDS sample table + image pairs, live blocks only
+        if (fg.x >= 2 && ctx->fwd_flat_ztiles >= 2) {             // blocks of two z-adjacent 64-plane images, live blocks only
             const int nzb = (g.nz + 2 * FLZ - 1) / (2 * FLZ), nty = (int)fg.y;
             const size_t n_blk = (size_t)nzb * nty * fg.z;
             if (n_blk >= (size_t)1 << 30) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_forward: volume too large for the flat forward's block list");
-            ctx->fwd_blk_flat_ints = 1 + n_blk + (n_blk + 3) / 4;       // the general kernel's tile list of the same call goes behind it
-            rc = tomo_ensure_blk(ctx, ctx->fwd_blk_flat_ints + (n_proj > n_flat ? 1 + (size_t)grid.x * grid.y * grid.z * 5 / 4 + 1 : 0));
+            flat_ints = LiveList::ints(n_blk);
+            rc = tomo_ensure_blk(ctx, flat_ints + (n_proj > n_flat ? LiveList::ints((size_t)grid.x * grid.y * grid.z) : 0));    // (with the general kernel's list: d_blk grows once)
             if (rc) return rc;
-            int *d_list = ctx->d_blk;
-            unsigned char *d_flags = (unsigned char *)(ctx->d_blk + 1 + n_blk);
-            TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_live, dim3((unsigned)n_blk), dim3(256), 0, d_vol, g, xt0, nzb, nty, d_flags);
-            TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_compact, dim3(1), dim3(1024), 0, d_flags, (int)n_blk, d_list);
+            const LiveList live(ctx->d_blk, 0, n_blk);
+            TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_live, dim3((unsigned)n_blk), dim3(256), 0, d_vol, g, xt0, nzb, nty, live.flags);
+            TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_compact, dim3(1), dim3(1024), 0, live.flags, (int)n_blk, live.list);
             TOMO_LAUNCH(ctx, "k_fwd_tile_flat", k_fwd_flat_tab, dim3((unsigned)n_blk), dim3(FZ_WAVES * 64), 0, d_c, n_flat, d_proj, d_vol, g, xt0,
-                        (const int *)d_list, (const unsigned char *)d_flags, nzb, nty);
+                        (const int *)live.list, (const unsigned char *)live.flags, nzb, nty);
         }
-        else if (fg.x >= 2 && ctx->fwd_flat_ztiles >= 2)         // two z-adjacent tiles per work-group share the per-row set-up
-            TOMO_LAUNCH(ctx, "k_fwd_tile_flat", k_fwd_flat_z<2>, dim3((fg.x + 1) / 2, fg.y, fg.z), dim3(FZ_WAVES * 64), 0, d_c, n_flat,
-                        d_proj, d_vol, g, xt0);
         else
             TOMO_LAUNCH(ctx, "k_fwd_tile_flat", k_tile_flat<true>, fg, dim3(ADJ_WAVES * 64), 0, d_c, n_flat, d_proj,
                         (float *)d_vol, g, (const unsigned *)nullptr, 1.f, xt0);
@@ -332,16 +304,14 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     if (n_proj > n_flat) {
         // the general kernel over the LIVE tiles only (kernels_tile.hip.h, k_tile_live); its list sits behind the flat forward's in d_blk
         const size_t n_tile = (size_t)grid.x * grid.y * grid.z;
-        const size_t flat_ints = ctx->fwd_blk_flat_ints;
         if (n_tile >= (size_t)1 << 30) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_forward: volume too large for the tile list");
-        rc = tomo_ensure_blk(ctx, flat_ints + 1 + n_tile + (n_tile + 3) / 4);
+        rc = tomo_ensure_blk(ctx, flat_ints + LiveList::ints(n_tile));
         if (rc) return rc;
-        int *t_list = ctx->d_blk + flat_ints;
-        unsigned char *t_flags = (unsigned char *)(t_list + 1 + n_tile);
-        TOMO_LAUNCH(ctx, "k_fwd_live", k_tile_live, dim3((unsigned)n_tile), dim3(256), 0, d_vol, g, xt0, (int)grid.x, (int)grid.y, t_flags);
-        TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_compact, dim3(1), dim3(1024), 0, (const unsigned char *)t_flags, (int)n_tile, t_list);
+        const LiveList live(ctx->d_blk, flat_ints, n_tile);
+        TOMO_LAUNCH(ctx, "k_fwd_live", k_tile_live, dim3((unsigned)n_tile), dim3(256), 0, d_vol, g, xt0, (int)grid.x, (int)grid.y, live.flags);
+        TOMO_LAUNCH(ctx, "k_fwd_live", k_fwd_compact, dim3(1), dim3(1024), 0, (const unsigned char *)live.flags, (int)n_tile, live.list);
         TOMO_LAUNCH(ctx, "k_fwd_tile", (k_tile<true, TILE_FWD_WAVES>), dim3((unsigned)n_tile), dim3(TILE_FWD_WAVES * 64), 0, d_c + n_flat, n_proj - n_flat, d_proj, (float *)d_vol,
-                    g, (const unsigned *)nullptr, 1.f, xt0, (const int *)t_list, (int)grid.x, (int)grid.y, (const int *)nullptr);
+                    g, (const unsigned *)nullptr, 1.f, xt0, (const int *)live.list, (int)grid.x, (int)grid.y, (const int *)nullptr);
     }
     return TOMO_OK;
 }
@@ -412,23 +382,26 @@ static int adjoint_atomic(tomo_ctx *ctx, const double *h_poses, int n_proj, cons
     return TOMO_OK;
 }
 
-// The passes that derive from freshly written plane flags (d_zf, in d_blk) and the key under which adjoint_tiles finds them: used by
+// the key of plane flags for this sinogram under the current geometry and the poses staged last (stage_tile_consts)
+static inline ZfKey zf_key_of(const tomo_ctx *ctx, const void *d_proj, int n_proj)
+{
+    return ZfKey{d_proj, n_proj, ctx->g.ndz, ctx->g.ndx, ctx->g.nz, ctx->plan.zc_lo, ctx->plan.zc_hi};
+}
+
+// The passes that derive from freshly written plane flags (head.zf, in d_blk) and the key under which adjoint_tiles finds them: used by
 // adjoint_tiles after its own scan and by tomo_vec_residual_scale_flags (tomo_ctx.hip), whose residual pass wrote the flags itself
-// (recorded = true: see tomo_ctx.h, zf_recorded).  zc range: that of the poses staged last (stage_tile_consts).
-int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, unsigned char *d_zf, int *d_zcum, int *d_zshift,
-                       const char *prof_name, bool recorded)
+// (recorded = true: see tomo_ctx.h, zf_recorded).
+int tomo_record_zflags(tomo_ctx *ctx, const void *d_proj, int n_proj, bool want_cum, bool want_shift, const BlkHead &head, const char *prof_name,
+                       bool recorded)
 {
     const TomoGeomC &g = ctx->g;
-    if (want_cum) TOMO_LAUNCH(ctx, prof_name, k_zflags_prefix, dim3(1), dim3(1024), 0, (const unsigned char *)d_zf, g.ndz, d_zcum);
+    if (want_cum) TOMO_LAUNCH(ctx, prof_name, k_zflags_prefix, dim3(1), dim3(1024), 0, (const unsigned char *)head.zf, g.ndz, head.zcum);
     if (want_shift)
-        TOMO_LAUNCH(ctx, prof_name, k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)d_zf, g.ndz, g.nz, ctx->tile_cache_zc_lo,
-                    ctx->tile_cache_zc_hi, d_zshift);
-    ctx->zf_src = d_proj;
-    ctx->zf_nproj = n_proj;
+        TOMO_LAUNCH(ctx, prof_name, k_zchunk_shift, dim3(1), dim3(64), 0, (const unsigned char *)head.zf, g.ndz, g.nz, ctx->plan.zc_lo, ctx->plan.zc_hi,
+                    head.zshift);
+    ctx->zf_key = zf_key_of(ctx, d_proj, n_proj);
     ctx->zf_has_cum = want_cum;
     ctx->zf_has_shift = want_shift;
-    ctx->zf_ndz = g.ndz; ctx->zf_ndx = g.ndx; ctx->zf_nz = g.nz;
-    ctx->zf_zc_lo = ctx->tile_cache_zc_lo; ctx->zf_zc_hi = ctx->tile_cache_zc_hi;
     ctx->zf_recorded = recorded;
     return TOMO_OK;
 }
@@ -449,15 +422,12 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     const size_t n_det = (size_t)g.ndx * g.ndz;
     dim3 grid = tile_grid(g);
     *done = false;
-    bool ok = false;
-    double weight_bound = 2.0;
-    int n_flat = 0;
     if (ctx->adj_variant == 1 || n_proj <= 0 || grid.y > 65535 || grid.z > 65535) return TOMO_OK;
-    int n_gather = 0;
-    const GfC *d_gfc = nullptr;
-    int rc = stage_tile_consts(ctx, h_poses, n_proj, &ok, &weight_bound, &n_flat, &n_gather, &d_gfc);
+    const TilePlan *plan = nullptr;
+    int rc = stage_tile_consts(ctx, h_poses, n_proj, &plan);
     if (rc) return rc;
-    if (!ok) return TOMO_OK;
+    if (!plan->ok) return TOMO_OK;
+    const int n_flat = plan->n_flat, n_gather = plan->n_gather;
     const int n_xt = (int)grid.z;
     xt0 = std::max(xt0, 0);
     xt1 = std::min(xt1, n_xt);
@@ -465,35 +435,29 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
     *done = true;
     if (xt1 <= xt0) return TOMO_OK;
     grid.z = (unsigned)(xt1 - xt0);
-    const AdjC *d_c = (const AdjC *)ctx->d_stage;
+    const AdjC *d_c = plan_adjc(ctx);
+    const GfC *d_gfc = plan_gfc(ctx, *plan);
     // Which detector-z planes of this call's sinogram hold a non-zero value at all (any projection, any row)?  A residual sinogram is exactly
     // zero wherever the rays miss the object's support: a wave of the gather kernel whose 64 voxel planes can only receive from all-zero
     // planes skips its loads and its plane loop (zlive), the general kernel skips a (tile, projection) whose rays all lie in such planes
     // (zcum: prefix counts of the flags).  One coalesced pass over the sinogram (0.8 ms for 4.3 GB); flags and counts live in d_blk.
-    unsigned char *d_zf = nullptr;
-    int *d_zcum = nullptr, *d_zshift = nullptr;
+    // The general kernel's live tile list (below) sits behind them: d_blk is sized once, here.
+    BlkHead head{};
+    const size_t n_tile = (size_t)grid.x * grid.y * grid.z;
     if (n_gather > 0 || n_proj > n_flat) {
-        const size_t zf_ints = ((size_t)g.ndz + 3) / 4;
-        const size_t n_tile_all = (size_t)grid.x * grid.y * grid.z;
-        rc = tomo_ensure_blk(ctx, zf_ints + (size_t)g.ndz + 2 + (n_proj > n_flat ? 1 + n_tile_all + (n_tile_all + 3) / 4 : 0));
+        rc = tomo_blk_head(ctx, n_proj > n_flat ? LiveList::ints(n_tile) : 0, &head);
         if (rc) return rc;
-        d_zf = (unsigned char *)ctx->d_blk;
-        d_zcum = ctx->d_blk + zf_ints;
-        d_zshift = d_zcum + g.ndz + 1;
         const bool want_cum = n_proj > n_flat;
-        // (option "reuse_sino_flags": the x-slab calls of one back-projection pass scan the sinogram once, not once per slab)
-        // The key holds everything the cached words depend on: the sinogram and its shape (layout of d_zf / d_zcum), and the
-        // volume height and the poses' integer z offsets the chunk shift was computed from.
-        // (zf_recorded: the flags were recorded by the residual pass that wrote d_proj and nothing ran since -- no caller's word needed)
-        const bool cached = (ctx->reuse_sino_flags || ctx->zf_recorded) && ctx->zf_src == (const void *)d_proj && ctx->zf_nproj == n_proj && (ctx->zf_has_cum || !want_cum) &&
-                            (ctx->zf_has_shift || n_gather == 0) && ctx->zf_ndz == g.ndz && ctx->zf_ndx == g.ndx && ctx->zf_nz == g.nz &&
-                            ctx->zf_zc_lo == ctx->tile_cache_zc_lo && ctx->zf_zc_hi == ctx->tile_cache_zc_hi;
+        // (option "reuse_sino_flags": the x-slab calls of one back-projection pass scan the sinogram once, not once per slab;
+        // zf_recorded: the flags were recorded by the residual pass that wrote d_proj and nothing ran since -- no caller's word needed)
+        const bool cached = ctx->zf_key == zf_key_of(ctx, d_proj, n_proj) && (ctx->zf_has_cum || !want_cum) && (ctx->zf_has_shift || n_gather == 0) &&
+                            (ctx->reuse_sino_flags || ctx->zf_recorded);
         if (!cached) {
-            TOMO_HIP(ctx, hipMemsetAsync(d_zf, 0, (size_t)g.ndz, ctx->stream));
+            TOMO_HIP(ctx, hipMemsetAsync(head.zf, 0, (size_t)g.ndz, ctx->stream));
             const long long n_rows = (long long)n_proj * g.ndx;
             const unsigned gy = (unsigned)std::min<long long>(n_rows, 4096);
-            TOMO_LAUNCH(ctx, "k_sino_zflags", k_sino_zflags, dim3((unsigned)((g.ndz + 255) / 256), gy), dim3(256), 0, d_proj, n_rows, g.ndz, d_zf);
-            rc = tomo_record_zflags(ctx, d_proj, n_proj, want_cum, n_gather > 0, d_zf, d_zcum, d_zshift, "k_sino_zflags", false);
+            TOMO_LAUNCH(ctx, "k_sino_zflags", k_sino_zflags, dim3((unsigned)((g.ndz + 255) / 256), gy), dim3(256), 0, d_proj, n_rows, g.ndz, head.zf);
+            rc = tomo_record_zflags(ctx, d_proj, n_proj, want_cum, n_gather > 0, head, "k_sino_zflags", false);
             if (rc) return rc;
         }
     }
@@ -508,15 +472,15 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
             const long long n_wg = patched ? ((n_patch + 7) / 8) * 8 * (GPX * GPY) : (long long)nzq * ntx * nty;
             if (n_wg >= ((long long)1 << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather adjoint: grid too large");
             const dim3 ggrid((unsigned)n_wg);
-            const int zc_lo = ctx->tile_cache_zc_lo, zc_hi = ctx->tile_cache_zc_hi;
+            const int zc_lo = plan->zc_lo, zc_hi = plan->zc_hi;
             const float *u_v = upd ? upd->v : nullptr, *u_gt = upd ? upd->gt : nullptr;
             const int u_pos = upd ? upd->positivity : 0;
             if (upd && upd->gt) TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));      // the slot k_update sums into (tomo_vec_update)
 #define GATHER_LAUNCH(NJ, UPD)                                                                                                                       \
     TOMO_LAUNCH(ctx, "k_adj_gather_flat", (k_adj_gather_flat<NJ, UPD>), ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, d_vol, g, xs, xe, patched, \
-                (const unsigned char *)d_zf, zc_lo, zc_hi, (const int *)d_zshift, u_v, u_gt, u_pos, ctx->d_red)
+                (const unsigned char *)head.zf, zc_lo, zc_hi, (const int *)head.zshift, u_v, u_gt, u_pos, ctx->d_red)
             // NJ = 6: finer sampling along the rays (step down to ~0.475 voxel): six samples per row can reach a column
-            if (ctx->tile_cache_eb_max < 1.49) { if (upd) GATHER_LAUNCH(3, 1); else GATHER_LAUNCH(3, 0); }
+            if (plan->eb_max < 1.49) { if (upd) GATHER_LAUNCH(3, 1); else GATHER_LAUNCH(3, 0); }
             else { if (upd) GATHER_LAUNCH(6, 1); else GATHER_LAUNCH(6, 0); }
 #undef GATHER_LAUNCH
         }
@@ -532,24 +496,18 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
         dim3 fgrid = tile_grid(g, FTZ);
         fgrid.z = grid.z;
         TOMO_LAUNCH(ctx, "k_adj_tile_flat", k_tile_flat<false>, fgrid, dim3(ADJ_WAVES * 64), 0, d_c + n_gather, n_flat - n_gather, (float *)d_proj,
-                    d_vol, g, (const unsigned *)d_absmax, (float)weight_bound, xt0);
+                    d_vol, g, (const unsigned *)d_absmax, (float)plan->weight_bound, xt0);
     }
     if (n_proj > n_flat) {
         // the tiles some projection can bring something to, compacted in launch order (kernels_tile.hip.h: k_tile_adj_live); list and flags
         // sit behind the plane flags and their prefix counts in d_blk
-        const size_t n_tile = (size_t)grid.x * grid.y * grid.z;
         if (n_tile >= (size_t)1 << 30) return tomo_fail(ctx, TOMO_ERR_ARG, "tomo_adjoint: volume too large for the tile list");
-        const size_t head = ((size_t)g.ndz + 3) / 4 + (size_t)g.ndz + 2;
-        rc = tomo_ensure_blk(ctx, head + 1 + n_tile + (n_tile + 3) / 4);      // (grows at most once per geometry: d_zf / d_zcum are re-derived below)
-        if (rc) return rc;
-        if ((unsigned char *)ctx->d_blk != d_zf) return tomo_fail(ctx, TOMO_ERR_STATE, "tomo_adjoint: block buffer moved");
-        int *t_list = ctx->d_blk + head;
-        unsigned char *t_flags = (unsigned char *)(t_list + 1 + n_tile);
+        const LiveList live(ctx->d_blk, head.ints, n_tile);
         TOMO_LAUNCH(ctx, "k_sino_zflags", k_tile_adj_live, dim3((unsigned)n_tile), dim3(64), 0, d_c + n_flat, n_proj - n_flat, g, xt0, (int)grid.x,
-                    (int)grid.y, (const int *)d_zcum, t_flags);
-        TOMO_LAUNCH(ctx, "k_sino_zflags", k_fwd_compact, dim3(1), dim3(1024), 0, (const unsigned char *)t_flags, (int)n_tile, t_list);
+                    (int)grid.y, (const int *)head.zcum, live.flags);
+        TOMO_LAUNCH(ctx, "k_sino_zflags", k_fwd_compact, dim3(1), dim3(1024), 0, (const unsigned char *)live.flags, (int)n_tile, live.list);
         TOMO_LAUNCH(ctx, "k_adj_tile", (k_tile<false, TILE_ADJ_WAVES>), dim3((unsigned)n_tile), dim3(TILE_ADJ_WAVES * 64), 0, d_c + n_flat, n_proj - n_flat, (float *)d_proj, d_vol, g,
-                    (const unsigned *)d_absmax, (float)weight_bound, xt0, (const int *)t_list, (int)grid.x, (int)grid.y, (const int *)d_zcum);
+                    (const unsigned *)d_absmax, (float)plan->weight_bound, xt0, (const int *)live.list, (int)grid.x, (int)grid.y, (const int *)head.zcum);
     }
     return TOMO_OK;
 }
