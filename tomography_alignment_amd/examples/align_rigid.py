@@ -264,7 +264,8 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
-        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None):
+        kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None, export=None,
+        export_dtype=np.uint8):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
     fsc            True: every history entry gains `fsc_resolution` (pixels) and `fsc_curve` (_fsc_entry); needs no phantom.
@@ -272,6 +273,9 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
                    value every history entry carries it as `cor`; with None nothing changes.
     prealign       None, "moment", "profile" (only without a communicator) or an (n_proj, 3) array (resolve_prealign): the loop's base
                    pose is (xyz0, 0, 0); with None the loop is built as before.
+    export         None, or a directory: after the last outer iteration postprocess.export_stack writes the reconstruction there from
+                   where it lies in HBM (8- or 16-bit z slices by export_dtype, meta.json, previews; rank 0 of a sharded run, whose
+                   volume is whole on every rank).  With None nothing of the run changes.
     kernel_names   with a HIP context: the history carries the HIP-event kernel time of each half of each outer iteration for these names.
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
@@ -289,6 +293,9 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     finally:
         if res is not None:
             res.close()
+    if export is not None and loop.d_rec is not None and loop.rank == 0:
+        from .. import postprocess
+        postprocess.export_stack(loop.d_rec, export, dtype=export_dtype, ctx=loop.ctx, shape=loop.vox_shape)
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
@@ -483,8 +490,13 @@ def main():
                     "from the sinograms first (rotation_axis.find_center; one GPU)")
     ap.add_argument("--prealign", default=None, metavar="moment|profile|file", help="start the shifts from the projections' moments "
                     "(align.consistency; one GPU), or from the key xyz0 of the data file itself with 'file' (preprocess --prealign)")
+    ap.add_argument("--export", default=None, metavar="DIR", help="write the reconstruction as a stack of z slices (slice_%%05d.npy), "
+                    "meta.json and previews into DIR, converted on the GPU (postprocess.export_stack; --levels 1)")
+    ap.add_argument("--export-dtype", choices=("uint8", "uint16"), default="uint8")
     a = ap.parse_args()
     cor = a.cor if a.cor in (None, "auto") else float(a.cor)
+    if a.export is not None and a.levels != 1:
+        ap.error("--export goes with --levels 1")
     if a.prealign not in (None, "moment", "profile", "file"):
         ap.error("--prealign must be moment, profile or file")
     import os
@@ -497,7 +509,8 @@ def main():
         ap.error("--prealign file: %s holds no xyz0 (write it with examples/preprocess --prealign)" % a.data)
     prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
-        run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
+        run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign, export=a.export,
+            export_dtype=np.dtype(a.export_dtype))
     else:
         run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:
