@@ -46,7 +46,7 @@ import time
 
 import numpy as np
 
-from .. import alignment, multires, resolution, rotation_axis
+from .. import alignment, multires, registration, resolution, rotation_axis
 from ..align import consistency
 from ..recon import fbp, fbp_mpi, sirt, sirt_mpi
 from ..utilities import geometry
@@ -265,8 +265,10 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
         kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None, export=None,
-        export_dtype=np.uint8):
+        export_dtype=np.uint8, register_truth=False):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
+    register_truth True, and the data carry a phantom: every history entry gains `truth_shift` and `rmse_registered` (_truth_entry), the
+                   RMSE after the gauge translation between reconstruction and phantom is taken out; `rmse` stays as it is.
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
     fsc            True: every history entry gains `fsc_resolution` (pixels) and `fsc_curve` (_fsc_entry); needs no phantom.
     cor            None, a number or "auto" (resolve_cor; "auto" only without a communicator): the geometry's cor_shift x.  With a
@@ -286,13 +288,16 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     loop = OuterLoop(data, backend=backend, comm=comm, kernel_names=kernel_names, cor=cor, **start)
     history = []
     res = resolution.Resolution(loop.ctx) if fsc else None
+    reg = registration.Registrar(loop.ctx) if (register_truth and loop.d_gt is not None) else None
     try:
         for it in range(n_outer):
             history.append(_outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, fsc_with=res,
-                                            extra=None if cor is None else {"cor": cor}))
+                                            extra=None if cor is None else {"cor": cor}, truth_with=reg))
     finally:
         if res is not None:
             res.close()
+        if reg is not None:
+            reg.close()
     if export is not None and loop.d_rec is not None and loop.rank == 0:
         from .. import postprocess
         postprocess.export_stack(loop.d_rec, export, dtype=export_dtype, ctx=loop.ctx, shape=loop.vox_shape)
@@ -310,9 +315,27 @@ def _fsc_entry(loop, res):
     return {"fsc_resolution": float(loop.factor * (curve.nyquist if r is None else r)), "fsc_curve": curve}
 
 
-def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, extra=None, fsc_with=None):
+def _truth_entry(loop, reg, upsample=10):
+    """`truth_shift`: the translation that moves the reconstruction onto the phantom (registration.Registrar.register, upsample 10, one
+    pass).  No mask and no mean: the Fourier shift does not lengthen a volume, so the largest plain correlation IS the smallest
+    ||phantom - shifted reconstruction|| over the candidates, the coarse peak is one of them and is no worse than a shift of zero;
+    without a mask there is no mask bias for a second pass to remove.
+    `rmse_registered`: ||phantom - shift_volume(rec, truth_shift)|| / ||phantom||, formed on the device from loop.d_rec, which is not
+    written; `rmse` punishes a correct alignment that moved the object by half a voxel like a wrong one, this does not."""
+    be, shape = loop.be, loop.vox_shape
+    found = reg.register(loop.d_gt, loop.d_rec, upsample=upsample, mask=None, subtract_mean=False, passes=1, shape=shape)
+    d_s = reg.shift_volume(loop.d_rec, found.shift, shape=shape)
+    try:
+        norm = np.sqrt(be.dot(loop.d_gt, loop.d_gt))
+        rmse = float(np.sqrt(be.diff_sumsq(loop.d_gt, d_s)) / norm) if norm > 0 else float("nan")
+    finally:
+        d_s.free()
+    return {"truth_shift": [float(v) for v in found.shift], "rmse_registered": rmse}
+
+
+def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_names, verbose, extra=None, fsc_with=None, truth_with=None):
     """One outer iteration of `loop` -- SIRT, then the alignment pass -- and its history entry (`extra`: more keys for it; `fsc_with`: a
-    resolution.Resolution -> the entry of _fsc_entry)."""
+    resolution.Resolution -> the entry of _fsc_entry; `truth_with`: a registration.Registrar -> the entry of _truth_entry)."""
     ctx = loop.ctx
     k0 = _kernel_ms(ctx, kernel_names)
     t0 = time.perf_counter()
@@ -320,12 +343,14 @@ def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_na
     if ctx is not None:
         ctx.sync()
     t1 = time.perf_counter()
+    truth = _truth_entry(loop, truth_with) if truth_with is not None else None      # of the reconstruction `rmse` is of; outside both walls
+    t1a = time.perf_counter() if truth is not None else t1
     k1 = _kernel_ms(ctx, kernel_names)
     res = loop.align(bounds, **(align_kwargs or {}))
     t2 = time.perf_counter()
     k2 = _kernel_ms(ctx, kernel_names)
     entry = {"outer": it, "rmse": float(err[-1]), "sirt_iterations": int(k_done), "residual": float(res["fun"].sum()), "launches": res["n_launch"],
-             "evals": res["n_eval"], "driver": res.get("driver"), "sirt_wall_s": round(t1 - t0, 3), "align_wall_s": round(t2 - t1, 3),
+             "evals": res["n_eval"], "driver": res.get("driver"), "sirt_wall_s": round(t1 - t0, 3), "align_wall_s": round(t2 - t1a, 3),
              "ranks": loop.size}
     if kernel_names and ctx is not None:
         entry["sirt_kernel_ms"] = {k: round(k1[k] - k0[k], 1) for k in k1 if k1[k] - k0[k] > 0}
@@ -335,6 +360,8 @@ def _outer_iteration(loop, it, sirt_iters, bounds, init, align_kwargs, kernel_na
         entry.update(extra)
     if fsc_with is not None:
         entry.update(_fsc_entry(loop, fsc_with))
+    if truth is not None:
+        entry.update(truth)
     if verbose and loop.rank == 0:
         print(entry)
     return entry
@@ -493,6 +520,8 @@ def main():
     ap.add_argument("--export", default=None, metavar="DIR", help="write the reconstruction as a stack of z slices (slice_%%05d.npy), "
                     "meta.json and previews into DIR, converted on the GPU (postprocess.export_stack; --levels 1)")
     ap.add_argument("--export-dtype", choices=("uint8", "uint16"), default="uint8")
+    ap.add_argument("--register-truth", action="store_true", help="with a phantom in the data: also report the RMSE after the reconstruction "
+                    "is registered to the phantom (truth_shift, rmse_registered); --levels 1 only")
     a = ap.parse_args()
     cor = a.cor if a.cor in (None, "auto") else float(a.cor)
     if a.export is not None and a.levels != 1:
@@ -510,7 +539,7 @@ def main():
     prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
         run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign, export=a.export,
-            export_dtype=np.dtype(a.export_dtype))
+            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth)
     else:
         run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:

@@ -62,7 +62,10 @@ class FSCCurve(object):
     C, PA, PB, count   float64 (S,), S = min(n)/2 + 1 (module docstring)
     fsc                C / sqrt(PA PB); 0 where the denominator is 0 (shell 0 of mean-free inputs)
     freq               s / (nmax voxel_size), cycles per unit length
-    nmax, voxel_size"""
+    nmax, voxel_size
+    shift              None, or with fsc(..., register=True) the translation that was applied to the second volume first"""
+
+    shift = None
 
     def __init__(self, C, PA, PB, count, nmax, voxel_size=1.0):
         self.C, self.PA, self.PB, self.count = (np.asarray(v, np.float64) for v in (C, PA, PB, count))
@@ -215,10 +218,39 @@ class Resolution(HandleOwner):
             for t in tmp:
                 t.free()
 
-    def fsc(self, vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, shape=None):
-        """The FSC of two volumes (nx, ny, nz) -> FSCCurve (module docstring)."""
-        t = self.shell_sums(vol_a, vol_b, 3, shape=shape, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean)[0]
-        return FSCCurve(t[0], t[1], t[2], t[3], max(_shape_of(vol_a, shape, 3, "vol_a")), voxel_size)
+    def fsc(self, vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, shape=None, register=False,
+            upsample=10):
+        """The FSC of two volumes (nx, ny, nz) -> FSCCurve (module docstring).
+        register   True: vol_b is first registered to vol_a (registration.Registrar.register with the same mask arguments, `upsample`
+                   and passes=2) and Fourier-shifted into a scratch volume, and the curve is taken of that; the curve's `shift` is the
+                   translation found.  For two reconstructions that were aligned independently and so differ by the alignment's gauge."""
+        if not register:
+            t = self.shell_sums(vol_a, vol_b, 3, shape=shape, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean)[0]
+            return FSCCurve(t[0], t[1], t[2], t[3], max(_shape_of(vol_a, shape, 3, "vol_a")), voxel_size)
+        from . import registration
+        sv = _shape_of(vol_a, shape, 3, "vol_a")
+        if _shape_of(vol_b, shape, 3, "vol_b") != sv:
+            raise ValueError("the two inputs must have one shape, got %s and %s" % (sv, _shape_of(vol_b, shape, 3, "vol_b")))
+        _fsc_lib.n_shells(3, 1, *sv)
+        self._ready_ctx(vol_a if _is_dev(vol_a) else vol_b)
+        tmp = []
+        try:
+            d_a, d_b = vol_a, vol_b
+            if not _is_dev(vol_b):
+                d_b = self.ctx.to_device(np.ascontiguousarray(vol_b, np.float32), np.float32)
+                tmp.append(d_b)
+            with registration.Registrar(self.ctx) as rg:
+                reg = rg.register(d_a, d_b, upsample=upsample, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean, passes=2,
+                                  shape=sv)
+                d_s = rg.shift_volume(d_b, reg.shift, shape=sv)
+            tmp.append(d_s)
+            t = self.shell_sums(d_a, d_s, 3, shape=sv, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean)[0]
+        finally:
+            for d in tmp:
+                d.free()
+        curve = FSCCurve(t[0], t[1], t[2], t[3], max(sv), voxel_size)
+        curve.shift = tuple(float(v) for v in reg.shift)
+        return curve
 
     def frc(self, stack_a, stack_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, shape=None, pool=False):
         """The FRC of every pair of planes of two stacks (nb, nx, nz): a list of nb FSCCurves, or with `pool` their pool_curves.  The
@@ -239,10 +271,12 @@ class Resolution(HandleOwner):
         return out
 
 
-def fsc(vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, ctx=None, shape=None):
+def fsc(vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, ctx=None, shape=None, register=False,
+        upsample=10):
     """Resolution.fsc on a handle of its own."""
     with Resolution(ctx) as r:
-        return r.fsc(vol_a, vol_b, voxel_size=voxel_size, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean, shape=shape)
+        return r.fsc(vol_a, vol_b, voxel_size=voxel_size, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean, shape=shape,
+                     register=register, upsample=upsample)
 
 
 def frc(stack_a, stack_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, ctx=None, shape=None, pool=False):
