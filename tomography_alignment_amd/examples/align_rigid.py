@@ -265,8 +265,13 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
         kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None, export=None,
-        export_dtype=np.uint8, register_truth=False):
+        export_dtype=np.uint8, register_truth=False, segment=False):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
+    segment        True: after the last outer iteration the reconstruction is segmented where it lies in HBM (_segmentation: Otsu's
+                   threshold over the cylinder, threshold, label with 6 neighbours, measure; rank 0 of a sharded run) and the last
+                   history entry gains `segmentation` = {"threshold", "n_components", "foreground_fraction", "largest_fraction"};
+                   with `export` as well, export/labels_meta.json holds the same figures and the table of at most the 1000 largest
+                   components.  With False (the default) nothing of the run changes.
     register_truth True, and the data carry a phantom: every history entry gains `truth_shift` and `rmse_registered` (_truth_entry), the
                    RMSE after the gauge translation between reconstruction and phantom is taken out; `rmse` stays as it is.
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
@@ -301,9 +306,46 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     if export is not None and loop.d_rec is not None and loop.rank == 0:
         from .. import postprocess
         postprocess.export_stack(loop.d_rec, export, dtype=export_dtype, ctx=loop.ctx, shape=loop.vox_shape)
+    if segment and loop.d_rec is not None and loop.rank == 0:
+        if not history:
+            history.append({})
+        history[-1]["segmentation"] = _segmentation(loop, export, verbose)
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
+
+
+def _segmentation(loop, export=None, verbose=False, limit=1000):
+    """The reconstruction (loop.d_rec, not written) split into its connected objects on the device: Otsu's threshold of the 4096-bin
+    histogram over the reconstruction cylinder, the mask v >= threshold inside the cylinder, its components with 6 neighbours and their
+    measures; only the tables come to the host.  -> {"threshold", "n_components", "foreground_fraction" (of the cylinder's voxels),
+    "largest_fraction" (of the foreground; 0 without one)}.  export: a directory; labels_meta.json there holds the same and
+    "components", the `limit` largest as {"label", "count", "bbox", "centroid"}."""
+    import json
+    import os
+
+    from .. import segment as seg_mod
+    from ..postprocess import region_r4
+    shape = tuple(int(s) for s in loop.vox_shape)
+    with seg_mod.Segmenter(loop.ctx) as seg:
+        t, = seg.otsu(loop.d_rec, 2, 4096, None, "cylinder", shape=shape)
+        d_mask = seg.threshold(loop.d_rec, lo=t, region="cylinder", shape=shape)
+        d_labels, n = seg.label(d_mask, 1, shape=shape)
+        d_mask.free()
+        comp = seg.measure(d_labels, n, shape=shape)
+        d_labels.free()
+    fg = int(comp.count.sum())
+    a, b = (2 * np.arange(k, dtype=np.int64) - k + 1 for k in shape[:2])          # the region's integer test (postprocess)
+    inside = int(np.count_nonzero(a[:, None] ** 2 + b[None, :] ** 2 <= region_r4("cylinder", shape[0], shape[1]))) * shape[2]
+    out = {"threshold": float(t), "n_components": int(n), "foreground_fraction": fg / float(inside),
+           "largest_fraction": float(comp.count.max()) / fg if n else 0.0}
+    if export is not None:
+        os.makedirs(export, exist_ok=True)
+        with open(os.path.join(export, "labels_meta.json"), "w") as f:
+            json.dump(dict(out, components=comp.table(limit)), f, indent=1)
+    if verbose:
+        print({"segmentation": out})
+    return out
 
 
 def _fsc_entry(loop, res):
@@ -520,12 +562,17 @@ def main():
     ap.add_argument("--export", default=None, metavar="DIR", help="write the reconstruction as a stack of z slices (slice_%%05d.npy), "
                     "meta.json and previews into DIR, converted on the GPU (postprocess.export_stack; --levels 1)")
     ap.add_argument("--export-dtype", choices=("uint8", "uint16"), default="uint8")
+    ap.add_argument("--segment", action="store_true", help="segment the reconstruction on the GPU after the last outer iteration: Otsu's "
+                    "threshold over the cylinder, connected components with 6 neighbours and their measures (segment; --levels 1); with "
+                    "--export, DIR/labels_meta.json holds the component table")
     ap.add_argument("--register-truth", action="store_true", help="with a phantom in the data: also report the RMSE after the reconstruction "
                     "is registered to the phantom (truth_shift, rmse_registered); --levels 1 only")
     a = ap.parse_args()
     cor = a.cor if a.cor in (None, "auto") else float(a.cor)
     if a.export is not None and a.levels != 1:
         ap.error("--export goes with --levels 1")
+    if a.segment and a.levels != 1:
+        ap.error("--segment goes with --levels 1")
     if a.prealign not in (None, "moment", "profile", "file"):
         ap.error("--prealign must be moment, profile or file")
     import os
@@ -539,7 +586,7 @@ def main():
     prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
         run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign, export=a.export,
-            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth)
+            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth, segment=a.segment)
     else:
         run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:
