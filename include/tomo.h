@@ -107,6 +107,11 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *                 spread a wave over more windows of volume lines.
  *                 Calls that do not qualify, tomo_forward_xslab and value 0 keep k_fwd_flat_tab; needs "adj_flat_gather" 1 (the two
  *                 kernels share their per-projection constants)
+ *   "fwd_gather_patch" order in which the work-groups of k_fwd_gather_flat are dealt to the XCDs; the sums and their bits are the same in all:
+ *                 0 the k-th eighth of the (projection group, row tile) pairs of a z quad to XCD k, row tiles fastest;
+ *                 1 (default) patches of 16 projection groups x 4 row tiles per XCD, whose rays share volume lines in that XCD's L2, when
+ *                 the call has 128 such patches or more (1024^3 x 1024 angles: 1600; 256^3 x 256: 64), else as 0;
+ *                 2 patches at any size.  Other values are TOMO_ERR_ARG
  *   "adj_flat_gather" 1 (default): untilted projections (as for "tile_flat") whose x-y lattice is coarse enough take the gather-form
  *                 adjoint (accumulators in registers, no atomics) instead of the LDS-atomic flat tile kernel: three consecutive detector
  *                 rows must cover a voxel's footprint, (|cos phi| + |sin phi|) / det_dx < 1.45, and six consecutive samples,

@@ -191,7 +191,8 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
     // L2 -- with a plain (z, y, x) grid they formed a 128 x 1.5-tile strip with almost no common rows and every row load went
     // to the fabric (0.88 TB per launch at 1024^3).  Work-groups are dealt to the XCDs round-robin in dispatch order, so XCD k
     // sees the linear ids k, k+8, ...: those are mapped to compact GPX x GPY patches of (x, y) tiles of one z quad (patch
-    // p*8 + k for the p-th group of 96 of them): ~10x row reuse within a patch.
+    // p*8 + k for the p-th group of 96 of them): ~10x row reuse within a patch.  ("XCD patches": k_fwd_gather_flat deals its
+    // work-groups the same way.)
     // (Small grids keep the plain order, patched = 0: the patch grid is padded to 8 x 96 work-groups, which costs more than
     // the reuse gains below ~256 patches.  Measured at 1024^3: same speed; fabric traffic -64 % on a 64-angle launch, -15 %
     // (0.89 -> 0.76 TB) over 1024 angles, where the work-groups of a patch drift apart in angle index.)
@@ -479,12 +480,28 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
 // ------------------------------------------------------------------------------------------------
 #define FGROWS 24
 #define FG_NONE (1 << 29)          // "this lane has no line": above every real line index, far from integer overflow
+#ifndef FPG
+#define FPG 16             // patch of (projection groups x row tiles) that an XCD's work-groups cover together.  MEASURED at 1024^3 x 1024
+#define FPR 4              // (profiles/fwd_patches_before_after.md): every shape of >= 13 groups x 2 .. 4 row tiles gives the same time, 8 % under the
+#endif                     // plain order; the model's choice, 8 x 12, gives none (tools/fwd_gather_model.py counts lines, not when they are asked for)
+#define FWD_PATCH_MIN 128  // patches (all lists, all z quads) from which forward_tiles deals patches: 64 (256^3 x 256) lose 12 %, 144 (384^3 x 384) gain 3 %
+
+// Work-groups that one list of n_list entries (padding included) takes in the grid of k_fwd_gather_flat: the (group, row tile) pairs of a z
+// quad rounded up to a multiple of the 8 XCDs, times the z quads; or the list's patches of FPG x FPR such pairs (all z quads), rounded up
+// to a multiple of 8.  The host sizes the grid with it, the kernel finds a work-group's list with it.
+__host__ __device__ static inline unsigned long long fg_list_wgs(int n_list, int nrt, int nzq, int patched)
+{
+    const unsigned long long npg = (unsigned long long)((n_list + 7) / 8);
+    if (!patched) return 8ull * ((npg * (unsigned long long)nrt + 7) / 8) * (unsigned long long)nzq;
+    const unsigned long long npq = ((npg + FPG - 1) / FPG) * (unsigned long long)((nrt + FPR - 1) / FPR);
+    return 8ull * ((npq * (unsigned long long)nzq + 7) / 8) * (unsigned long long)(FPG * FPR);
+}
 
 // The body of k_fwd_gather_flat for one list.  (A line's plane is addressed as slab base, wave-uniform 64-bit, + 32-bit byte offset: the host
 // checks that the volume is <= 4 GiB.)
 template <int NW, int WALKY>
 __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs, const int *__restrict__ perm, int n_list, unsigned block_id,
-                                                     float *__restrict__ proj, const float *__restrict__ vol, const TomoGeomC &g,
+                                                     int patched, float *__restrict__ proj, const float *__restrict__ vol, const TomoGeomC &g,
                                                      const unsigned char *__restrict__ vflags, const int *__restrict__ zshift,
                                                      float (*rows)[FGROWS * GPITCH], float4 (*wtab)[GWAVES][64], int (*ltab)[GWAVES][64], int *wlive)
 {
@@ -495,15 +512,40 @@ __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs,
     const int nS = WALKY ? g.ny : g.nx, nL = WALKY ? g.nx : g.ny;
     const uint32_t strideL4 = (WALKY ? (uint32_t)g.ny * (uint32_t)g.nz : (uint32_t)g.nz) * 4u;
     const size_t strideS = WALKY ? (size_t)g.nz : (size_t)g.ny * g.nz;
-    // Work-group -> (projection group, row tile, z quad).  Work-groups are dealt to the 8 XCDs round-robin: XCD k takes the k-th eighth of
-    // the (group, tile) pairs of one z quad after the other, row tiles fastest -- its resident work-groups walk the same slabs of the same
-    // z quad at about the same time and find each other's lines in that XCD's L2.
+    // Work-group -> (projection group, row tile, z quad).  Work-groups are dealt to the 8 XCDs round-robin, so XCD k sees the ids k, k + 8, ...
+    // of the list ("XCD patches", the scheme of k_adj_gather_flat).  patched: the work-groups that follow each other on an XCD
+    // form PATCHES of FPG consecutive projection groups x FPR consecutive row tiles of one z quad: the same few detector rows under many
+    // neighbouring angles.  Their rays cross each other inside the volume and their slab ranges nearly coincide, so part of the lines a
+    // wave asks for is still in that XCD's L2; with the plain order below the resident work-groups are one group x 96 row tiles, and
+    // only neighbouring row tiles overlap.  A patch never leaves its list; groups and row tiles are split evenly over the patches of a
+    // list, and the surplus work-groups of a patch (its FPG x FPR slots are not all used) end here.  Patch p * 8 + k of the list goes to
+    // XCD k, patches numbered z quad by z quad, row-tile patches fastest: the eight XCDs hold neighbouring patches of one z quad, and
+    // every XCD gets its share of the light patches (detector edge, dead z quads) -- the k-th eighth of the patches per XCD was 50 % slower.
+    // Plain order (small grids: the padding costs more than the reuse gains): XCD k takes the k-th eighth of the (group, tile) pairs of one
+    // z quad after the other, row tiles fastest.
     const int npg = (n_list + 7) / 8, nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
-    const int m_all = npg * nrt, m8 = (m_all + 7) / 8;
     const int slot_id = (int)(block_id >> 3), xcd = (int)(block_id & 7);
-    const int zq = slot_id / m8, tile = xcd * m8 + slot_id % m8;
-    if (tile >= m_all || zq >= nzq) return;                               // uniform over the work-group
-    const int pg = tile / nrt, rt = tile % nrt;
+    int pg, rt, zq;
+    if (patched) {
+        const int npp = (npg + FPG - 1) / FPG, nrp = (nrt + FPR - 1) / FPR, npq = npp * nrp;
+        const int within = slot_id % (FPG * FPR);
+        const int patch = (slot_id / (FPG * FPR)) * 8 + xcd;
+        zq = patch / npq;
+        const int pgp = (patch % npq) / nrp, rtp = (patch % npq) % nrp;
+        // the groups and the row tiles are split EVENLY over the patches (38 groups: 13 13 12, not 16 16 6): patches of like size
+        const int pg0 = pgp * npg / npp, pgc = (pgp + 1) * npg / npp - pg0, rt0 = rtp * nrt / nrp, rtc = (rtp + 1) * nrt / nrp - rt0;
+        if (zq >= nzq || within / FPR >= pgc || within % FPR >= rtc) return;     // uniform over the work-group, before the first barrier
+        pg = pg0 + within / FPR;
+        rt = rt0 + within % FPR;
+    } else {
+        const int m_all = npg * nrt, m8 = (m_all + 7) / 8;
+        const int tile = xcd * m8 + slot_id % m8;
+        zq = slot_id / m8;
+        if (tile >= m_all) return;                                        // uniform over the work-group
+        pg = tile / nrt;
+        rt = tile % nrt;
+    }
+    if (zq >= nzq) return;
     const int z0 = (zq * GWAVES + wv - *zshift) * 64;
     bool zlive = z0 >= 0 && z0 < g.nz;
     if (zlive) {
@@ -615,7 +657,11 @@ __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs,
     //         exactly 4 GiB, which the host admits, would lie outside it and read as zero.)
     const uint32_t slab_bytes = (uint32_t)min(WALKY ? (unsigned long long)(g.nx - 1) * strideL4 + (unsigned long long)g.nz * 4ull
                                                     : (unsigned long long)g.ny * g.nz * 4ull, 0xffffffffull);
+#ifdef TOMO_ABLATE_FWD_SLAB_LO      /* measurement builds only: every slab's lines are fetched from the wave's FIRST slab (wrong sums) -- the same */
+#define FG_SLAB_RSRC(SX) __builtin_amdgcn_make_buffer_rsrc((void *)(vol + (size_t)(s_lo) * strideS), 0, (int)slab_bytes, 0x00020000)   /* instructions, LDS traffic and loads, every line from the cache */
+#else
 #define FG_SLAB_RSRC(SX) __builtin_amdgcn_make_buffer_rsrc((void *)(vol + (size_t)(SX) * strideS), 0, (int)slab_bytes, 0x00020000)
+#endif
 #define FG_LINE_LOAD(RS, SOFF) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32((RS), o0, (SOFF), 0))
 #define FG_SETUP(SX, BUF, SLOT)                                                                                            \
     {                                                                                                                      \
@@ -757,25 +803,25 @@ __device__ __forceinline__ void fwd_gather_flat_body(const GfC *__restrict__ cs,
     }
 }
 
-// One launch per forward call: the work-groups of the four lists (x walk NW 3 | x walk NW 4 | y walk NW 3 | y walk NW 4, each 8 * m8 * nzq
+// One launch per forward call: the work-groups of the four lists (x walk NW 3 | x walk NW 4 | y walk NW 3 | y walk NW 4, each fg_list_wgs()
 // work-groups, see the body) follow each other in the grid; a work-group finds its list from its index and runs that instantiation.
 __global__ __launch_bounds__(GWAVES * 64, 3) void k_fwd_gather_flat(const GfC *__restrict__ cs, const int *__restrict__ perm, int n0, int n1, int n2, int n3,
-                                                                    float *__restrict__ proj, const float *__restrict__ vol, TomoGeomC g,
+                                                                    int patched, float *__restrict__ proj, const float *__restrict__ vol, TomoGeomC g,
                                                                     const unsigned char *__restrict__ vflags, const int *__restrict__ zshift)
 {
     __shared__ __attribute__((aligned(16))) float rows[GWAVES][FGROWS * GPITCH];
     __shared__ float4 wtab[3][GWAVES][64];          // [group mod 3][slab of the group][ray] = W0 .. W3
     __shared__ int ltab[3][GWAVES][64];             //                                      = L0
     __shared__ int wlive[GWAVES];
-    const unsigned nrt = (unsigned)(g.ndx + 7) / 8, nzq = (unsigned)(g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
-    const unsigned w0 = 8u * ((((unsigned)n0 + 7) / 8 * nrt + 7) / 8) * nzq, w1 = 8u * ((((unsigned)n1 + 7) / 8 * nrt + 7) / 8) * nzq,
-                   w2 = 8u * ((((unsigned)n2 + 7) / 8 * nrt + 7) / 8) * nzq;
+    const int nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
+    const unsigned w0 = (unsigned)fg_list_wgs(n0, nrt, nzq, patched), w1 = (unsigned)fg_list_wgs(n1, nrt, nzq, patched),
+                   w2 = (unsigned)fg_list_wgs(n2, nrt, nzq, patched);         // (the host launches only grids below 2^31)
     unsigned b = blockIdx.x;
-    if (b < w0) { fwd_gather_flat_body<3, 0>(cs, perm, n0, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    if (b < w0) { fwd_gather_flat_body<3, 0>(cs, perm, n0, b, patched, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
     b -= w0;
-    if (b < w1) { fwd_gather_flat_body<4, 0>(cs, perm + n0, n1, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    if (b < w1) { fwd_gather_flat_body<4, 0>(cs, perm + n0, n1, b, patched, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
     b -= w1;
-    if (b < w2) { fwd_gather_flat_body<3, 1>(cs, perm + n0 + n1, n2, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
+    if (b < w2) { fwd_gather_flat_body<3, 1>(cs, perm + n0 + n1, n2, b, patched, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive); return; }
     b -= w2;
-    fwd_gather_flat_body<4, 1>(cs, perm + n0 + n1 + n2, n3, b, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive);
+    fwd_gather_flat_body<4, 1>(cs, perm + n0 + n1 + n2, n3, b, patched, proj, vol, g, vflags, zshift, rows, wtab, ltab, wlive);
 }

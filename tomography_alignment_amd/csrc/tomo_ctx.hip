@@ -196,6 +196,10 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
     else if (!strcmp(key, "fused_update")) ctx->fused_update = value;
     else if (!strcmp(key, "fwd_flat_ztiles")) ctx->fwd_flat_ztiles = value;
     else if (!strcmp(key, "fwd_flat_gather")) ctx->fwd_flat_gather = value;
+    else if (!strcmp(key, "fwd_gather_patch")) {
+        if (value < 0 || value > 2) return tomo_fail(ctx, TOMO_ERR_ARG, "fwd_gather_patch: 0, 1 or 2");
+        ctx->fwd_gather_patch = value;
+    }
     else if (!strcmp(key, "reuse_staged_volume")) ctx->reuse_staged = value;
     else if (!strcmp(key, "reuse_sino_flags")) ctx->reuse_sino_flags = value;
     else if (!strcmp(key, "roctx")) {

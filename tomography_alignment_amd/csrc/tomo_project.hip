@@ -272,13 +272,19 @@ static int forward_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
         const GfC *d_gfc = plan_gfc(ctx, *plan);
         const int *d_perm = plan_fwd_lists(ctx, *plan);
         const int nrt = (g.ndx + 7) / 8, nzq = (g.nz + 64 * GWAVES - 1) / (64 * GWAVES) + 1;
-        // one launch: the four lists' work-groups follow each other in the grid (an empty list has none)
+        // one launch: the four lists' work-groups follow each other in the grid (an empty list has none), dealt in patches of FPG x FPR
+        // (group, row tile) pairs per XCD (see the kernel) when the lists hold FWD_PATCH_MIN patches or more, or option fwd_gather_patch = 2;
+        // smaller grids, and option 0, keep the plain order
         const int *fn = plan->fg_n;
-        long long n_wg = 0;
-        for (int l = 0; l < 4; ++l) n_wg += 8 * (((long long)((fn[l] + 7) / 8) * nrt + 7) / 8) * nzq;
-        if (n_wg >= ((long long)1 << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather forward: grid too large");
-        TOMO_LAUNCH(ctx, "k_fwd_tile_flat", k_fwd_gather_flat, dim3((unsigned)n_wg), dim3(GWAVES * 64), 0, d_gfc, d_perm, fn[0], fn[1], fn[2], fn[3], d_proj, d_vol, g,
-                    (const unsigned char *)d_vf, (const int *)d_shift);
+        long long n_patch = 0;
+        for (int l = 0; l < 4; ++l) n_patch += (long long)(((fn[l] + 7) / 8 + FPG - 1) / FPG) * ((nrt + FPR - 1) / FPR) * nzq;
+        const int patched = ctx->fwd_gather_patch == 2 || (ctx->fwd_gather_patch == 1 && n_patch >= FWD_PATCH_MIN) ? 1 : 0;
+        unsigned long long n_wg = 0;
+        for (int l = 0; l < 4; ++l) n_wg += fg_list_wgs(fn[l], nrt, nzq, patched);
+        if (n_wg >= (1ull << 31)) return tomo_fail(ctx, TOMO_ERR_UNSUPPORTED, "gather forward: grid too large");
+        // (a patched launch is profiled as "k_fwd_tile_flat(patched)": tomo_profile_get("k_fwd_tile_flat") counts both, the full name only these)
+        TOMO_LAUNCH(ctx, patched ? "k_fwd_tile_flat(patched)" : "k_fwd_tile_flat", k_fwd_gather_flat, dim3((unsigned)n_wg), dim3(GWAVES * 64), 0, d_gfc, d_perm, fn[0], fn[1], fn[2], fn[3], patched, d_proj,
+                    d_vol, g, (const unsigned char *)d_vf, (const int *)d_shift);
         return TOMO_OK;
     }
     if (n_flat > 0) {

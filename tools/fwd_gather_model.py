@@ -5,7 +5,8 @@ Emulates the kernel's tiling for a parallel-beam scan of an N^3 volume with N de
 8 projections x 8 detector rows x 64 planes and walks the volume one slab at a time (x slabs where |d_x| >= |d_y|, y slabs
 otherwise; projections are grouped per walk, in pose order).  Per (ray, slab) the kernel needs the lines L0 .. L0 + NW - 1
 (L0 = lowest node touched by the <= 3 samples with |p_s - S| < 1); per wave-step it stages the lines wave_min(L0) ..
-wave_max(L0) + NW - 1 in windows of FROWS.  Prints what the kernel's constants were chosen from:
+wave_max(L0) + NW - 1 in windows of FROWS.  Prints what the kernel's constants were chosen from, and, for the work-group order
+(patches of G groups x R row tiles per XCD), how many of the lines a patch requests per slab are distinct:
 
   python tools/fwd_gather_model.py [--n 1024] [--angles 1024] > profiles/fwd_gather_model.md
 """
@@ -58,7 +59,36 @@ def group_stats(poses, walk, n, frows_list, nbins):
     return lmin, lmax, live, nodes.max()
 
 
-def run(name, phis, txs, n, frows_list, out):
+def patch_reuse(lmin, lmax, live, nw, n, fpg, fpr):
+    """Lines requested and distinct lines touched per patch-slab, summed over the patches of fpg groups x fpr row tiles of one list
+    (groups and row tiles split evenly over the patches, as the kernel does).  lmin, lmax, live: [groups, row tiles, slabs] of the
+    list's waves.  A wave requests its first window's lines lmin .. lmax + nw - 1, clamped to the volume as the kernel clamps them;
+    the distinct lines of a patch-slab are the union of those intervals over the patch's waves.  Requested / distinct is the reuse
+    one XCD's L2 can give IF the work-groups of a patch walk their slabs together; nothing here says whether they do."""
+    npg, nrt, ns = lmin.shape
+    npp, nrp = (npg + fpg - 1) // fpg, (nrt + fpr - 1) // fpr
+    lo = np.clip(np.where(live, lmin, 0), 0, n)
+    hi = np.clip(np.where(live, lmax + nw, 0), 0, n)            # exclusive
+    req = dist = 0.0
+    n_ps = 0
+    for a in range(npp):
+        g0, g1 = a * npg // npp, (a + 1) * npg // npp
+        for b in range(nrp):
+            r0, r1 = b * nrt // nrp, (b + 1) * nrt // nrp
+            l = lo[g0:g1, r0:r1].reshape(-1, ns)
+            h = hi[g0:g1, r0:r1].reshape(-1, ns)
+            cover = np.zeros((n + 1, ns), dtype=np.int32)
+            cols = np.broadcast_to(np.arange(ns), l.shape)
+            np.add.at(cover, (l, cols), 1)
+            np.add.at(cover, (h, cols), -1)
+            d = (np.cumsum(cover, axis=0) > 0).sum(axis=0)
+            req += float((h - l).sum())
+            dist += float(d.sum())
+            n_ps += int((d > 0).sum())
+    return req, dist, n_ps, (-(-npg // npp), -(-nrt // nrp))       # ... and the largest patch actually formed (groups, row tiles)
+
+
+def run(name, phis, txs, n, frows_list, out, patches=()):
     A = len(phis)
     dsx = np.abs(np.sin(phis)) >= np.abs(np.cos(phis))                  # |d_x| >= |d_y|: x walk
     ratio = np.where(dsx, np.abs(np.cos(phis) / np.maximum(np.abs(np.sin(phis)), 1e-300)),
@@ -81,6 +111,7 @@ def run(name, phis, txs, n, frows_list, out):
     staged = {f: 0.0 for f in frows_list}
     w_steps = {3: 0, 4: 0}
     max_nodes = {3: 0, 4: 0}
+    per_list = {}
     for (walk, nw), sel in sorted(lists.items()):
         # groups of eight in pose order; a new group starts where the list jumps to another range of poses (as the host pads its lists)
         groups, cur = [], []
@@ -90,9 +121,12 @@ def run(name, phis, txs, n, frows_list, out):
                 cur = []
             cur.append(i)
         groups.append(cur)
+        per_list[(walk, nw)] = ([], [], [])
         for grp in groups:
             poses = [(phis[i], txs[i]) for i in grp]
             lmin, lmax, live, mx = group_stats(poses, walk, n, frows_list, nbins)
+            for store, arr in zip(per_list[(walk, nw)], (lmin, lmax, live)):
+                store.append(arr)
             max_nodes[nw] = max(max_nodes[nw], int(mx))
             lines = np.where(live, lmax - lmin + nw, 0)
             tot_steps += live.size
@@ -132,6 +166,24 @@ def run(name, phis, txs, n, frows_list, out):
         gb = staged[f] * LINE_BYTES * n_chunk / 1e9
         p(f"| {f} | {100.0 * over[f] / max(tot_live, 1):.1f} % | {staged[f] / max(tot_live, 1):.2f} | {gb:.0f} GB | {gb * 11 / 16:.0f} GB |")
     p()
+    if patches:
+        # the work-group order of the kernel (option fwd_gather_patch): which waves are resident on one XCD together
+        p("Patches of G projection groups x R row tiles that one XCD's work-groups cover together: lines requested / distinct lines touched, "
+          "per patch-slab.  In brackets: distinct lines per patch-slab; the largest patch actually formed -- groups and row tiles are split "
+          "evenly over ceil(groups / G) x ceil(row tiles / R) patches, as the kernel does, so G x R is an upper limit "
+          "(the plain order's resident set, one group x 96 consecutive row tiles, is evaluated as the 1 x 96 row's 1 x 64 at 128 row tiles):")
+        p()
+        keys = sorted(per_list)
+        p("| patch G x R | " + " | ".join("%s walk, NW %d" % ("xy"[w], nw) for w, nw in keys) + " |")
+        p("|---|" + "---|" * len(keys))
+        for fpg, fpr in patches:
+            cells = []
+            for k in keys:
+                lmin, lmax, live = (np.stack(a) for a in per_list[k])
+                req, dist, n_ps, eff = patch_reuse(lmin, lmax, live, k[1], n, fpg, fpr)
+                cells.append("%.2f (%.0f; %d x %d)" % (req / max(dist, 1.0), dist / max(n_ps, 1), eff[0], eff[1]))
+            p("| %d x %d | " % (fpg, fpr) + " | ".join(cells) + " |")
+        p()
     return sum_lines / max(tot_live, 1)
 
 
@@ -140,7 +192,10 @@ def main():
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--angles", type=int, default=1024)
     ap.add_argument("--frows", type=int, nargs="*", default=[16, 20, 24, 28, 32])
+    ap.add_argument("--patches", nargs="*", default=["1x96", "2x48", "4x24", "8x12", "12x8", "16x6", "24x4", "16x4", "32x3", "48x2"],
+                    help="patch shapes GxR (projection groups x row tiles) of the work-group order table")
     args = ap.parse_args()
+    patches = [tuple(int(v) for v in s.split("x")) for s in args.patches]
     import sys
     out = sys.stdout
     print("# Cost model of the gather-form flat forward (tools/fwd_gather_model.py)", file=out)
@@ -149,12 +204,12 @@ def main():
           "live z chunks (960 GB with all chunks live), 506 GB by FETCH_SIZE.", file=out)
     print(file=out)
     phis = np.linspace(0.0, np.pi, args.angles)
-    run("headline poses", phis, np.zeros(args.angles), args.n, args.frows, out)
+    run("headline poses", phis, np.zeros(args.angles), args.n, args.frows, out, patches)
     rng = np.random.default_rng(0)                              # bench.py --perturbed draws alpha, beta, then tx from this generator
     rng.uniform(-1, 1, args.angles)
     rng.uniform(-1, 1, args.angles)
     tx = rng.uniform(-2, 2, args.angles)
-    run("perturbed translations (the tx of bench.py --perturbed, default_rng(0); alpha = beta = 0)", phis, tx, args.n, args.frows, out)
+    run("perturbed translations (the tx of bench.py --perturbed, default_rng(0); alpha = beta = 0)", phis, tx, args.n, args.frows, out, patches)
 
 
 if __name__ == "__main__":
