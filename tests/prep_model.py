@@ -14,10 +14,12 @@ def reference_mean(frames):
 
 
 def reference_median(frames):
-    """Exact per-pixel median; for even n float32(0.5 * (double(a) + double(b))) of the two middle values."""
+    """Exact per-pixel median; for even n float32(0.5 * (double(a) + double(b))) of the two middle values.  As in the kernel's key, -0 is
+    read as +0 (the median of zeros is +0 whichever zero the sort leaves in the middle) and every NaN sorts above +inf."""
     f = np.asarray(frames)
     f = f[None] if f.ndim == 2 else f
-    s = np.sort(f.astype(np.float32), axis=0)
+    f = f.astype(np.float32)
+    s = np.sort(np.where(f == 0, np.float32(0), f), axis=0)
     n = s.shape[0]
     a, b = s[(n - 1) // 2], s[n // 2]
     if n % 2:

@@ -1,6 +1,7 @@
 """preprocess.py on the GPU (libtomo_prep.so) against the numpy models of tests/prep_model.py: reference frames and the normalisation bit
 for bit (the log within 2e-6 relative), the stripe removal under np.array_equal over tie-heavy and signed-zero data, in place, chunked,
-the 8192-angle limit, device residency with no leaked buffers, and generate_data --raw -> examples/preprocess -> FBP -> align_rigid."""
+the 8192-angle limit, device residency with no leaked buffers, and generate_data --raw -> examples/preprocess -> FBP -> align_rigid.
+Every path the host can choose for these kernels (frame groups, tiles, median windows, group widths, chunks): test_gpu_prep_paths.py."""
 import numpy as np
 import pytest
 
