@@ -214,6 +214,7 @@ struct tomo_cor {
     Buf pairs;                   // double t[npairs], then int slice[npairs]
     Buf tab;                     // int hi[R]
     Buf part, dm;                // double partial[batch][nblk], double m[npairs]
+    auto bufs() { return std::array{&work, &S, &coef, &rows, &spec, &pairs, &tab, &part, &dm}; }
     std::vector<int> host_rows, host_tab;
     std::vector<unsigned char> host_pairs;
     PassTimer<TOMO_COR_METRIC_MS_N> timer;       // of a load's passes as well
@@ -297,15 +298,12 @@ extern "C" {
 TOMO_API int tomo_cor_abi_version(void) { return 1; }
 
 TOMO_API int tomo_cor_create(int device, tomo_cor **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_COR_ERR_HIP, "hipSetDevice failed");
-    tomo_cor *h = new tomo_cor();
-    h->device = device;
-    if (!h->timer.create()) {
-        delete h;
+    CHK(create_plain(device, true, out));
+    if (!(*out)->timer.create()) {
+        delete *out;
+        *out = nullptr;
         return fail(nullptr, TOMO_COR_ERR_HIP, "hipEventCreate failed");
     }
-    *out = h;
     return TOMO_COR_OK;
 }
 
@@ -313,8 +311,7 @@ TOMO_API int tomo_cor_destroy(tomo_cor *h) {
     if (!h) return TOMO_COR_OK;
     (void)hipSetDevice(h->device);
     h->plans.destroy_all();
-    for (Buf *b : {&h->work, &h->S, &h->coef, &h->rows, &h->spec, &h->pairs, &h->tab, &h->part, &h->dm})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     h->timer.destroy();
     delete h;
     return TOMO_COR_OK;
@@ -342,7 +339,7 @@ TOMO_API int tomo_cor_batch(int npairs, int n, int nx, size_t max_scratch_bytes,
 
 TOMO_API int tomo_cor_device_bytes(tomo_cor *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_COR_ERR_ARG, "tomo_cor_device_bytes: NULL");
-    *bytes = (int64_t)(h->work.n + h->S.n + h->coef.n + h->rows.n + h->spec.n + h->pairs.n + h->tab.n + h->part.n + h->dm.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_COR_OK;
 }
 

@@ -334,6 +334,7 @@ struct tomo_dff {
     Buf gpart, G, V;                 // double [groups][pairs], double [K][K], double [K][m]
     Buf par, cpart, cres;            // uint32 [nids][2 + m], double [nids][tiles][1 + m], double [nids][1 + m]
     Buf wts;                         // float [n][m] of tomo_dff_apply
+    auto bufs() { return std::array{&rb, &gpart, &G, &V, &par, &cpart, &cres, &wts}; }
     std::vector<uint32_t> hpar;      // what par is uploaded from: alive until the copy has been made
     std::vector<double> hV;
     std::vector<float> hw;
@@ -413,19 +414,13 @@ extern "C" {
 TOMO_API int tomo_dff_abi_version(void) { return 1; }
 
 TOMO_API int tomo_dff_create(int device, tomo_dff **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_DFF_ERR_HIP, "hipSetDevice failed");
-    tomo_dff *h = new tomo_dff();
-    h->device = device;
-    *out = h;
-    return TOMO_DFF_OK;
+    return create_plain(device, true, out);
 }
 
 TOMO_API int tomo_dff_destroy(tomo_dff *h) {
     if (!h) return TOMO_DFF_OK;
     (void)hipSetDevice(h->device);
-    for (Buf *b : {&h->rb, &h->gpart, &h->G, &h->V, &h->par, &h->cpart, &h->cres, &h->wts})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_DFF_OK;
 }
@@ -471,7 +466,7 @@ TOMO_API int tomo_dff_set_max_scratch(tomo_dff *h, size_t max_scratch_bytes) {
 
 TOMO_API int tomo_dff_device_bytes(tomo_dff *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_DFF_ERR_ARG, "tomo_dff_device_bytes: NULL");
-    *bytes = (int64_t)(h->rb.n + h->gpart.n + h->G.n + h->V.n + h->par.n + h->cpart.n + h->cres.n + h->wts.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_DFF_OK;
 }
 

@@ -28,6 +28,7 @@ constexpr int SIDE_ERR_ARG = TOMO_FSC_ERR_ARG, SIDE_ERR_HIP = TOMO_FSC_ERR_HIP, 
 }
 #include "../tomo_side_host.h"
 #include "../tomo_side_fft.h"
+#include "../tomo_side_reduce.h"
 
 namespace {
 
@@ -35,7 +36,6 @@ constexpr int TPB = 256;             // threads per block of the streaming kerne
 constexpr int SUM_G = 256;           // blocks per plane of the first-stage sums (== TPB: the second stage is one partial per thread)
 constexpr int WAVE = 64;             // k_shell: one wave per work-group
 constexpr int SHELL_WGS = 2048;      // k_shell: at most this many work-groups (partial tables); a constant, so the sums do not depend on the device
-constexpr double PI = 3.141592653589793238462643383279502884;
 
 struct Shape {
     int ndim, nb, nx, ny, nz;        // ny == 1 for ndim 2
@@ -49,24 +49,6 @@ struct Shape {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------- kernels
-
-// Block tree reduction of a sum in LDS, fixed order; every thread gets the total.
-__device__ inline double block_sum(double v, double *sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = TPB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-struct Mask {
-    int mode;                        // tomo_fsc_mask
-    const float *arr;
-    double R, E;
-};
 
 // The mask at voxel (ix, iy, iz) of a plane (linear index i within the plane), float64.
 template <int DIM>
@@ -83,11 +65,7 @@ __device__ inline double mask_at(const Mask &m, const Shape &g, long long i) {
         dx = (double)row - 0.5 * (g.nx - 1);
     }
     const double dz = (double)iz - 0.5 * (g.nz - 1);
-    const double d2 = dx * dx + dy * dy + dz * dz;
-    if (d2 <= m.R * m.R) return 1.0;
-    const double Ro = m.R + m.E;
-    if (d2 >= Ro * Ro || m.E <= 0.0) return 0.0;
-    return 0.5 * (1.0 + cos(PI * (sqrt(d2) - m.R) / m.E));
+    return mask_edge(dx * dx + dy * dy + dz * dz, m.R, m.E);
 }
 
 // part[(b * SUM_G + blk) * 2 + {0, 1}] = this block's share of sum(m v), sum(m) over plane b.
@@ -104,8 +82,8 @@ __global__ __launch_bounds__(TPB) void k_mask_sums(const float *__restrict__ v, 
         smv += w * (double)v[b * N + i];
         sm += w;
     }
-    const double t0 = block_sum(smv, sh);
-    const double t1 = block_sum(sm, sh);
+    const double t0 = block_sum<TPB>(smv, sh);
+    const double t1 = block_sum<TPB>(sm, sh);
     if (threadIdx.x == 0) {
         part[(b * SUM_G + blockIdx.x) * 2] = t0;
         part[(b * SUM_G + blockIdx.x) * 2 + 1] = t1;
@@ -121,8 +99,8 @@ __global__ __launch_bounds__(TPB) void k_prepare(const float *__restrict__ v, Sh
     const long long b = blockIdx.y;
     double mean = 0.0;
     if (part) {
-        const double smv = block_sum(part[(b * SUM_G + threadIdx.x) * 2], sh);
-        const double sm = block_sum(part[(b * SUM_G + threadIdx.x) * 2 + 1], sh);
+        const double smv = block_sum<TPB>(part[(b * SUM_G + threadIdx.x) * 2], sh);
+        const double sm = block_sum<TPB>(part[(b * SUM_G + threadIdx.x) * 2 + 1], sh);
         mean = sm != 0.0 ? smv / sm : 0.0;
     }
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -264,6 +242,7 @@ struct tomo_fsc {
     FftPlan *plan = nullptr;
     std::vector<void *> areas;       // the plans' work areas, set when a plan is made; a plan's size is its work_bytes
     Buf spec[2], sums, part, table;
+    auto bufs() { return std::array{&spec[0], &spec[1], &sums, &part, &table}; }
 };
 
 namespace {
@@ -337,11 +316,7 @@ extern "C" {
 TOMO_API int tomo_fsc_abi_version(void) { return 1; }
 
 TOMO_API int tomo_fsc_create(int device, tomo_fsc **out) {
-    CHK(check_create(device, out));
-    tomo_fsc *h = new tomo_fsc();
-    h->device = device;
-    *out = h;
-    return TOMO_FSC_OK;
+    return create_plain(device, false, out);
 }
 
 TOMO_API int tomo_fsc_destroy(tomo_fsc *h) {
@@ -349,8 +324,7 @@ TOMO_API int tomo_fsc_destroy(tomo_fsc *h) {
     (void)hipSetDevice(h->device);
     h->plans.destroy_all();
     for (void *w : h->areas) (void)hipFree(w);
-    for (Buf *b : {&h->spec[0], &h->spec[1], &h->sums, &h->part, &h->table})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_FSC_OK;
 }
@@ -384,7 +358,7 @@ TOMO_API int tomo_fsc_set_shape(tomo_fsc *h, int ndim, int nb, int nx, int ny, i
 
 TOMO_API int tomo_fsc_device_bytes(tomo_fsc *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_FSC_ERR_ARG, "tomo_fsc_device_bytes: NULL");
-    size_t t = h->spec[0].n + h->spec[1].n + h->sums.n + h->part.n + h->table.n;
+    size_t t = buf_bytes(h->bufs());
     for (auto &kv : h->plans.plans) t += kv.second.work_bytes;
     *bytes = (int64_t)t;
     return TOMO_FSC_OK;

@@ -209,6 +209,7 @@ struct tomo_half {
     int w = 0;                           // of the last tomo_half_search; 0 before it
     Buf S, rows, cs, cs2, part, m;       // float [nr][n][nx], int [nr], double [nr][2][nx] twice, double [batch][2][njt][np], double [nr][2][np]
     Buf table;                           // tomo_half_column [W]
+    auto bufs() { return std::array{&S, &rows, &cs, &cs2, &part, &m, &table}; }
     std::vector<int> host_rows;          // what the asynchronous copies read
     std::vector<tomo_half_column> host_table;
     bool staging_in_flight = false;
@@ -312,19 +313,13 @@ extern "C" {
 TOMO_API int tomo_half_abi_version(void) { return 1; }
 
 TOMO_API int tomo_half_create(int device, tomo_half **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_HALF_ERR_HIP, "hipSetDevice failed");
-    tomo_half *h = new tomo_half();
-    h->device = device;
-    *out = h;
-    return TOMO_HALF_OK;
+    return create_plain(device, true, out);
 }
 
 TOMO_API int tomo_half_destroy(tomo_half *h) {
     if (!h) return TOMO_HALF_OK;
     (void)hipSetDevice(h->device);
-    for (Buf *b : {&h->S, &h->rows, &h->cs, &h->cs2, &h->part, &h->m, &h->table})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_HALF_OK;
 }
@@ -377,7 +372,7 @@ TOMO_API int tomo_half_set_max_scratch(tomo_half *h, size_t max_scratch_bytes) {
 
 TOMO_API int tomo_half_device_bytes(tomo_half *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_HALF_ERR_ARG, "tomo_half_device_bytes: NULL");
-    *bytes = (int64_t)(h->S.n + h->rows.n + h->cs.n + h->cs2.n + h->part.n + h->m.n + h->table.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_HALF_OK;
 }
 

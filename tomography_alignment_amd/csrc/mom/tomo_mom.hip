@@ -160,6 +160,7 @@ struct tomo_mom {
     int n = 0, nx = 0, nz = 0;       // of the last tomo_mom_marginals; n = 0 before it
     Buf zpart, qpart, badpart;       // double [batch][ntile * ng][nz], double [batch][nchunk][nx], int [batch][ntile][nchunk]
     Buf Q, Z, bad;                   // double [n][nx], double [n][nz], int [n]
+    auto bufs() { return std::array{&zpart, &qpart, &badpart, &Q, &Z, &bad}; }
 };
 
 namespace {
@@ -198,19 +199,13 @@ extern "C" {
 TOMO_API int tomo_mom_abi_version(void) { return 1; }
 
 TOMO_API int tomo_mom_create(int device, tomo_mom **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_MOM_ERR_HIP, "hipSetDevice failed");
-    tomo_mom *h = new tomo_mom();
-    h->device = device;
-    *out = h;
-    return TOMO_MOM_OK;
+    return create_plain(device, true, out);
 }
 
 TOMO_API int tomo_mom_destroy(tomo_mom *h) {
     if (!h) return TOMO_MOM_OK;
     (void)hipSetDevice(h->device);
-    for (Buf *b : {&h->zpart, &h->qpart, &h->badpart, &h->Q, &h->Z, &h->bad})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_MOM_OK;
 }
@@ -241,7 +236,7 @@ TOMO_API int tomo_mom_set_max_scratch(tomo_mom *h, size_t max_scratch_bytes) {
 
 TOMO_API int tomo_mom_device_bytes(tomo_mom *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_MOM_ERR_ARG, "tomo_mom_device_bytes: NULL");
-    *bytes = (int64_t)(h->zpart.n + h->qpart.n + h->badpart.n + h->Q.n + h->Z.n + h->bad.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_MOM_OK;
 }
 

@@ -142,6 +142,7 @@ struct tomo_phase {
     FftPlans<std::tuple<int, int, int>> plans;   // R2C + C2R per (px, pz, batch)
     Buf work;                    // the hipFFT work area all plans share
     Buf tables;                  // double tx[px], tz[pzh]
+    auto bufs() { return std::array{&work, &tables}; }
     std::vector<double> host_tables;
     PassTimer<TOMO_PHASE_MS_N> timer;
 };
@@ -254,15 +255,12 @@ extern "C" {
 TOMO_API int tomo_phase_abi_version(void) { return 1; }
 
 TOMO_API int tomo_phase_create(int device, tomo_phase **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipSetDevice failed");
-    tomo_phase *h = new tomo_phase();
-    h->device = device;
-    if (!h->timer.create()) {
-        delete h;
+    CHK(create_plain(device, true, out));
+    if (!(*out)->timer.create()) {
+        delete *out;
+        *out = nullptr;
         return fail(nullptr, TOMO_PHASE_ERR_HIP, "hipEventCreate failed");
     }
-    *out = h;
     return TOMO_PHASE_OK;
 }
 
@@ -270,8 +268,7 @@ TOMO_API int tomo_phase_destroy(tomo_phase *h) {
     if (!h) return TOMO_PHASE_OK;
     (void)hipSetDevice(h->device);
     h->plans.destroy_all();
-    if (h->work.p) (void)hipFree(h->work.p);
-    if (h->tables.p) (void)hipFree(h->tables.p);
+    free_bufs(h->bufs());
     h->timer.destroy();
     delete h;
     return TOMO_PHASE_OK;
@@ -294,7 +291,7 @@ TOMO_API int tomo_phase_batch(int n, int px, int pz, size_t max_scratch_bytes, i
 
 TOMO_API int tomo_phase_device_bytes(tomo_phase *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_PHASE_ERR_ARG, "tomo_phase_device_bytes: NULL");
-    *bytes = (int64_t)(h->work.n + h->tables.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_PHASE_OK;
 }
 

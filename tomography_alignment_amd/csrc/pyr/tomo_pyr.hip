@@ -133,7 +133,6 @@ struct tomo_pyr {
 
 namespace {
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 bool overlap(const float *a, size_t na, const float *b, size_t nb) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
@@ -175,11 +174,7 @@ extern "C" {
 TOMO_API int tomo_pyr_abi_version(void) { return 1; }
 
 TOMO_API int tomo_pyr_create(int device, tomo_pyr **out) {
-    CHK(check_create(device, out));
-    tomo_pyr *h = new tomo_pyr();
-    h->device = device;
-    *out = h;
-    return TOMO_PYR_OK;
+    return create_plain(device, false, out);
 }
 
 TOMO_API int tomo_pyr_destroy(tomo_pyr *h) {
@@ -196,7 +191,7 @@ TOMO_API int tomo_pyr_bin_sino(tomo_pyr *h, void *stream, const float *d_src, in
     if (int rc = check_factor(h, "tomo_pyr_bin_sino", f, ext, 2)) return rc;
     if (n == 0) return TOMO_PYR_OK;
     if (!d_src || !d_dst) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_sino: NULL pointer");
-    if (!aligned16(d_src) || !aligned16(d_dst)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_sino: buffers must be 16-byte aligned");
+    if (!aligned(d_src, 16) || !aligned(d_dst, 16)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_sino: buffers must be 16-byte aligned");
     const size_t n_in = (size_t)n * nx * nz, n_out = n_in / ((size_t)f * f);
     if (overlap(d_src, n_in, d_dst, n_out)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_sino: source and destination overlap");
     HIPCHK(h, hipSetDevice(h->device));
@@ -210,7 +205,7 @@ TOMO_API int tomo_pyr_bin_vol(tomo_pyr *h, void *stream, const float *d_src, int
     const int ext[3] = {nx, ny, nz};
     if (int rc = check_factor(h, "tomo_pyr_bin_vol", f, ext, 3)) return rc;
     if (!d_src || !d_dst) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_vol: NULL pointer");
-    if (!aligned16(d_src) || !aligned16(d_dst)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_vol: buffers must be 16-byte aligned");
+    if (!aligned(d_src, 16) || !aligned(d_dst, 16)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_vol: buffers must be 16-byte aligned");
     const size_t n_in = (size_t)nx * ny * nz, n_out = n_in / ((size_t)f * f * f);
     if (overlap(d_src, n_in, d_dst, n_out)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_bin_vol: source and destination overlap");
     HIPCHK(h, hipSetDevice(h->device));
@@ -223,7 +218,7 @@ TOMO_API int tomo_pyr_prolong_vol(tomo_pyr *h, void *stream, const float *d_src,
     if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 29) || ny > (1 << 29) || nz > (1 << 29))
         return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_prolong_vol: bad shape");
     if (!d_src || !d_dst) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_prolong_vol: NULL pointer");
-    if (!aligned16(d_src) || !aligned16(d_dst)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_prolong_vol: buffers must be 16-byte aligned");
+    if (!aligned(d_src, 16) || !aligned(d_dst, 16)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_prolong_vol: buffers must be 16-byte aligned");
     const size_t n_in = (size_t)nx * ny * nz;
     if (overlap(d_src, n_in, d_dst, 8 * n_in)) return fail(h, TOMO_PYR_ERR_ARG, "tomo_pyr_prolong_vol: source and destination overlap");
     const long long tiles_x = (nx + PRO_CX - 1) / PRO_CX, tiles_y = (ny + PRO_CY - 1) / PRO_CY, tiles_z = (nz + PRO_CZ - 1) / PRO_CZ;

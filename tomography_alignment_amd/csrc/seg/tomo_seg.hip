@@ -1,10 +1,8 @@
 // libtomo_seg.so: threshold, 3-D connected-component labels, per-component measures, small-component removal and the largest component
 // of a device volume [nx][ny][nz] (z fastest) on gfx950 (include/tomo_seg.h, tomography_alignment_amd/segment.py).
 //
-// The elementwise kernels share libtomo_vol's decomposition: a row (x, y) is cut into G = ceil(nz / 4) groups of four consecutive z, a
-// lane owns one group at a time (one 16-byte access of float32 / int32, one 4-byte access of four mask bytes where nz % 4 == 0 and the
-// pointer is aligned to that; guarded single accesses of the same elements otherwise) and a work-group of 256 lanes owns SPAN
-// consecutive groups, i.e. a stretch of the volume in linear-index order.
+// The elementwise kernels share the decomposition of csrc/tomo_side_zgroups.h: groups of four z (one 16-byte access of float32 /
+// int32, one 4-byte access of four mask bytes), SPAN of them a work-group, i.e. a stretch of the volume in linear-index order.
 //
 // Labelling is union-find on the label array L itself (int32).  Invariant: the parent L[i] of a foreground voxel i is a foreground
 // index <= i of the same component; the background holds SENT = 2^31 - 1, which is no index (a volume has at most 2^31 - 1 voxels).
@@ -50,6 +48,7 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_SEG_ERR_ARG, SIDE_ERR_HIP = TOMO_SEG_ERR_HIP, SIDE_ERR_NODEV = TOMO_SEG_ERR_NODEV;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_zgroups.h"
 
 namespace {
 
@@ -63,13 +62,6 @@ constexpr long long TILE_MAX_GRID = 1 << 20;
 constexpr int AGG_ROUNDS = 3;                      // labels a wave of k_measure / k_count combines across its lanes per step
 constexpr int AGG_MIN_LANES = 4;                   // ... when at least this many lanes hold the label
 static_assert(SPAN % TPB == 0 && BX == 8 && BY == 8 && BZ == 64 && TPB == 256, "the brick maps assume 8 x 8 x 64 and 256 lanes");
-
-struct Vol {
-    int nx, ny, nz;
-    unsigned G;              // groups of four z of a row
-    long long R4;            // < 0: no region
-    long long groups;        // nx ny G
-};
 
 struct Tab {                 // the tables of one pass of measure, entry = label - 1 - l0
     unsigned long long *count;
@@ -89,83 +81,6 @@ struct Acc {                 // what some voxels of one label add to the tables
 };
 
 // ---------------------------------------------------------------------------------------------------------------------- device helpers
-
-__device__ inline bool inside(const Vol &g, unsigned row) {
-    if (g.R4 < 0) return true;
-    const unsigned x = row / (unsigned)g.ny, y = row - x * (unsigned)g.ny;
-    const long long a = 2LL * x - g.nx + 1, b = 2LL * y - g.ny + 1;
-    return a * a + b * b <= g.R4;
-}
-
-template <bool VEC>
-__device__ inline void load4(const float *__restrict__ row, int nz, unsigned zq, float f[4], bool in[4]) {
-    const int z = 4 * (int)zq;
-    if (VEC) {
-        const float4 t = *reinterpret_cast<const float4 *>(row + z);
-        f[0] = t.x, f[1] = t.y, f[2] = t.z, f[3] = t.w;
-        in[0] = in[1] = in[2] = in[3] = true;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            in[k] = z + k < nz;
-            f[k] = in[k] ? row[z + k] : 0.f;
-        }
-    }
-}
-
-template <bool VEC>
-__device__ inline void load4i(const int *row, int nz, unsigned zq, int v[4], bool in[4]) {
-    const int z = 4 * (int)zq;
-    if (VEC) {
-        const int4 t = *reinterpret_cast<const int4 *>(row + z);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-        in[0] = in[1] = in[2] = in[3] = true;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            in[k] = z + k < nz;
-            v[k] = in[k] ? row[z + k] : 0;
-        }
-    }
-}
-
-template <bool VEC>
-__device__ inline void store4i(int *row, int nz, unsigned zq, const int v[4]) {
-    const int z = 4 * (int)zq;
-    if (VEC) {
-        *reinterpret_cast<int4 *>(row + z) = make_int4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (z + k < nz) row[z + k] = v[k];
-    }
-}
-
-template <bool PACK>
-__device__ inline void store4b(uint8_t *row, int nz, unsigned zq, const unsigned c[4]) {
-    const int z = 4 * (int)zq;
-    if (PACK) {
-        *reinterpret_cast<unsigned *>(row + z) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (z + k < nz) row[z + k] = (uint8_t)c[k];
-    }
-}
-
-struct Walk {
-    long long row0;          // the row of the work-group's first group
-    unsigned zb;             // that group's index in its row
-    long long left;          // groups from g0 to the end of the volume
-};
-
-__device__ inline Walk walk_of(const Vol &g, long long g0) {
-    Walk w;
-    w.row0 = g0 / g.G;
-    w.zb = (unsigned)(g0 - w.row0 * g.G);
-    w.left = g.groups - g0;
-    return w;
-}
 
 // Parents are read with relaxed atomic loads: the compiler may not keep one in a register, and every value ever stored is an ancestor.
 __device__ inline int ld_global(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -215,8 +130,7 @@ __global__ __launch_bounds__(TPB) void k_threshold(const float *__restrict__ v, 
 #pragma unroll 4
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         unsigned c[4] = {0u, 0u, 0u, 0u};
         if (inside(g, (unsigned)row)) {
             float f[4];
@@ -336,8 +250,7 @@ __global__ __launch_bounds__(TPB) void k_border(int *L, Vol g) {
     const Walk w = walk_of(g, (long long)blockIdx.x * SPAN);
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         const int x = (int)(row / g.ny), y = (int)(row - (long long)x * g.ny);
         const int lx = x & (BX - 1), ly = y & (BY - 1), lq = (int)(zq & 15u);
         const bool rowc = lx == 0 || ly == 0 || (CONN > 1 && ly == BY - 1);
@@ -382,8 +295,7 @@ __global__ __launch_bounds__(TPB) void k_compress(int *L, Vol g, int *__restrict
     int roots = 0;
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         int v[4];
         bool in[4];
         load4i<VEC>(L + row * g.nz, g.nz, zq, v, in);
@@ -463,8 +375,7 @@ __global__ __launch_bounds__(TPB) void k_rank(int *L, Vol g, const int *__restri
         long long i0 = 0;
         int c = 0;
         if (live) {
-            const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-            const long long row = w.row0 + dr;
+            const auto [row, zq] = step_of(g, w, off);
             int v[4];
             bool in[4];
             load4i<VEC>(L + row * g.nz, g.nz, zq, v, in);
@@ -503,8 +414,7 @@ __global__ __launch_bounds__(TPB) void k_final(int *L, Vol g) {
     const Walk w = walk_of(g, (long long)blockIdx.x * SPAN);
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         int v[4], out[4];
         bool in[4];
         load4i<VEC>(L + row * g.nz, g.nz, zq, v, in);
@@ -562,8 +472,6 @@ __device__ inline void commit(const Tab &t, const Acc &a, int l0) {
     }
 }
 
-__device__ inline bool finite32(float v) { return fabsf(v) <= FLT_MAX; }
-
 // Labels in (l0, l1] are measured.
 template <bool VEC, bool WITHVOL>
 __global__ __launch_bounds__(TPB) void k_measure(const int *__restrict__ L, const float *__restrict__ vol, Vol g, int l0, int l1, Tab t) {
@@ -575,8 +483,7 @@ __global__ __launch_bounds__(TPB) void k_measure(const int *__restrict__ L, cons
         float f[4] = {0.f, 0.f, 0.f, 0.f};
         int x = 0, y = 0, z = 0;
         if (live) {
-            const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-            const long long row = w.row0 + dr;
+            const auto [row, zq] = step_of(g, w, off);
             bool in[4];
             load4i<VEC>(L + row * g.nz, g.nz, zq, lab, in);
             if (WITHVOL) load4<VEC>(vol + row * g.nz, g.nz, zq, f, in);
@@ -651,8 +558,7 @@ __global__ __launch_bounds__(TPB) void k_count(const int *__restrict__ L, Vol g,
         const bool live = (long long)off < w.left;
         int lab[4] = {0, 0, 0, 0};
         if (live) {
-            const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-            const long long row = w.row0 + dr;
+            const auto [row, zq] = step_of(g, w, off);
             bool in[4];
             load4i<VEC>(L + row * g.nz, g.nz, zq, lab, in);
 #pragma unroll
@@ -711,8 +617,7 @@ __global__ __launch_bounds__(TPB) void k_pick(const int *__restrict__ L, Vol g, 
     const int want = res[0];
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         int v[4];
         bool in[4];
         load4i<VEC>(L + row * g.nz, g.nz, zq, v, in);
@@ -729,8 +634,7 @@ __global__ __launch_bounds__(TPB) void k_relabel(const int *L, Vol g, int n, con
     const Walk w = walk_of(g, (long long)blockIdx.x * SPAN);
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         int v[4], o[4];
         bool in[4];
         load4i<VEC>(L + row * g.nz, g.nz, zq, v, in);
@@ -753,6 +657,7 @@ struct tomo_seg {
     Buf tab;                 // measure's tables of one pass; the sizes of remove_small and largest
     Buf res;                 // two int: what k_scan and k_argmax hand back
     size_t max_scratch = 0;  // 0: TOMO_SEG_DEFAULT_SCRATCH
+    auto bufs() { return std::array{&cnt, &tab, &res}; }
 };
 
 namespace {
@@ -765,22 +670,9 @@ int check_shape(tomo_seg *h, long long nx, long long ny, long long nz) {
                                                      std::to_string(TOMO_SEG_MAX_DIM) + ", 1 <= nz; nothing was launched");
     if (nx * ny * nz > (long long)TOMO_SEG_MAX_VOXELS)                   // at most 2^28 * (2^31 - 1): no overflow
         return fail(h, TOMO_SEG_ERR_UNSUPPORTED, "tomo_seg: a volume of " + dims(nx, ny, nz) + " has more than 2^31 - 1 voxels; nothing was launched");
+    // groups <= nx ny nz < 2^31, so there are fewer than 2^21 + 1 work-groups of SPAN groups (span_blocks): one grid.
     return TOMO_SEG_OK;
 }
-
-Vol vol_of(int nx, int ny, int nz, long long R4) {
-    Vol g;
-    g.nx = nx, g.ny = ny, g.nz = nz;
-    g.G = (unsigned)(((long long)nz + 3) / 4);
-    g.R4 = R4 < 0 ? -1 : R4;
-    g.groups = (long long)nx * ny * g.G;
-    return g;
-}
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// groups <= nx ny nz < 2^31, so there are fewer than 2^21 + 1 work-groups of SPAN groups: one grid.
-inline unsigned span_blocks(const Vol &g) { return (unsigned)((g.groups + SPAN - 1) / SPAN); }
 
 int check_call(tomo_seg *h, const char *what, const void *p, uintptr_t align, const void *q, uintptr_t qalign, int nx, int ny, int nz) {
     if (!h) return fail(h, TOMO_SEG_ERR_ARG, std::string(what) + ": NULL handle");
@@ -791,7 +683,7 @@ int check_call(tomo_seg *h, const char *what, const void *p, uintptr_t align, co
 
 // Scratch above TOMO_SEG_KEEP_BYTES goes back before a call returns (the call has waited for the stream by then).
 void release(tomo_seg *h) {
-    for (Buf *b : {&h->cnt, &h->tab, &h->res})
+    for (Buf *b : h->bufs())
         if (b->p && b->n > (size_t)TOMO_SEG_KEEP_BYTES) {
             (void)hipFree(b->p);
             b->p = nullptr, b->n = 0;
@@ -830,9 +722,9 @@ int count_sizes(tomo_seg *h, hipStream_t st, const int32_t *d_labels, const Vol 
     CHK(grow(h, h->tab, sizeof(unsigned) * (size_t)std::max(n, 1)));
     HIPCHK(h, hipMemsetAsync(h->tab.p, 0, sizeof(unsigned) * (size_t)std::max(n, 1), st));
     if (g.nz % 4 == 0 && aligned(d_labels, 16))
-        hipLaunchKernelGGL(k_count<true>, dim3(span_blocks(g)), dim3(TPB), 0, st, d_labels, g, n, (unsigned *)h->tab.p);
+        hipLaunchKernelGGL(k_count<true>, dim3(span_blocks(g, SPAN)), dim3(TPB), 0, st, d_labels, g, n, (unsigned *)h->tab.p);
     else
-        hipLaunchKernelGGL(k_count<false>, dim3(span_blocks(g)), dim3(TPB), 0, st, d_labels, g, n, (unsigned *)h->tab.p);
+        hipLaunchKernelGGL(k_count<false>, dim3(span_blocks(g, SPAN)), dim3(TPB), 0, st, d_labels, g, n, (unsigned *)h->tab.p);
     HIPCHK(h, hipGetLastError());
     return TOMO_SEG_OK;
 }
@@ -844,19 +736,13 @@ extern "C" {
 TOMO_API int tomo_seg_abi_version(void) { return 1; }
 
 TOMO_API int tomo_seg_create(int device, tomo_seg **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_SEG_ERR_HIP, "hipSetDevice failed");
-    tomo_seg *h = new tomo_seg();
-    h->device = device;
-    *out = h;
-    return TOMO_SEG_OK;
+    return create_plain(device, true, out);
 }
 
 TOMO_API int tomo_seg_destroy(tomo_seg *h) {
     if (!h) return TOMO_SEG_OK;
     (void)hipSetDevice(h->device);
-    for (Buf *b : {&h->cnt, &h->tab, &h->res})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_SEG_OK;
 }
@@ -865,7 +751,7 @@ TOMO_API const char *tomo_seg_last_error(tomo_seg *h) { return last_error(h); }
 
 TOMO_API int tomo_seg_device_bytes(tomo_seg *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_SEG_ERR_ARG, "tomo_seg_device_bytes: NULL");
-    *bytes = (int64_t)(h->cnt.n + h->tab.n + h->res.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_SEG_OK;
 }
 
@@ -894,7 +780,7 @@ TOMO_API int tomo_seg_threshold(tomo_seg *h, void *stream, const float *d_v, int
     HIPCHK(h, hipSetDevice(h->device));
     const Vol g = vol_of(nx, ny, nz, R4);
     const bool vec = nz % 4 == 0 && aligned(d_v, 16), pack = nz % 4 == 0 && aligned(d_mask, 4);
-    const dim3 grid(span_blocks(g));
+    const dim3 grid(span_blocks(g, SPAN));
     const int a = has_lo ? 1 : 0, b = has_hi ? 1 : 0;
     if (vec && pack) hipLaunchKernelGGL((k_threshold<true, true>), grid, dim3(TPB), 0, st, d_v, g, lo, hi, a, b, d_mask);
     else if (vec) hipLaunchKernelGGL((k_threshold<true, false>), grid, dim3(TPB), 0, st, d_v, g, lo, hi, a, b, d_mask);
@@ -912,7 +798,7 @@ TOMO_API int tomo_seg_label(tomo_seg *h, void *stream, const uint8_t *d_mask, in
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(h, hipSetDevice(h->device));
     const Vol g = vol_of(nx, ny, nz, -1);
-    const unsigned nb = span_blocks(g);
+    const unsigned nb = span_blocks(g, SPAN);
     CHK(grow(h, h->cnt, sizeof(int) * ((size_t)nb + 1)));
     CHK(grow(h, h->res, sizeof(int) * 2));
     int *counts = static_cast<int *>(h->cnt.p), *res = static_cast<int *>(h->res.p);
@@ -973,7 +859,7 @@ TOMO_API int tomo_seg_measure(tomo_seg *h, void *stream, const int32_t *d_labels
     CHK(grow(h, h->tab, entry_bytes(with_vol) * (size_t)m));
     const Tab t = tab_of(h->tab.p, m, with_vol);
     const bool vec = nz % 4 == 0 && aligned(d_labels, 16) && (!with_vol || aligned(d_v, 16));
-    const dim3 grid(span_blocks(g));
+    const dim3 grid(span_blocks(g, SPAN));
     std::vector<int> codes;
     for (long long l0 = 0; l0 < n; l0 += per) {
         const long long k = std::min<long long>(per, n - l0);
@@ -1021,7 +907,7 @@ TOMO_API int tomo_seg_remove_small(tomo_seg *h, void *stream, const int32_t *d_l
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(SCAN_TPB), 0, st, (int *)h->tab.p, (long long)n, 1, ms, (int *)h->res.p);
     HIPCHK(h, hipGetLastError());
     const bool vec = nz % 4 == 0 && aligned(d_labels, 16), vout = nz % 4 == 0 && aligned(d_out, 16);
-    const dim3 grid(span_blocks(g));
+    const dim3 grid(span_blocks(g, SPAN));
     const int *table = static_cast<const int *>(h->tab.p);
     if (vec && vout) hipLaunchKernelGGL((k_relabel<true, true>), grid, dim3(TPB), 0, st, d_labels, g, n, table, d_out);
     else if (vec) hipLaunchKernelGGL((k_relabel<true, false>), grid, dim3(TPB), 0, st, d_labels, g, n, table, d_out);
@@ -1048,7 +934,7 @@ TOMO_API int tomo_seg_largest(tomo_seg *h, void *stream, const int32_t *d_labels
     hipLaunchKernelGGL(k_argmax, dim3(1), dim3(TPB), 0, st, (const unsigned *)h->tab.p, n, res);
     HIPCHK(h, hipGetLastError());
     const bool vec = nz % 4 == 0 && aligned(d_labels, 16), pack = nz % 4 == 0 && aligned(d_mask, 4);
-    const dim3 grid(span_blocks(g));
+    const dim3 grid(span_blocks(g, SPAN));
     if (vec && pack) hipLaunchKernelGGL((k_pick<true, true>), grid, dim3(TPB), 0, st, d_labels, g, (const int *)res, d_mask);
     else if (vec) hipLaunchKernelGGL((k_pick<true, false>), grid, dim3(TPB), 0, st, d_labels, g, (const int *)res, d_mask);
     else if (pack) hipLaunchKernelGGL((k_pick<false, true>), grid, dim3(TPB), 0, st, d_labels, g, (const int *)res, d_mask);

@@ -8,11 +8,15 @@ CXXFLAGS ?= -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -mun
             -Wall -Wno-unused-function -DTOMO_$(shell echo $(NAME) | tr a-z A-Z)_BUILD
 LDFLAGS ?= $(strip -shared $(LIBS))
 SRCS = tomo_$(NAME).hip
-HDRS = ../../../include/tomo_$(NAME).h ../tomo_side_host.h ../tomo_side_fft.h
+HDRS = ../../../include/tomo_$(NAME).h ../tomo_side_host.h ../tomo_side_fft.h ../tomo_side_zgroups.h ../tomo_side_reduce.h
 OUT = ../../libtomo_$(NAME).so
 all: $(OUT)
 $(OUT): $(SRCS) $(HDRS)
 	$(HIPCC) $(CXXFLAGS) $(EXTRA) $(SRCS) -o $@ $(LDFLAGS)
+# the device assembly and the kernels' register, LDS and scratch use, as `make asm` of ../Makefile
+asm: $(SRCS) $(HDRS)
+	mkdir -p ../../../build/asm && $(HIPCC) $(CXXFLAGS) $(EXTRA) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $(SRCS) \
+	    -o ../../../build/asm/$(SRCS).s 2> ../../../build/asm/$(SRCS).usage.txt
 clean:
 	rm -f $(OUT)
-.PHONY: all clean
+.PHONY: all asm clean

@@ -1,11 +1,8 @@
 // libtomo_vol.so: statistics, histogram, 8/16-bit conversion, cylinder mask, projections and planes of a device volume v[nx][ny][nz]
 // (z fastest) on gfx950 (include/tomo_vol.h, tomography_alignment_amd/postprocess.py).
 //
-// The elementwise kernels share one decomposition.  A row (x, y) is cut into G = ceil(nz / 4) groups of four consecutive z; the
-// volume is nx ny G groups in memory order and a lane owns one group at a time: a 16-byte load (VEC: nz % 4 == 0 and v 16-byte aligned,
-// so every group's address is) or four guarded 4-byte loads of the same elements.  A work-group of 256 lanes owns SPAN consecutive
-// groups (the histogram: a longer stretch, see below) and walks them 256 at a time, so short rows waste no lanes.  One 64-bit division
-// per work-group places its first group; a lane's (row, group of the row) follow by a 32-bit one.  A row outside the region is not read.
+// The elementwise kernels share the decomposition of csrc/tomo_side_zgroups.h: groups of four z, SPAN of them a work-group (the
+// histogram: a longer stretch, see below).
 //
 // k_stats      per lane float64 sum and sum of squares, min, max and the two counts over its groups in order; the wave by a fixed
 //              shuffle tree, the four waves in order: one partial per work-group.  The grid depends on (nx, ny, nz) only.
@@ -37,6 +34,7 @@ namespace {
 constexpr int SIDE_ERR_ARG = TOMO_VOL_ERR_ARG, SIDE_ERR_HIP = TOMO_VOL_ERR_HIP, SIDE_ERR_NODEV = TOMO_VOL_ERR_NODEV;
 }
 #include "../tomo_side_host.h"
+#include "../tomo_side_zgroups.h"
 
 namespace {
 
@@ -47,13 +45,6 @@ constexpr int TILE = TOMO_VOL_TILE, LD = TILE + 1;
 constexpr int ZYX_MAX_GRID = 1 << 10;              // z tiles of the grid of k_quant_zyx: 2^10 * 64 = 2^31 - TOMO_VOL_MAX_NZ, so z0 stays an int
 constexpr long long MAX_BLOCKS = 0xffffff;         // of 256 lanes along x of a grid: HIP takes fewer than 2^32 threads per dimension
 static_assert(SPAN % TPB == 0 && TILE == 64 && TPB == 256, "a work-group walks its span 256 groups at a time; the tile maps assume 64 and 256");
-
-struct Vol {
-    int nx, ny, nz;
-    unsigned G;              // groups of four z of a row
-    long long R4;            // < 0: no region
-    long long groups;        // nx ny G
-};
 
 struct Part {                // what one work-group of k_stats leaves
     double sum, sumsq;
@@ -69,47 +60,6 @@ struct Stats {               // tomo_vol_stats_t on the device
 static_assert(sizeof(Stats) == sizeof(tomo_vol_stats_t), "the device result is copied into the caller's struct as it is");
 
 // ---------------------------------------------------------------------------------------------------------------------- device helpers
-
-__device__ inline bool finite32(float v) { return fabsf(v) <= FLT_MAX; }          // false for NaN and +-inf
-
-__device__ inline bool inside(const Vol &g, unsigned row) {
-    if (g.R4 < 0) return true;
-    const unsigned x = row / (unsigned)g.ny, y = row - x * (unsigned)g.ny;
-    const long long a = 2LL * x - g.nx + 1, b = 2LL * y - g.ny + 1;
-    return a * a + b * b <= g.R4;
-}
-
-// The four z of group zq of a row that starts at `row`: f[k] and whether z + k < nz.
-template <bool VEC>
-__device__ inline void load4(const float *__restrict__ row, int nz, unsigned zq, float f[4], bool in[4]) {
-    const int z = 4 * (int)zq;
-    if (VEC) {                                                           // nz % 4 == 0: the whole group is inside the row
-        const float4 t = *reinterpret_cast<const float4 *>(row + z);
-        f[0] = t.x, f[1] = t.y, f[2] = t.z, f[3] = t.w;
-        in[0] = in[1] = in[2] = in[3] = true;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            in[k] = z + k < nz;
-            f[k] = in[k] ? row[z + k] : 0.f;
-        }
-    }
-}
-
-// The walk of a work-group over `span` groups from group g0: lane's step s is group g0 + s * TPB + tid.
-struct Walk {
-    long long row0;          // the row of the work-group's first group
-    unsigned zb;             // that group's index in its row
-    long long left;          // groups from g0 to the end of the volume
-};
-
-__device__ inline Walk walk_of(const Vol &g, long long g0) {
-    Walk w;
-    w.row0 = g0 / g.G;
-    w.zb = (unsigned)(g0 - w.row0 * g.G);
-    w.left = g.groups - g0;
-    return w;
-}
 
 __device__ inline unsigned quant(float v, float lo, float s, unsigned qmax) {
     const float r = rintf((v - lo) * s);                                 // half to even
@@ -129,8 +79,7 @@ __global__ __launch_bounds__(TPB) void k_stats(const float *__restrict__ v, Vol 
 #pragma unroll 4
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         if (!inside(g, (unsigned)row)) continue;
         float f[4];
         bool in[4];
@@ -224,9 +173,8 @@ __global__ __launch_bounds__(TPB) void k_hist(const float *__restrict__ v, Vol g
         long long row = 0;
         unsigned zq = 0;
         if (live) {
-            const unsigned local = w.zb + off, dr = local / g.G;
-            zq = local - dr * g.G;
-            row = w.row0 + dr;
+            const Step s = step_of(g, w, off);
+            zq = s.zq, row = s.row;
             live = inside(g, (unsigned)row);
         }
         int b[4] = {-1, -1, -1, -1};                                     // -1: nothing to add to a bin
@@ -284,8 +232,7 @@ __global__ __launch_bounds__(TPB) void k_quant_xyz(const float *__restrict__ v, 
 #pragma unroll 4
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         const int z = 4 * (int)zq;
         unsigned c[4] = {fill, fill, fill, fill};
         bool in[4];
@@ -383,8 +330,7 @@ __global__ __launch_bounds__(TPB) void k_mask(const float *v, Vol g, float value
 #pragma unroll 4
     for (unsigned off = threadIdx.x; off < SPAN; off += TPB) {
         if ((long long)off >= w.left) break;
-        const unsigned local = w.zb + off, dr = local / g.G, zq = local - dr * g.G;
-        const long long row = w.row0 + dr;
+        const auto [row, zq] = step_of(g, w, off);
         const int z = 4 * (int)zq;
         float f[4] = {value, value, value, value};
         bool in[4];
@@ -477,6 +423,7 @@ struct tomo_vol {
     Buf table;               // uint64 [nbins + 3]
     bool have_stats = false;
     int nbins = 0;           // of the last tomo_vol_histogram; 0 before it
+    auto bufs() { return std::array{&part, &stats, &table}; }
 };
 
 namespace {
@@ -492,17 +439,6 @@ int check_shape(tomo_vol *h, long long nx, long long ny, long long nz) {
     return TOMO_VOL_OK;
 }
 
-Vol vol_of(int nx, int ny, int nz, long long R4) {
-    Vol g;
-    g.nx = nx, g.ny = ny, g.nz = nz;
-    g.G = (unsigned)(((long long)nz + 3) / 4);
-    g.R4 = R4 < 0 ? -1 : R4;
-    g.groups = (long long)nx * ny * g.G;
-    return g;
-}
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // What every entry point checks first.
 int check_call(tomo_vol *h, const char *what, const void *d_v, int nx, int ny, int nz) {
     if (!h) return fail(h, TOMO_VOL_ERR_ARG, std::string(what) + ": NULL handle");
@@ -511,8 +447,6 @@ int check_call(tomo_vol *h, const char *what, const void *d_v, int nx, int ny, i
     return check_shape(h, nx, ny, nz);
 }
 
-inline unsigned span_blocks(const Vol &g) { return (unsigned)((g.groups + SPAN - 1) / SPAN); }
-
 }  // namespace
 
 extern "C" {
@@ -520,19 +454,13 @@ extern "C" {
 TOMO_API int tomo_vol_abi_version(void) { return 1; }
 
 TOMO_API int tomo_vol_create(int device, tomo_vol **out) {
-    CHK(check_create(device, out));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, TOMO_VOL_ERR_HIP, "hipSetDevice failed");
-    tomo_vol *h = new tomo_vol();
-    h->device = device;
-    *out = h;
-    return TOMO_VOL_OK;
+    return create_plain(device, true, out);
 }
 
 TOMO_API int tomo_vol_destroy(tomo_vol *h) {
     if (!h) return TOMO_VOL_OK;
     (void)hipSetDevice(h->device);
-    for (Buf *b : {&h->part, &h->stats, &h->table})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_VOL_OK;
 }
@@ -541,7 +469,7 @@ TOMO_API const char *tomo_vol_last_error(tomo_vol *h) { return last_error(h); }
 
 TOMO_API int tomo_vol_device_bytes(tomo_vol *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_VOL_ERR_ARG, "tomo_vol_device_bytes: NULL");
-    *bytes = (int64_t)(h->part.n + h->stats.n + h->table.n);
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_VOL_OK;
 }
 
@@ -564,7 +492,7 @@ TOMO_API int tomo_vol_stats(tomo_vol *h, void *stream, const float *d_v, int nx,
     HIPCHK(h, hipSetDevice(h->device));
     h->have_stats = false;
     const Vol g = vol_of(nx, ny, nz, R4);
-    const unsigned nb = span_blocks(g);
+    const unsigned nb = span_blocks(g, SPAN);
     // a grow frees the old block: hipFree waits for the device, so nothing in flight still uses it
     CHK(grow(h, h->part, sizeof(Part) * (size_t)nb));
     CHK(grow(h, h->stats, sizeof(Stats)));
@@ -655,7 +583,7 @@ TOMO_API int tomo_vol_quantize(tomo_vol *h, void *stream, const float *d_v, int 
         else VOL_LAUNCH(K, T, false, false, grid);             \
     } while (0)
     if (order == 0) {
-        const dim3 grid(span_blocks(g));
+        const dim3 grid(span_blocks(g, SPAN));
         const bool pack = nz % 4 == 0 && aligned(d_out, (uintptr_t)(bits / 2));       // four codes: 4 or 8 bytes
         if (bits == 8) VOL_PICK(k_quant_xyz, uint8_t, vec, pack, grid);
         else VOL_PICK(k_quant_xyz, uint16_t, vec, pack, grid);
@@ -679,7 +607,7 @@ TOMO_API int tomo_vol_mask(tomo_vol *h, void *stream, const float *d_v, int nx, 
     HIPCHK(h, hipSetDevice(h->device));
     const Vol g = vol_of(nx, ny, nz, R4);
     const bool vec = nz % 4 == 0 && aligned(d_v, 16), vout = nz % 4 == 0 && aligned(d_out, 16);
-    const dim3 grid(span_blocks(g));
+    const dim3 grid(span_blocks(g, SPAN));
     if (vec && vout) hipLaunchKernelGGL((k_mask<true, true>), grid, dim3(TPB), 0, st, d_v, g, value, d_out);
     else if (vec) hipLaunchKernelGGL((k_mask<true, false>), grid, dim3(TPB), 0, st, d_v, g, value, d_out);
     else if (vout) hipLaunchKernelGGL((k_mask<false, true>), grid, dim3(TPB), 0, st, d_v, g, value, d_out);

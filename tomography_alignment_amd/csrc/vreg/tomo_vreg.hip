@@ -45,6 +45,7 @@ constexpr int SIDE_ERR_ARG = TOMO_VREG_ERR_ARG, SIDE_ERR_HIP = TOMO_VREG_ERR_HIP
 }
 #include "../tomo_side_host.h"
 #include "../tomo_side_fft.h"
+#include "../tomo_side_reduce.h"
 
 namespace {
 
@@ -69,12 +70,6 @@ struct Shape {
     long long M;                     // rows * nzh stored coefficients
 };
 
-struct Mask {
-    int mode;                        // tomo_vreg_mask
-    const float *arr;
-    double R, E;
-};
-
 struct Pair {                        // a candidate of the maximum; i < 0: none yet
     double v;
     long long i;
@@ -82,19 +77,7 @@ struct Pair {                        // a candidate of the maximum; i < 0: none 
 
 // ---------------------------------------------------------------------------------------------------------------------- kernels
 
-// Block tree reduction of a sum in LDS, fixed order; every thread gets the total.
-__device__ inline double block_sum(double v, double *sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = TPB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-// The mask at voxel (row = ix ny + iy, iz), float64 (tomo_fsc.hip's mask_at).
+// The mask at voxel (row = ix ny + iy, iz), float64; the edge is tomo_side_reduce.h's.
 __device__ inline double mask_at(const Mask &m, const Shape &g, long long row, int iz) {
     if (m.mode == TOMO_VREG_MASK_NONE) return 1.0;
     if (m.mode == TOMO_VREG_MASK_ARRAY) return (double)m.arr[row * g.nz + iz];
@@ -102,11 +85,7 @@ __device__ inline double mask_at(const Mask &m, const Shape &g, long long row, i
     const double dx = (double)(r / g.ny) - 0.5 * (g.nx - 1);
     const double dy = (double)(r % g.ny) - 0.5 * (g.ny - 1);
     const double dz = (double)iz - 0.5 * (g.nz - 1);
-    const double d2 = dx * dx + dy * dy + dz * dz;
-    if (d2 <= m.R * m.R) return 1.0;
-    const double Ro = m.R + m.E;
-    if (d2 >= Ro * Ro || m.E <= 0.0) return 0.0;
-    return 0.5 * (1.0 + cos(PI * (sqrt(d2) - m.R) / m.E));
+    return mask_edge(dx * dx + dy * dy + dz * dz, m.R, m.E);
 }
 
 // The four values of the group at z of a row of nz floats; elements past the row are 0.  vec: nz % 4 == 0 and the volume is 16-byte aligned.
@@ -153,8 +132,8 @@ __global__ __launch_bounds__(TPB) void k_mask_sums(const float *__restrict__ v, 
                 }
         }
     }
-    const double t0 = block_sum(smv, sh);
-    const double t1 = block_sum(sm, sh);
+    const double t0 = block_sum<TPB>(smv, sh);
+    const double t1 = block_sum<TPB>(sm, sh);
     if (threadIdx.x == 0) {
         part[blockIdx.x * 2] = t0;
         part[blockIdx.x * 2 + 1] = t1;
@@ -164,8 +143,8 @@ __global__ __launch_bounds__(TPB) void k_mask_sums(const float *__restrict__ v, 
 // *mean = sum(m v) / sum(m) from the SUM_G partials of k_mask_sums by the fixed tree; 0 where sum(m) is 0.  One work-group.
 __global__ __launch_bounds__(TPB) void k_fold_mean(const double *__restrict__ part, double *__restrict__ mean) {
     __shared__ double sh[TPB];
-    const double smv = block_sum(part[threadIdx.x * 2], sh);
-    const double sm = block_sum(part[threadIdx.x * 2 + 1], sh);
+    const double smv = block_sum<TPB>(part[threadIdx.x * 2], sh);
+    const double sm = block_sum<TPB>(part[threadIdx.x * 2 + 1], sh);
     if (threadIdx.x == 0) *mean = sm != 0.0 ? smv / sm : 0.0;
 }
 
@@ -201,7 +180,7 @@ __global__ __launch_bounds__(TPB) void k_prepare(const float *__restrict__ v, Sh
         if (z + 2 < g.pitch) *reinterpret_cast<float2 *>(o + 2) = make_float2(a[2], a[3]);
     }
     if (esq) {
-        const double t = block_sum(e2, sh);
+        const double t = block_sum<TPB>(e2, sh);
         if (threadIdx.x == 0) esq[blockIdx.x] = t;
     }
 }
@@ -211,7 +190,7 @@ __global__ __launch_bounds__(TPB) void k_fold_sums(const double *__restrict__ pa
     __shared__ double sh[TPB];
     double t = 0.0;
     for (long long i = threadIdx.x; i < n; i += TPB) t += part[i];
-    const double s = block_sum(t, sh);
+    const double s = block_sum<TPB>(t, sh);
     if (threadIdx.x == 0) *dst = s;
 }
 
@@ -540,6 +519,7 @@ struct tomo_vreg {
     Buf spec[2], pcopy;              // the padded buffers of the two slots; the copy of P (and the work buffer of shift)
     Buf sums, esq, apart, small;     // mean partials; E partials; argmax partials; the small results (see Small)
     Buf tab[3], t1, t2, cu, ramp;    // refine's tables and scratch; shift's three tables
+    auto bufs() { return std::array{&work, &spec[0], &spec[1], &pcopy, &sums, &esq, &apart, &small, &tab[0], &tab[1], &tab[2], &t1, &t2, &cu, &ramp}; }
     size_t scratch = DEFAULT_SCRATCH;
 };
 
@@ -604,13 +584,12 @@ int ready(tomo_vreg *h, const char *who) {
 }
 
 inline unsigned blocks(long long n, int per = TPB) { return (unsigned)((n + per - 1) / per); }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline Small *small(tomo_vreg *h) { return (Small *)h->small.p; }
 
 // (v - mean) m, or v itself, into a padded buffer.  E: where the sum of squares goes (NULL: not wanted).
 int launch_prepare(tomo_vreg *h, hipStream_t st, const float *d_vol, const Mask &m, bool subtract_mean, float *out, double *E) {
     const Shape &g = h->g;
-    const int vec = g.nz % 4 == 0 && aligned16(d_vol);
+    const int vec = g.nz % 4 == 0 && aligned(d_vol, 16);
     double *part = (double *)h->sums.p, *mean = subtract_mean ? &small(h)->mean : nullptr;
     const long long groups = g.rows * ((g.pitch + 3) / 4);
     const unsigned wgs = blocks(groups, GPW);
@@ -667,20 +646,14 @@ extern "C" {
 TOMO_API int tomo_vreg_abi_version(void) { return 1; }
 
 TOMO_API int tomo_vreg_create(int device, tomo_vreg **out) {
-    CHK(check_create(device, out));
-    tomo_vreg *h = new tomo_vreg();
-    h->device = device;
-    *out = h;
-    return TOMO_VREG_OK;
+    return create_plain(device, false, out);
 }
 
 TOMO_API int tomo_vreg_destroy(tomo_vreg *h) {
     if (!h) return TOMO_VREG_OK;
     (void)hipSetDevice(h->device);
     h->plans.destroy_all();
-    for (Buf *b : {&h->work, &h->spec[0], &h->spec[1], &h->pcopy, &h->sums, &h->esq, &h->apart, &h->small, &h->tab[0], &h->tab[1], &h->tab[2], &h->t1,
-                   &h->t2, &h->cu, &h->ramp})
-        if (b->p) (void)hipFree(b->p);
+    free_bufs(h->bufs());
     delete h;
     return TOMO_VREG_OK;
 }
@@ -720,11 +693,7 @@ TOMO_API int tomo_vreg_set_shape(tomo_vreg *h, int nx, int ny, int nz) {
 
 TOMO_API int tomo_vreg_device_bytes(tomo_vreg *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, TOMO_VREG_ERR_ARG, "tomo_vreg_device_bytes: NULL");
-    size_t t = 0;
-    for (const Buf *b : {&h->work, &h->spec[0], &h->spec[1], &h->pcopy, &h->sums, &h->esq, &h->apart, &h->small, &h->tab[0], &h->tab[1], &h->tab[2],
-                         &h->t1, &h->t2, &h->cu, &h->ramp})
-        t += b->n;
-    *bytes = (int64_t)t;
+    *bytes = (int64_t)buf_bytes(h->bufs());
     return TOMO_VREG_OK;
 }
 
@@ -845,7 +814,7 @@ TOMO_API int tomo_vreg_shift(tomo_vreg *h, void *stream, const float *d_src, con
     if (a0 != b0 && a0 < b0 + bytes && b0 < a0 + bytes) return fail(h, TOMO_VREG_ERR_ARG, "tomo_vreg_shift: src and dst overlap without being equal");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int vec = g.nz % 4 == 0 && aligned16(d_dst);
+    const int vec = g.nz % 4 == 0 && aligned(d_dst, 16);
     const unsigned wgs = blocks(g.rows * ((g.nz + 3) / 4));
     if (integer) {
         const float *src = d_src;
@@ -878,7 +847,7 @@ TOMO_API int tomo_vreg_argmax(tomo_vreg *h, void *stream, const float *d_vol, in
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const Shape &g = h->g;
-    CHK(launch_argmax(h, st, d_vol, g.rows, g.nz, (long long)g.nz, g.nz % 4 == 0 && aligned16(d_vol), &small(h)->user));
+    CHK(launch_argmax(h, st, d_vol, g.rows, g.nz, (long long)g.nz, g.nz % 4 == 0 && aligned(d_vol, 16), &small(h)->user));
     Pair p{};
     HIPCHK(h, hipMemcpyAsync(&p, &small(h)->user, sizeof(Pair), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));

@@ -20,6 +20,7 @@ constexpr int SIDE_ERR_ARG = TOMO_XCORR_ERR_ARG, SIDE_ERR_HIP = TOMO_XCORR_ERR_H
 }
 #include "../tomo_side_host.h"
 #include "../tomo_side_fft.h"
+#include "../tomo_side_reduce.h"
 
 namespace {
 
@@ -34,17 +35,6 @@ std::atomic<int64_t> g_device_bytes{0};
 template <class T>
 __device__ inline double ld(const T *p, long i) { return (double)p[i]; }
 
-// Block tree reduction of a sum in LDS, fixed order; every thread gets the total.
-__device__ inline double block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = TPB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // Partial sums of B planes of N values (dtype T): part[b * G + blk].
 template <class T>
 __global__ __launch_bounds__(TPB) void k_sum_partial(const T *x, long N, double *part) {
@@ -54,7 +44,7 @@ __global__ __launch_bounds__(TPB) void k_sum_partial(const T *x, long N, double 
     const long lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
     double s = 0.0;
     for (long i = lo + threadIdx.x; i < hi; i += TPB) s += ld(x + b * N, i);
-    double t = block_sum(s, sh);
+    double t = block_sum<TPB>(s, sh);
     if (threadIdx.x == 0) part[b * G + blockIdx.x] = t;
 }
 
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(TPB) void k_sumsq_partial(const double2 *x, long N,
         double2 z = x[b * N + i];
         s += z.x * z.x + z.y * z.y;
     }
-    double t = block_sum(s, sh);
+    double t = block_sum<TPB>(s, sh);
     if (threadIdx.x == 0) part[b * G + blockIdx.x] = t;
 }
 
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(TPB) void k_load_window(const T *x, long N, const d
     const long b = blockIdx.y;
     double mean = 0.0;
     if (part) {
-        double t = block_sum(part[b * G + threadIdx.x], sh);
+        double t = block_sum<TPB>(part[b * G + threadIdx.x], sh);
         mean = t / (double)N;
     }
     const long i = (long)blockIdx.x * TPB + threadIdx.x;
@@ -376,9 +366,8 @@ __global__ __launch_bounds__(TPB) void k_pcc_scalars(const double *part_src, con
                                                      int upsample, double *err, double *phase) {
     __shared__ double sh[TPB];
     const long b = blockIdx.x;
-    double sa = block_sum(part_src[b * G + threadIdx.x], sh);
-    __syncthreads();
-    double ta = block_sum(part_tgt[b * G + threadIdx.x], sh);
+    double sa = block_sum<TPB>(part_src[b * G + threadIdx.x], sh);
+    double ta = block_sum<TPB>(part_tgt[b * G + threadIdx.x], sh);
     if (threadIdx.x != 0) return;
     if (upsample == 1) { sa /= (double)N; ta /= (double)N; }
     const double2 c = ccmax[b];
