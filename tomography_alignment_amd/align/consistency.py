@@ -40,7 +40,7 @@ import numpy as np
 
 from .. import _mom_lib
 from .._mom_lib import MomUnsupported  # noqa: F401  (re-exported)
-from .._ops import HandleOwner, _is_dev
+from .._ops import HandleOwner, stack_shape as _shape_of
 
 DEFAULT_SCRATCH = 2 << 30
 MIN_N = 4
@@ -199,18 +199,6 @@ def shifts_from_marginals(m, phi, vertical="moment", upsample=20, max_lag=None, 
 
 # ------------------------------------------------------------------------------------------------------------------- the device
 
-def _shape_of(proj, shape, who):
-    own = tuple(proj.shape) if _is_dev(proj) else np.shape(proj)
-    shp = tuple(int(v) for v in (own if shape is None else shape))
-    if len(shp) != 3:
-        raise ValueError("%s: proj must be (n, nx, nz) (give `shape` for a flat device buffer), got shape %s" % (who, shp))
-    if int(np.prod(shp)) != int(np.prod(own)):
-        raise ValueError("%s: proj holds %d values, not the %d of shape %s" % (who, int(np.prod(own)), int(np.prod(shp)), shp))
-    if _is_dev(proj) and np.dtype(proj.dtype) != np.float32:
-        raise ValueError("%s: proj must be float32 on the device, got %s" % (who, proj.dtype))
-    return shp
-
-
 def _window(zrange, nz, who):
     if zrange is None:
         return 0, nz
@@ -245,16 +233,10 @@ class Consistency(HandleOwner):
         _mom_lib.check_shape(n, nx, nz, z0, z1)                     # MomUnsupported before a context, a handle or a launch
         self._ready(proj)
         ctx, h = self.ctx, self.handle
-        tmp = None
-        try:
-            d_p = proj if _is_dev(proj) else ctx.to_device(np.asarray(proj, np.float32))
-            if d_p is not proj:
-                tmp = d_p
+        with self._staging(proj) as st:
+            d_p = st.source(proj)
             h.set_max_scratch(max_scratch_bytes)
             Q, Z, bad = h.marginals(ctx.stream(), d_p.ptr, n, nx, nz, floor, z0, z1)      # waits
-        finally:
-            if tmp is not None:
-                tmp.free()
         return moments(Q, Z, bad)
 
     def estimate_shifts(self, proj, phi, floor=None, zrange=None, vertical="moment", upsample=20, max_lag=None, allow_bad=False,

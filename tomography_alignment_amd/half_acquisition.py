@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _half_lib
 from ._half_lib import HalfUnsupported  # noqa: F401  (re-exported)
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, _is_dev, stack_shape as _shape3
 
 SIDES = ("right", "left")          # the order of the curves of one row
 DEFAULT_SCRATCH = 1 << 30
@@ -169,18 +169,6 @@ def center_from_curves(m_right, m_left, nx, w, side=None):
     return best
 
 
-def _shape3(proj, shape, what):
-    own = tuple(proj.shape) if _is_dev(proj) else np.shape(proj)
-    shp = tuple(int(v) for v in (own if shape is None else shape))
-    if len(shp) != 3:
-        raise ValueError("%s: proj must be (n, nx, nz) (give `shape` for a flat device buffer), got shape %s" % (what, shp))
-    if int(np.prod(shp)) != int(np.prod(own)):
-        raise ValueError("%s: proj holds %d values, not the %d of shape %s" % (what, int(np.prod(own)), int(np.prod(shp)), shp))
-    if _is_dev(proj) and np.dtype(proj.dtype) != np.float32:
-        raise ValueError("%s: proj must be float32 on the device, got %s" % (what, proj.dtype))
-    return shp
-
-
 class HalfAcquisition(HandleOwner):
     """One libtomo_half handle -- the gathered sinograms, the search's sums and the stitch's table -- reused across calls.  ctx: the
     _lib.Context whose device and stream the work uses (default: that of the DeviceArray passed in, or a context of the handle's own)."""
@@ -205,21 +193,14 @@ class HalfAcquisition(HandleOwner):
         _half_lib.check_shape(n, nx, nz, rows.size, w)             # HalfUnsupported before a context, a handle or a launch
         self._ready(proj)
         ctx, h = self.ctx, self.handle
-        tmp = None
-        try:
-            if _is_dev(proj):
-                d_p, nz_d, rows_d = proj, nz, rows
-            else:                                                    # only the rows searched are uploaded
-                host = np.ascontiguousarray(np.asarray(proj, np.float32)[:n, :, rows])
-                d_p = tmp = ctx.to_device(host, np.float32)
-                nz_d, rows_d, n_p = rows.size, np.arange(rows.size), n
+        with self._staging(proj) as st:
+            src, nz_d, rows_d = proj, nz, rows
+            if not st.dev:                                           # only the rows searched are uploaded
+                src, nz_d, rows_d, n_p = np.asarray(proj, np.float32)[:n, :, rows], rows.size, np.arange(rows.size), n
+            d_p = st.source(src)
             h.set_max_scratch(max_scratch_bytes)
             h.load_rows(ctx.stream(), d_p.ptr, n_p, nx, nz_d, n, rows_d)
-            m = h.search(ctx.stream(), w)                            # waits
-        finally:
-            if tmp is not None:
-                ctx.sync()                                           # the gather reads it
-                tmp.free()
+            m = h.search(ctx.stream(), w)                            # waits; so does the free of the upload, which the gather reads
         return m, rows, n, nx, w
 
     def find_center_360(self, proj, angles=None, rows=None, win_width=None, side=None, return_curves=False, shape=None,
@@ -260,26 +241,11 @@ class HalfAcquisition(HandleOwner):
         self._ready(proj)
         ctx, hd = self.ctx, self.handle
         half_angles = None if angles is None else np.asarray(angles, np.float64).ravel()[:h].copy()
-        if dev:
-            d_out = ctx.empty((h, W, nz), np.float32) if out is None else out
-            try:
-                hd.stitch(ctx.stream(), proj.ptr, n, nx, nz, c, d_out.ptr)     # refuses an out that overlaps proj
-            except Exception:
-                if out is None:
-                    d_out.free()
-                raise
-            return StitchResult(d_out, c + j0, W, half_angles)
-        d_p = d_out = None
-        try:
-            d_p = ctx.to_device(np.asarray(proj, np.float32)[:n], np.float32)
-            d_out = ctx.empty((h, W, nz), np.float32)
-            hd.stitch(ctx.stream(), d_p.ptr, n, nx, nz, c, d_out.ptr)
-            res = d_out.download(out)
-        finally:
-            for d in (d_p, d_out):
-                if d is not None:
-                    d.free()
-        return StitchResult(res, c + j0, W, half_angles)
+        with self._staging(proj) as st:
+            d_p = st.source(proj if dev else np.asarray(proj, np.float32)[:n])
+            d_out = st.dest((h, W, nz), np.float32, out)
+            hd.stitch(ctx.stream(), d_p.ptr, n, nx, nz, c, d_out.ptr)          # refuses a device out that overlaps proj
+            return StitchResult(st.result(d_out, out), c + j0, W, half_angles)
 
 
 def find_center_360(proj, angles=None, rows=None, win_width=None, side=None, return_curves=False, ctx=None, shape=None,

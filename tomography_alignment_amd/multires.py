@@ -26,7 +26,7 @@ ValueError before the library is loaded; nothing here synchronises.
 import numpy as np
 
 from . import _pyr_lib
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, _is_dev, shape_of
 from ._pyr_lib import PyrUnsupported  # noqa: F401  (re-exported)
 
 FACTORS = _pyr_lib.FACTORS
@@ -34,20 +34,7 @@ FACTORS = _pyr_lib.FACTORS
 
 def _shape_of(a, shape, what, ndim):
     """The (n, nx, nz) / (nx, ny, nz) of `a`: `shape` if given (it must hold a's number of values), else a's own."""
-    own = tuple(a.shape) if _is_dev(a) else np.shape(a)
-    if shape is None:
-        shape = own
-    shape = tuple(int(v) for v in shape)
-    if len(shape) != ndim:
-        raise ValueError("%s must have %d dimensions (give `shape` for a flat buffer), got shape %s" % (what, ndim, shape))
-    if any(s < 1 for s in shape):
-        raise ValueError("%s must not be empty, got shape %s" % (what, shape))
-    if int(np.prod(shape)) != int(np.prod(own)):
-        raise ValueError("%s holds %d values, not the %d of shape %s" % (what, int(np.prod(own)), int(np.prod(shape)), shape))
-    dtype = a.dtype if _is_dev(a) else None
-    if dtype is not None and np.dtype(dtype) != np.float32:
-        raise ValueError("%s must be float32 on the device, got %s" % (what, dtype))
-    return shape
+    return shape_of(a, shape, ndim, what, nonempty=True)
 
 
 def _check_factor(f, extents, what):
@@ -93,25 +80,11 @@ class Pyramid(HandleOwner):
             if _is_dev(src) and src.ptr.value < out.ptr.value + out.nbytes and out.ptr.value < src.ptr.value + src.nbytes:
                 raise ValueError("out must not overlap the source")
         self._ready(src)
-        on_dev = _is_dev(src)
-        d_src = src if on_dev else self.ctx.to_device(np.ascontiguousarray(src, np.float32), np.float32)
-        try:
-            res = out if out is not None else self.ctx.empty(oshape, np.float32)
-            try:
-                launch(self.ctx.stream(), d_src.ptr, res.ptr)
-                if on_dev:
-                    return res
-                host = res.download().reshape(oshape)
-            except Exception:
-                if out is None:
-                    res.free()
-                raise
-            if out is None:
-                res.free()
-            return host
-        finally:
-            if not on_dev:
-                d_src.free()
+        with self._staging(src) as st:
+            d_src = st.source(src)
+            res = st.dest(oshape, np.float32, out)
+            launch(self.ctx.stream(), d_src.ptr, res.ptr)
+            return st.result(res, shape=oshape)
 
     def bin_projections(self, proj, f, scale=None, out=None, shape=None):
         """The sinogram proj [n][nx][nz] binned by f within each projection (module docstring); scale None: 1 / f."""

@@ -118,14 +118,7 @@ def _window(window, what):
 
 
 def _shape3(vol, shape):
-    s = tuple(int(n) for n in (shape if shape is not None else vol.shape))
-    if len(s) != 3:
-        raise ValueError("postprocess: need a 3-D volume [nx][ny][nz], not shape %r (a flat DeviceArray: pass shape=)" % (s,))
-    if int(np.prod(s, dtype=np.int64)) != int(vol.size):
-        raise ValueError("postprocess: shape %r does not hold %d elements" % (s, vol.size))
-    if np.dtype(vol.dtype) != np.float32:
-        raise ValueError("postprocess: need float32, not %s" % vol.dtype)
-    return s
+    return _ops.volume_shape(vol, shape, [np.float32], "postprocess", "volume")
 
 
 def _axis(axis):
@@ -147,35 +140,14 @@ class PostProcessor(_ops.HandleOwner):
     def device_bytes(self):
         return 0 if self.handle is None else self.handle.device_bytes()
 
-    # ---- plumbing
-    def _enter(self, vol, shape):
-        """-> (shape, the volume on the device, whether it is a temporary upload).  Every check that needs no device comes first."""
-        s = _shape3(vol, shape)
-        _vol_lib.check_shape(*s)
-        self._ready(vol)
-        if _ops._is_dev(vol):
-            return s, vol, False
-        return s, self.ctx.to_device(np.ascontiguousarray(vol, np.float32)), True
-
-    def _leave(self, vol, d, tmp, result=None, shape=None):
-        """Free a temporary upload; a device result of a host input comes back as numpy."""
-        if tmp:
-            d.free()
-        if result is not None and tmp:
-            host = result.download().reshape(shape if shape is not None else result.shape)
-            result.free()
-            return host
-        return result
-
-    # ---- the operations
+    # ---- the operations: every check that needs no device comes before _ready
     def statistics(self, vol, region=None, shape=None):
         s = _shape3(vol, shape)
         r4 = region_r4(region, s[0], s[1])
-        s, d, tmp = self._enter(vol, shape)
-        try:
-            r = self.handle.stats(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4)
-        finally:
-            self._leave(vol, d, tmp)
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            r = self.handle.stats(self.ctx.stream(), st.source(vol).ptr, s[0], s[1], s[2], r4)
         return VolumeStats(r.n_finite, r.n_nonfinite, r.min, r.max, r.sum, r.sumsq)
 
     def histogram(self, vol, bins=4096, range=None, region=None, shape=None):
@@ -185,18 +157,18 @@ class PostProcessor(_ops.HandleOwner):
             raise ValueError("histogram: bins must be an integer in 1 ... %d, not %r" % (MAX_BINS, bins))
         if range is not None:
             lo, hi = _window(range, "histogram: range")
-        s, d, tmp = self._enter(vol, shape)
-        try:
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            d = st.source(vol)
             if range is None:
-                st = self.handle.stats(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4)
-                if st.n_finite == 0:
+                r = self.handle.stats(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4)
+                if r.n_finite == 0:
                     raise ValueError("histogram: the region holds no finite value to take a range from")
-                lo, hi = np.float32(st.min), np.float32(st.max)
+                lo, hi = np.float32(r.min), np.float32(r.max)
                 if lo == hi:                                   # one ulp on each side, so that lo < hi
                     lo, hi = np.nextafter(lo, np.float32(-np.inf)), np.nextafter(hi, np.float32(np.inf))
             counts, (under, over, nonfinite) = self.handle.histogram(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4, lo, hi, int(bins))
-        finally:
-            self._leave(vol, d, tmp)
         return Histogram(counts, under, over, nonfinite, lo, hi)
 
     def circular_mask(self, vol, ratio=1.0, value=0.0, out=None, shape=None):
@@ -209,16 +181,13 @@ class PostProcessor(_ops.HandleOwner):
                 raise ValueError("circular_mask: out must be a float32 array of the volume's kind and size")
             if not dev and not out.flags["C_CONTIGUOUS"]:
                 raise ValueError("circular_mask: out must be C-contiguous")
-        s, d, tmp = self._enter(vol, shape)
-        try:
-            d_out = out if (dev and out is not None) else (d if tmp else self.ctx.empty(s, np.float32))
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            d = st.source(vol)
+            d_out = st.dest(s, np.float32, out, inplace=d)      # a temporary upload is masked in place
             self.handle.mask(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4, value, d_out.ptr)
-            if dev:
-                return d_out
-            host = d_out.download(out.reshape(s) if out is not None else None)      # d_out is the temporary upload, masked in place
-            return host if out is None else out
-        finally:
-            self._leave(vol, d, tmp)
+            return st.result(d_out, out)
 
     def quantize(self, vol, window, dtype=np.uint8, order="zyx", region=None, fill=0, out=None, shape=None):
         """-> codes of `dtype`, (nx, ny, nz) for order "xyz", (nz, ny, nx) for "zyx".  `out`: a DeviceArray of that dtype and size for a
@@ -241,49 +210,39 @@ class PostProcessor(_ops.HandleOwner):
                 raise ValueError("quantize: out must be a %s array of the volume's kind and size" % np.dtype(dtype).name)
             if not dev and not out.flags["C_CONTIGUOUS"]:
                 raise ValueError("quantize: out must be C-contiguous")
-        s, d, tmp = self._enter(vol, shape)
-        d_out = None
-        try:
-            d_out = out if (dev and out is not None) else self.ctx.empty(oshape, dtype)
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            d = st.source(vol)
+            d_out = st.dest(oshape, dtype, out)
             self.handle.quantize(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4, lo, hi, bits, _ORDERS[order], int(fill), d_out.ptr)
-            if dev:
-                return d_out
-            host = d_out.download(out.reshape(oshape) if out is not None else None)
-            return host if out is None else out
-        finally:
-            if not dev and d_out is not None:
-                d_out.free()
-            self._leave(vol, d, tmp)
+            return st.result(d_out, out)
 
     def project(self, vol, axis, op="max", shape=None):
         s = _shape3(vol, shape)
         axis = _axis(axis)
         if op not in _OPS:
             raise ValueError("project: op must be 'max' or 'min', not %r" % (op,))
-        s, d, tmp = self._enter(vol, shape)
-        d_out = self.ctx.empty(_plane_shape(s, axis), np.float32)
-        try:
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            d = st.source(vol)
+            d_out = st.dest(_plane_shape(s, axis), np.float32)
             self.handle.project(self.ctx.stream(), d.ptr, s[0], s[1], s[2], axis, _OPS[op], d_out.ptr)
-        except Exception:
-            d_out.free()
-            self._leave(vol, d, tmp)
-            raise
-        return self._leave(vol, d, tmp, d_out)
+            return st.result(d_out)
 
     def slice(self, vol, axis, index, shape=None):
         s = _shape3(vol, shape)
         axis = _axis(axis)
         if int(index) != index or not (0 <= int(index) < s[axis]):
             raise ValueError("slice: index %r is outside 0 ... %d of axis %d" % (index, s[axis] - 1, axis))
-        s, d, tmp = self._enter(vol, shape)
-        d_out = self.ctx.empty(_plane_shape(s, axis), np.float32)
-        try:
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as st:
+            d = st.source(vol)
+            d_out = st.dest(_plane_shape(s, axis), np.float32)
             self.handle.slice(self.ctx.stream(), d.ptr, s[0], s[1], s[2], axis, int(index), d_out.ptr)
-        except Exception:
-            d_out.free()
-            self._leave(vol, d, tmp)
-            raise
-        return self._leave(vol, d, tmp, d_out)
+            return st.result(d_out)
 
     def export_stack(self, vol, directory, dtype=np.uint8, percentiles=(0.1, 99.9), bins=4096, region="cylinder", previews=True, shape=None,
                      write=True):
@@ -297,8 +256,10 @@ class PostProcessor(_ops.HandleOwner):
         region_r4(region, s[0], s[1])
         if np.dtype(dtype) not in _DTYPES:
             raise ValueError("export_stack: dtype must be uint8 or uint16, not %r" % (dtype,))
-        s, d, tmp = self._enter(vol, shape)
-        try:
+        _vol_lib.check_shape(*s)
+        self._ready(vol)
+        with self._staging(vol) as whole:
+            d = whole.source(vol)
             st = self.statistics(d, region, shape=s)
             if st.n_finite == 0:
                 raise ValueError("export_stack: the region holds no finite value")
@@ -309,9 +270,9 @@ class PostProcessor(_ops.HandleOwner):
                 lo, hi = np.nextafter(lo, np.float32(-np.inf)), np.nextafter(hi, np.float32(np.inf))
             if write:
                 os.makedirs(directory, exist_ok=True)
-            d_codes = self.quantize(d, (lo, hi), dtype, "zyx", region, 0, shape=s)
-            try:                                                # the one download, through a bounded staging array that is touched once
-                plane = s[0] * s[1]
+            with self._staging(d) as codes:                     # the codes go before the previews are made
+                d_codes = self.quantize(d, (lo, hi), dtype, "zyx", region, 0, codes.scratch(s[::-1], dtype), shape=s)
+                plane = s[0] * s[1]                             # the one download, through a bounded staging array that is touched once
                 step = max(1, min(s[2], _STAGE_BYTES // (plane * np.dtype(dtype).itemsize)))
                 stage = np.empty((step, s[1], s[0]), dtype)
                 for z0 in range(0, s[2], step):
@@ -320,17 +281,13 @@ class PostProcessor(_ops.HandleOwner):
                     if write:
                         for z in range(k):
                             np.save(os.path.join(directory, "slice_%05d.npy" % (z0 + z)), stage[z])
-            finally:
-                d_codes.free()
             pre = {}
             if previews:
                 for a in range(3):
                     for name, d_p in (("preview_slice_axis%d" % a, self.slice(d, a, s[a] // 2, shape=s)),
                                       ("preview_max_axis%d" % a, self.project(d, a, "max", shape=s))):
                         pre[name] = d_p.download()
-                        d_p.free()
-        finally:
-            self._leave(vol, d, tmp)
+                        d_p.free()                              # a plane at a time: slice and project take no `out`
         meta = {"window": [float(lo), float(hi)], "dtype": np.dtype(dtype).name, "shape": list(s), "stack_shape": list(s[::-1]),
                 "region": None if region is None else (["cylinder", 1.0] if isinstance(region, str) else [region[0], float(region[1])]),
                 "percentiles": [float(p) for p in percentiles], "bins": int(bins), "statistics": st.as_dict(),
@@ -345,36 +302,36 @@ class PostProcessor(_ops.HandleOwner):
         return meta
 
 
-def _with(ctx, like, fn):
-    if ctx is None and _ops._is_dev(like):
-        ctx = like.ctx
-    with PostProcessor(ctx) as p:
-        return fn(p)
-
-
 def statistics(vol, region=None, ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.statistics(vol, region, shape=shape))
+    with PostProcessor(ctx) as p:                            # without a ctx: a device volume's (_ops.HandleOwner)
+        return p.statistics(vol, region, shape=shape)
 
 
 def histogram(vol, bins=4096, range=None, region=None, ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.histogram(vol, bins, range, region, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.histogram(vol, bins, range, region, shape=shape)
 
 
 def circular_mask(vol, ratio=1.0, value=0.0, out=None, ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.circular_mask(vol, ratio, value, out, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.circular_mask(vol, ratio, value, out, shape=shape)
 
 
 def quantize(vol, window, dtype=np.uint8, order="zyx", region=None, fill=0, out=None, ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.quantize(vol, window, dtype, order, region, fill, out, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.quantize(vol, window, dtype, order, region, fill, out, shape=shape)
 
 
 def project(vol, axis, op="max", ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.project(vol, axis, op, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.project(vol, axis, op, shape=shape)
 
 
 def slice(vol, axis, index, ctx=None, shape=None):      # noqa: A001  (the builtin is not used in this module)
-    return _with(ctx, vol, lambda p: p.slice(vol, axis, index, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.slice(vol, axis, index, shape=shape)
 
 
 def export_stack(vol, directory, dtype=np.uint8, percentiles=(0.1, 99.9), bins=4096, region="cylinder", previews=True, ctx=None, shape=None):
-    return _with(ctx, vol, lambda p: p.export_stack(vol, directory, dtype, percentiles, bins, region, previews, shape=shape))
+    with PostProcessor(ctx) as p:
+        return p.export_stack(vol, directory, dtype, percentiles, bins, region, previews, shape=shape)

@@ -116,7 +116,7 @@ import numpy as np
 
 from . import _dff_lib, _lbfgsb_batch, _phase_lib, _prep_lib
 from ._dff_lib import DffUnsupported  # noqa: F401  (re-exported)
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, Staging, _is_dev
 from ._prep_lib import PrepUnsupported  # noqa: F401  (re-exported)
 
 DEFAULT_SCRATCH_BYTES = 2 << 30
@@ -392,29 +392,12 @@ class Preprocessor(HandleOwner):
             self._dff = None
         HandleOwner.close(self)
 
-    def _upload(self, a, temps):
-        if _is_dev(a):
-            return a
-        a = np.ascontiguousarray(a)
-        d = self.ctx.to_device(a, a.dtype)
-        temps.append(d)
-        return d
-
-    @staticmethod
-    def _free(temps):
-        for t in temps:
-            t.free()
-        del temps[:]
-
-    def _reference(self, d, shape, dtype, method):
+    def _reference(self, st, d, shape, dtype, method):
+        """The reference frame of the stack d, an array of the staging st."""
         n = 1 if len(shape) == 2 else shape[0]
         rows, cols = shape[-2:]
-        out = self.ctx.empty((rows, cols), np.float32)
-        try:
-            self.handle.reference(self.ctx.stream(), d.ptr, _DTYPES[dtype], n, rows, cols, METHODS[method], out.ptr)
-        except Exception:
-            out.free()
-            raise
+        out = st.scratch((rows, cols))
+        self.handle.reference(self.ctx.stream(), d.ptr, _DTYPES[dtype], n, rows, cols, METHODS[method], out.ptr)
         return out
 
     def _check_reference_args(self, stacks, method):
@@ -436,20 +419,9 @@ class Preprocessor(HandleOwner):
         DeviceArrays when flats is one, ndarrays otherwise."""
         infos = self._check_reference_args(((flats, "flats"), (darks, "darks")), method)
         self._ready(flats)
-        temps, res = [], []
-        try:
-            for a, (shape, dtype) in zip((flats, darks), infos):
-                res.append(self._reference(self._upload(a, temps), shape, dtype, method))
-        except Exception:
-            self._free(res)
-            raise
-        finally:
-            self._free(temps)
-        if _is_dev(flats):
-            return tuple(res)
-        out = tuple(r.download() for r in res)
-        self._free(res)
-        return out
+        with self._staging(flats) as st:
+            res = [self._reference(st, st.source(a, None), shape, dtype, method) for a, (shape, dtype) in zip((flats, darks), infos)]
+            return tuple(st.result(r) for r in res)
 
     def normalize(self, frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6, method="mean", crop=None, out=None):
         """The (n_proj, nx, nz) float32 sinogram of raw frames [n_proj][rows][cols] (module docstring): an ndarray for host frames, a
@@ -468,19 +440,13 @@ class Preprocessor(HandleOwner):
         if out is not None and not (_is_dev(out) and out.dtype == np.float32 and out.size == int(np.prod(oshape))):
             raise ValueError("out must be a float32 DeviceArray of %d values %s" % (int(np.prod(oshape)), oshape))
         self._ready(frames)
-        temps = []
-        try:
-            d_raw = self._upload(frames, temps)
-            d_flat, d_dark = (self._reference(self._upload(a, temps), s, dt, method) for a, (s, dt) in zip((flats, darks), infos))
-            temps += [d_flat, d_dark]
-            res = out if out is not None else self.ctx.empty(oshape, np.float32)
-            if out is None and not _is_dev(frames):
-                temps.append(res)
+        with self._staging(frames) as st:
+            d_raw = st.source(frames, None)
+            d_flat, d_dark = [self._reference(st, st.source(a, None), s, dt, method) for a, (s, dt) in zip((flats, darks), infos)]
+            res = st.dest(oshape, np.float32, out)
             self.handle.normalize(self.ctx.stream(), d_raw.ptr, _DTYPES[dtype], n, rows, cols, d_flat.ptr, d_dark.ptr,
                                   ((z0, z1), (x0, x1)), cutoff, minus_log, min_ratio, res.ptr)
-            return res if _is_dev(frames) else res.download()
-        finally:
-            self._free(temps)
+            return st.result(res)
 
     def _ready_dff(self, like):
         self._ready(like)
@@ -497,36 +463,34 @@ class Preprocessor(HandleOwner):
         _dff_lib.check(K, 0 if n_eff is None else n_eff, shape[-2], shape[-1], bin)
         return infos[0], infos[1], n_eff
 
-    def _eigen_flats(self, flats, darks, infos, n_eff, eig_ratio):
+    def _eigen_flats(self, keep, flats, darks, infos, n_eff, eig_ratio):
+        """The EigenFlats, its three arrays made in the staging `keep` of the caller; the uploads go when they are made."""
         (fshape, fdtype), (dshape, ddtype) = infos
         K, rows, cols = fshape
-        self._ready_dff(flats)
-        st = self.ctx.stream()
-        temps, keep = [], []
-        try:
-            d_flats = self._upload(flats, temps)
-            keep.append(self._reference(d_flats, fshape, fdtype, "mean"))
-            keep.append(self._reference(self._upload(darks, temps), dshape, ddtype, "mean"))
-            lam, V = eigen_decomposition(self._dff.gram(st, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, keep[0].ptr))
+        stream = self.ctx.stream()
+        with self._staging(flats) as st:
+            d_flats = st.source(flats, None)
+            flat = self._reference(keep, d_flats, fshape, fdtype, "mean")
+            dark = self._reference(keep, st.source(darks, None), dshape, ddtype, "mean")
+            lam, V = eigen_decomposition(self._dff.gram(stream, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, flat.ptr))
             m = count_eigen_flats(lam, eig_ratio) if n_eff is None else n_eff
             eff = None
             if m:
-                eff = self.ctx.empty((m, rows, cols), np.float32)
-                keep.append(eff)
-                self._dff.eff(st, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, keep[0].ptr, V[:, :m], eff.ptr)
-            return EigenFlats(keep[0], keep[1], eff, lam, m)
-        except Exception:
-            self._free(keep)
-            raise
-        finally:
-            self._free(temps)
+                eff = keep.scratch((m, rows, cols))
+                self._dff.eff(stream, d_flats.ptr, _DFF_DTYPES[fdtype], K, rows, cols, flat.ptr, V[:, :m], eff.ptr)
+            return EigenFlats(flat, dark, eff, lam, m)
 
     def eigen_flats(self, flats, darks, n_eff=None, eig_ratio=2.0):
         """The EigenFlats (module docstring) of the stacks flats [K][rows][cols] and darks, uint16 or float32, host or device: the mean
         flat, the mean dark and the n_eff leading eigen flat fields, all on the device.  n_eff=None: as many as have an eigenvalue above
         eig_ratio x the median eigenvalue (at most MAX_EFF, possibly 0)."""
         f, d, n_eff = self._check_eigen_args(flats, darks, n_eff, eig_ratio)
-        return self._eigen_flats(flats, darks, (f, d), n_eff, eig_ratio)
+        self._ready_dff(flats)
+        with Staging(self.ctx, True) as keep:                    # the fields stay on the device whatever the flats are
+            ef = self._eigen_flats(keep, flats, darks, (f, d), n_eff, eig_ratio)
+            for a in (ef.flat, ef.dark, ef.eff):
+                keep.result(a)
+            return ef
 
     def _estimate_weights(self, d_raw, dtype, n, rows, cols, ef, m, bin, tv_eps, w_max, budget):
         """((n, m) float64 weights, evaluations): the total-variation minimisation of normalize_dynamic."""
@@ -535,10 +499,8 @@ class Preprocessor(HandleOwner):
         zb, xb = rows // bin, cols // bin
         W, nfev = np.zeros((n, m), np.float64), 0
         h.set_max_scratch(budget)
-        temps = []
-        try:
-            Fb, Eb = self.ctx.empty((zb, xb), np.float32), self.ctx.empty((m, zb, xb), np.float32)
-            temps += [Fb, Eb]
+        with self._staging(d_raw) as scratch:
+            Fb, Eb = scratch.scratch((zb, xb)), scratch.scratch((m, zb, xb))
             h.bin(st, ef.flat.ptr, _dff_lib.F32, 1, rows, cols, bin, ef.dark.ptr, Fb.ptr)
             h.bin(st, ef.eff.ptr, _dff_lib.F32, m, rows, cols, bin, None, Eb.ptr)
             a = np.array([np.mean(Fb.download().astype(np.float64))] + [np.mean(e.astype(np.float64)) for e in Eb.download()], np.float64)
@@ -569,8 +531,6 @@ class Preprocessor(HandleOwner):
                             res = optimize.minimize(fun, np.zeros(m), jac=True, method="L-BFGS-B", bounds=bounds, options=dict(TV_OPTIONS))
                             x[i], nf[i] = res.x, res.nfev
                 W[i0:i0 + cnt], nfev = x, nfev + int(np.sum(nf))
-        finally:
-            self._free(temps)
         return W, nfev
 
     def normalize_dynamic(self, frames, flats, darks=None, n_eff=None, eig_ratio=2.0, bin=2, tv_eps=1e-3, w_max=10.0, weights=None,
@@ -629,32 +589,20 @@ class Preprocessor(HandleOwner):
         if given:
             _dff_lib.check(max(2, flats.n_eff + 1), flats.n_eff, rows, cols, bin)      # the frame and the bin factor
         self._ready_dff(frames)
-        temps, ef, res = [], None, None
-        try:
-            d_raw = self._upload(frames, temps)
-            ef = flats if given else self._eigen_flats(flats, darks, infos, n_eff, eig_ratio)
+        with self._staging(frames) as st:
+            d_raw = st.source(frames, None)
+            ef = flats if given else self._eigen_flats(st, flats, darks, infos, n_eff, eig_ratio)      # its fields go with this call
             m = ef.n_eff if n_eff is None else n_eff
             nfev = 0
             if weights is None:
                 weights = np.zeros((n, m), np.float64)
                 if m:
                     weights, nfev = self._estimate_weights(d_raw, dtype, n, rows, cols, ef, m, int(bin), tv_eps, w_max, budget)
-            res = out if out is not None else self.ctx.empty(oshape, np.float32)
+            res = st.dest(oshape, np.float32, out)
             self._dff.apply(self.ctx.stream(), d_raw.ptr, _DFF_DTYPES[dtype], n, rows, cols, ef.flat.ptr, ef.dark.ptr,
                             None if not m else ef.eff.ptr, weights.astype(np.float32).reshape(n, m), ((z0, z1), (x0, x1)), cutoff, minus_log,
                             min_ratio, res.ptr)
-            result = res if _is_dev(frames) else res.download()
-        except Exception:
-            if res is not None and out is None:
-                res.free()
-            raise
-        else:
-            if out is None and not _is_dev(frames):
-                res.free()
-        finally:
-            self._free(temps)
-            if ef is not None and not given:
-                ef.free()
+            result = st.result(res)
         return (result, weights, nfev) if return_weights else result
 
     def remove_stripe_sorting(self, proj, size=21, out=None, max_scratch_bytes=None, timed=False):
@@ -681,51 +629,24 @@ class Preprocessor(HandleOwner):
                 if a0 < b0 + out.nbytes and b0 < a0 + proj.nbytes:
                     raise ValueError("out must be proj itself or not overlap it")
         self._ready(proj)
-        temps = []
-        try:
-            d_in = self._upload(proj, temps)
-            res = out
-            if res is None:
-                res = self.ctx.empty(shape, np.float32)
-                if not _is_dev(proj):
-                    temps.append(res)
-            try:
-                ms = self.handle.stripe_sorting(self.ctx.stream(), d_in.ptr, res.ptr, n, nx, nz, size, budget, timed)
-            except Exception:
-                if out is None:
-                    res.free()
-                raise
-            result = res if _is_dev(proj) else res.download()
-        finally:
-            self._free(temps)
+        with self._staging(proj) as st:
+            d_in = st.source(proj)
+            res = st.dest(shape, np.float32, out)
+            ms = self.handle.stripe_sorting(self.ctx.stream(), d_in.ptr, res.ptr, n, nx, nz, size, budget, timed)
+            result = st.result(res)
         return (result, ms) if timed else result
 
     def _run_stripe(self, proj, shape, out, n_masks, call):
         """Upload / allocate as remove_stripe_sorting does, run call(d_in, d_out, masks) with n_masks zeroed uint8 (nx, nz) device
         buffers, and return (result, mask, ...) with the masks as boolean ndarrays."""
         self._ready(proj)
-        temps = []
-        try:
-            d_in = self._upload(proj, temps)
-            res = out
-            if res is None:
-                res = self.ctx.empty(shape, np.float32)
-                if not _is_dev(proj):
-                    temps.append(res)
-            try:
-                masks = []
-                for _ in range(n_masks):
-                    masks.append(self.ctx.zeros(shape[1:], np.uint8))
-                    temps.append(masks[-1])
-                call(d_in, res, [m.ptr for m in masks])
-                host_masks = tuple(m.download().astype(bool) for m in masks)
-            except Exception:
-                if out is None and _is_dev(proj):
-                    res.free()
-                raise
-            result = res if _is_dev(proj) else res.download()
-        finally:
-            self._free(temps)
+        with self._staging(proj) as st:
+            d_in = st.source(proj)
+            res = st.dest(shape, np.float32, out)
+            masks = [st.scratch(shape[1:], np.uint8, zero=True) for _ in range(n_masks)]
+            call(d_in, res, [m.ptr for m in masks])
+            host_masks = tuple(m.download().astype(bool) for m in masks)
+            result = st.result(res)
         return (result,) + host_masks if n_masks else result
 
     def remove_large_stripe(self, proj, snr=3.0, size=51, drop_ratio=0.1, norm=True, out=None, max_scratch_bytes=None, return_mask=False):
@@ -775,27 +696,14 @@ class Preprocessor(HandleOwner):
         """Upload / allocate as the conventions say (a host input's upload is filtered in place), enqueue, download a host input's result."""
         (n, rows, cols), dtype, size, budget = info
         self._ready(frames)
-        temps = []
-        try:
-            d_in = self._upload(frames, temps)
-            res = out
-            if res is None:
-                res = d_in if not _is_dev(frames) else self.ctx.empty(tuple(frames.shape), dtype)
-            try:
-                d_count = None
-                if return_count:
-                    d_count = self.ctx.empty((n,), np.uint32)
-                    temps.append(d_count)
-                self.handle.outlier(self.ctx.stream(), d_in.ptr, res.ptr, _DTYPES[dtype], n, rows, cols, size, mode, dif, two_sided, budget,
-                                    None if d_count is None else d_count.ptr)
-                counts = d_count.download().astype(np.int64) if return_count else None
-            except Exception:
-                if out is None and res is not d_in:
-                    res.free()
-                raise
-            result = res if _is_dev(frames) else res.download().reshape(np.shape(frames))
-        finally:
-            self._free(temps)
+        with self._staging(frames) as st:
+            d_in = st.source(frames, dtype)
+            res = st.dest(np.shape(frames), dtype, out, inplace=d_in)      # a host input's upload is filtered in place
+            d_count = st.scratch((n,), np.uint32) if return_count else None
+            self.handle.outlier(self.ctx.stream(), d_in.ptr, res.ptr, _DTYPES[dtype], n, rows, cols, size, mode, dif, two_sided, budget,
+                                None if d_count is None else d_count.ptr)
+            counts = d_count.download().astype(np.int64) if return_count else None
+            result = st.result(res, shape=np.shape(frames))
         return (result, counts) if return_count else result
 
     def remove_outlier(self, frames, dif, size=3, two_sided=False, out=None, max_scratch_bytes=None, return_count=False):
@@ -821,21 +729,11 @@ class Preprocessor(HandleOwner):
     def _run_phase(self, proj, shape, out, call):
         """Upload / allocate as the conventions say, run call(d_in, d_out), download a host input's result."""
         self._ready_phase(proj)
-        temps = []
-        try:
-            d_in = self._upload(proj, temps)
-            res = out
-            if res is None:
-                res = d_in if not _is_dev(proj) else self.ctx.empty(shape, np.float32)     # a host input's upload is ours: in place
-            try:
-                extra = call(d_in, res)
-            except Exception:
-                if out is None and res is not d_in:
-                    res.free()
-                raise
-            return (res if _is_dev(proj) else res.download()), extra
-        finally:
-            self._free(temps)
+        with self._staging(proj) as st:
+            d_in = st.source(proj)
+            res = st.dest(shape, np.float32, out, inplace=d_in)      # a host input's upload is ours: in place
+            extra = call(d_in, res)
+            return st.result(res), extra
 
     def retrieve_phase(self, proj, strength=None, *, pixel_size=None, dist=None, energy=None, wavelength=None, delta_beta=None, pad=None,
                        minus_log=True, min_ratio=1e-6, out=None, max_scratch_bytes=None, timed=False):
@@ -900,20 +798,14 @@ class Preprocessor(HandleOwner):
 
 def reference_frames(flats, darks, method="mean", ctx=None):
     """(flat, dark) float32 reference frames: Preprocessor.reference_frames on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.reference_frames(flats, darks, method)
-    finally:
-        p.close()
 
 
 def normalize(frames, flats, darks, cutoff=None, minus_log=True, min_ratio=1e-6, method="mean", crop=None, ctx=None, out=None):
     """The (n_proj, nx, nz) sinogram of raw frames: Preprocessor.normalize on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.normalize(frames, flats, darks, cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, method=method, crop=crop, out=out)
-    finally:
-        p.close()
 
 
 def eigen_flats(flats, darks, n_eff=None, eig_ratio=2.0, ctx=None):
@@ -921,11 +813,8 @@ def eigen_flats(flats, darks, n_eff=None, eig_ratio=2.0, ctx=None):
     one: to the context of device flats), which must outlive them."""
     if ctx is None and not _is_dev(flats):
         raise ValueError("eigen_flats: the EigenFlats lives on the device, so host flats need a ctx that outlives it")
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.eigen_flats(flats, darks, n_eff=n_eff, eig_ratio=eig_ratio)
-    finally:
-        p.close()
 
 
 def normalize_dynamic(frames, flats, darks=None, n_eff=None, eig_ratio=2.0, bin=2, tv_eps=1e-3, w_max=10.0, weights=None, cutoff=None,
@@ -933,86 +822,59 @@ def normalize_dynamic(frames, flats, darks=None, n_eff=None, eig_ratio=2.0, bin=
     """The sinogram of raw frames with a flat per projection: Preprocessor.normalize_dynamic on a handle of its own."""
     if ctx is None and isinstance(flats, EigenFlats) and flats.flat is not None:
         ctx = flats.flat.ctx
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.normalize_dynamic(frames, flats, darks, n_eff=n_eff, eig_ratio=eig_ratio, bin=bin, tv_eps=tv_eps, w_max=w_max, weights=weights,
                                    cutoff=cutoff, minus_log=minus_log, min_ratio=min_ratio, crop=crop, out=out,
                                    max_scratch_bytes=max_scratch_bytes, return_weights=return_weights)
-    finally:
-        p.close()
 
 
 def remove_outlier(frames, dif, size=3, two_sided=False, ctx=None, out=None, max_scratch_bytes=None, return_count=False):
     """Zinger removal: Preprocessor.remove_outlier on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.remove_outlier(frames, dif, size=size, two_sided=two_sided, out=out, max_scratch_bytes=max_scratch_bytes,
                                 return_count=return_count)
-    finally:
-        p.close()
 
 
 def median_filter(frames, size=3, ctx=None, out=None, max_scratch_bytes=None):
     """The 2-D median filter: Preprocessor.median_filter on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.median_filter(frames, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
-    finally:
-        p.close()
 
 
 def remove_stripe_sorting(proj, size=21, ctx=None, out=None, max_scratch_bytes=None):
     """Sorting-based stripe removal: Preprocessor.remove_stripe_sorting on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.remove_stripe_sorting(proj, size=size, out=out, max_scratch_bytes=max_scratch_bytes)
-    finally:
-        p.close()
 
 
 def remove_large_stripe(proj, snr=3.0, size=51, drop_ratio=0.1, norm=True, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
     """Large-stripe removal: Preprocessor.remove_large_stripe on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.remove_large_stripe(proj, snr=snr, size=size, drop_ratio=drop_ratio, norm=norm, out=out,
                                      max_scratch_bytes=max_scratch_bytes, return_mask=return_mask)
-    finally:
-        p.close()
 
 
 def remove_dead_stripe(proj, snr=3.0, size=51, norm=True, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
     """Dead-stripe removal: Preprocessor.remove_dead_stripe on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.remove_dead_stripe(proj, snr=snr, size=size, norm=norm, out=out, max_scratch_bytes=max_scratch_bytes,
                                     return_mask=return_mask)
-    finally:
-        p.close()
 
 
 def remove_all_stripe(proj, snr=3.0, la_size=61, sm_size=21, ctx=None, out=None, max_scratch_bytes=None, return_mask=False):
     """Dead, large and sorting-based stripe removal: Preprocessor.remove_all_stripe on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.remove_all_stripe(proj, snr=snr, la_size=la_size, sm_size=sm_size, out=out, max_scratch_bytes=max_scratch_bytes,
                                    return_mask=return_mask)
-    finally:
-        p.close()
 
 
 def retrieve_phase(proj, strength=None, ctx=None, **kwargs):
     """Paganin phase retrieval: Preprocessor.retrieve_phase (same keywords) on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.retrieve_phase(proj, strength, **kwargs)
-    finally:
-        p.close()
 
 
 def minus_log(proj, min_ratio=1e-6, ctx=None, out=None):
     """-log(fmax(proj, min_ratio)): Preprocessor.minus_log on a handle of its own."""
-    p = Preprocessor(ctx)
-    try:
+    with Preprocessor(ctx) as p:
         return p.minus_log(proj, min_ratio=min_ratio, out=out)
-    finally:
-        p.close()

@@ -31,7 +31,7 @@ or spline resampling.
 import numpy as np
 
 from . import _vreg_lib
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, Staging, _is_dev, shape_of
 from ._vreg_lib import VregUnsupported  # noqa: F401  (re-exported)
 
 NORMALIZATIONS = {None: _vreg_lib.NORM_NONE, "phase": _vreg_lib.NORM_PHASE}
@@ -68,15 +68,7 @@ class Registration(object):
 
 
 def _shape_of(a, shape, what):
-    own = tuple(a.shape) if _is_dev(a) else np.shape(a)
-    shape = tuple(int(v) for v in (own if shape is None else shape))
-    if len(shape) != 3:
-        raise ValueError("%s must have 3 dimensions (give `shape` for a flat buffer), got shape %s" % (what, shape))
-    if int(np.prod(shape)) != int(np.prod(own)):
-        raise ValueError("%s holds %d values, not the %d of shape %s" % (what, int(np.prod(own)), int(np.prod(shape)), shape))
-    if _is_dev(a) and np.dtype(a.dtype) != np.float32:
-        raise ValueError("%s must be float32 on the device, got %s" % (what, a.dtype))
-    return shape
+    return shape_of(a, shape, 3, what)
 
 
 def _mask_args(mask, edge, radius, shape):
@@ -115,13 +107,6 @@ class Registrar(HandleOwner):
     def device_bytes(self):
         return 0 if self.handle is None else self.handle.device_bytes()
 
-    def _device(self, v, tmp):
-        if _is_dev(v):
-            return v
-        d = self.ctx.to_device(np.ascontiguousarray(v, np.float32), np.float32)
-        tmp.append(d)
-        return d
-
     def register(self, ref, mov, upsample=10, normalization=None, mask="sphere", edge=6, radius=None, subtract_mean=True, passes=1,
                  shape=None):
         """The translation that moves `mov` onto `ref` (module docstring) -> Registration.
@@ -145,19 +130,16 @@ class Registrar(HandleOwner):
         mode, radius, edge = _mask_args(mask, edge, radius, sa)
         self._ready(ref if _is_dev(ref) else mov)
         ctx, h = self.ctx, self.handle
-        tmp = []
-        try:
-            d_mask = self._device(mask, tmp) if mode == _vreg_lib.MASK_ARRAY else None
-            m_ptr = None if d_mask is None else d_mask.ptr
-            d_ref, d_mov = self._device(ref, tmp), self._device(mov, tmp)
+        with self._staging(ref) as staging:
+            m_ptr = staging.source(mask).ptr if mode == _vreg_lib.MASK_ARRAY else None
+            d_ref, d_mov = staging.source(ref), staging.source(mov)
             h.set_shape(*sa)
             st = ctx.stream()
             total, first, d_cur = np.zeros(3), None, d_mov
             for p in range(passes):
                 if p > 0:
                     if d_cur is d_mov:
-                        d_cur = ctx.empty((int(np.prod(sa)),), np.float32)
-                        tmp.append(d_cur)
+                        d_cur = staging.scratch((int(np.prod(sa)),))
                     h.shift(st, d_mov.ptr, total, d_cur.ptr)
                 h.prepare(st, 0, d_ref.ptr, mode, m_ptr, radius, edge, subtract_mean)
                 h.prepare(st, 1, d_cur.ptr, mode, m_ptr, radius, edge, subtract_mean)
@@ -171,9 +153,6 @@ class Registrar(HandleOwner):
                     first = np.unravel_index(int(out[6]), sa)
             coarse = [int(i) if i <= n // 2 else int(i) - n for i, n in zip(first, sa)]
             return Registration(total, out[3], out[4], out[5], coarse, upsample, passes, normalization)
-        finally:
-            for t in tmp:
-                t.free()
 
     def shift_volume(self, vol, shift, out=None, shape=None):
         """`vol` moved by `shift` voxels (module docstring), periodic -> a device array of the volume's shape, `out` if given (a float32
@@ -184,16 +163,12 @@ class Registrar(HandleOwner):
         if out is not None and not (_is_dev(out) and np.dtype(out.dtype) == np.float32 and out.size == int(np.prod(sv))):
             raise ValueError("out must be a float32 device array of %d values" % int(np.prod(sv)))
         self._ready(vol if _is_dev(vol) else out)
-        tmp = []
-        try:
-            d_v = self._device(vol, tmp)
-            d_out = self.ctx.empty(sv, np.float32) if out is None else out
+        with Staging(self.ctx, True) as st:                      # the result stays on the device whatever `vol` is
+            d_v = st.source(vol)
+            d_out = st.dest(sv, np.float32, out)
             self.handle.set_shape(*sv)
             self.handle.shift(self.ctx.stream(), d_v.ptr, s, d_out.ptr)
-            return d_out
-        finally:
-            for t in tmp:
-                t.free()
+            return st.result(d_out)
 
     def argmax(self, vol, shape=None):
         """(index, value) of the largest element of a volume, index a tuple of three ints: NaN never wins, a tie goes to the smallest
@@ -201,15 +176,11 @@ class Registrar(HandleOwner):
         sv = _shape_of(vol, shape, "vol")
         _vreg_lib.check(*sv)
         self._ready(vol)
-        tmp = []
-        try:
-            d_v = self._device(vol, tmp)
+        with self._staging(vol) as st:
+            d_v = st.source(vol)
             self.handle.set_shape(*sv)
             i, v = self.handle.argmax(self.ctx.stream(), d_v.ptr)
             return tuple(int(j) for j in np.unravel_index(i, sv)), v
-        finally:
-            for t in tmp:
-                t.free()
 
 
 def register(ref, mov, upsample=10, normalization=None, mask="sphere", edge=6, radius=None, subtract_mean=True, passes=1, ctx=None,
@@ -225,11 +196,7 @@ def shift_volume(vol, shift, out=None, ctx=None, shape=None):
     array, because a device array does not outlive its context."""
     with Registrar(ctx) as r:
         d = r.shift_volume(vol, shift, out=out, shape=shape)
-        if r._own_ctx is not None:
-            host = d.download()
-            d.free()
-            return host
-        return d
+        return d if r._own_ctx is None else d.download()         # the context closes on the way out and frees d
 
 
 def argmax(vol, ctx=None, shape=None):

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import _fsc_lib
 from ._fsc_lib import FscUnsupported  # noqa: F401  (re-exported)
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, _is_dev, shape_of as _shape_of
 from .recon import fbp, sirt, sirt_mpi
 
 THRESHOLDS = ("half-bit", "one-bit", "0.143", "0.5")
@@ -145,18 +145,6 @@ def half_weights(phi, parity):
     return fbp.angle_weights(np.asarray(phi, np.float64).ravel()[parity::2])
 
 
-def _shape_of(a, shape, ndim, what):
-    own = tuple(a.shape) if _is_dev(a) else np.shape(a)
-    shape = tuple(int(v) for v in (own if shape is None else shape))
-    if len(shape) != ndim:
-        raise ValueError("%s must have %d dimensions (give `shape` for a flat buffer), got shape %s" % (what, ndim, shape))
-    if int(np.prod(shape)) != int(np.prod(own)):
-        raise ValueError("%s holds %d values, not the %d of shape %s" % (what, int(np.prod(own)), int(np.prod(shape)), shape))
-    if _is_dev(a) and np.dtype(a.dtype) != np.float32:
-        raise ValueError("%s must be float32 on the device, got %s" % (what, a.dtype))
-    return shape
-
-
 class Resolution(HandleOwner):
     """One libtomo_fsc handle and its hipFFT plans reused across calls.  ctx: the _lib.Context whose device and stream the work uses
     (default: that of the first DeviceArray passed in, or a context of the handle's own)."""
@@ -180,7 +168,7 @@ class Resolution(HandleOwner):
         _fsc_lib.n_shells(ndim, nb, nx, ny, nz)                  # FscUnsupported before a context, a handle or a launch
         mshape = (nx, ny, nz) if ndim == 3 else (nx, nz)
         axes = mshape
-        mode, d_mask, tmp = _fsc_lib.MASK_NONE, None, []
+        mode = _fsc_lib.MASK_NONE
         edge = float(edge)
         if isinstance(mask, str):
             if mask != "sphere":
@@ -197,26 +185,15 @@ class Resolution(HandleOwner):
                 raise ValueError("mask must have the shape %s" % (mshape,))
         self._ready(a if _is_dev(a) else b)
         ctx, h = self.ctx, self.handle
-        try:
-            if mode == _fsc_lib.MASK_ARRAY:
-                d_mask = mask
-                if not _is_dev(mask):
-                    d_mask = ctx.to_device(np.ascontiguousarray(mask, np.float32), np.float32)
-                    tmp.append(d_mask)
+        with self._staging(a) as staging:
+            m_ptr = staging.source(mask).ptr if mode == _fsc_lib.MASK_ARRAY else None
             h.set_shape(ndim, nb, nx, ny, nz)
             st = ctx.stream()
             for slot, v in enumerate((a, b)):
-                d_v = v
-                if not _is_dev(v):
-                    d_v = ctx.to_device(np.ascontiguousarray(v, np.float32), np.float32)
-                    tmp.append(d_v)
-                h.prepare(st, slot, d_v.ptr, mode, None if d_mask is None else d_mask.ptr, radius or 0.0, edge, subtract_mean)
+                h.prepare(st, slot, staging.source(v).ptr, mode, m_ptr, radius or 0.0, edge, subtract_mean)
                 h.fft(st, slot)
             h.reduce(st)
             return h.fetch(st)
-        finally:
-            for t in tmp:
-                t.free()
 
     def fsc(self, vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, shape=None, register=False,
             upsample=10):
@@ -233,21 +210,13 @@ class Resolution(HandleOwner):
             raise ValueError("the two inputs must have one shape, got %s and %s" % (sv, _shape_of(vol_b, shape, 3, "vol_b")))
         _fsc_lib.n_shells(3, 1, *sv)
         self._ready_ctx(vol_a if _is_dev(vol_a) else vol_b)
-        tmp = []
-        try:
-            d_a, d_b = vol_a, vol_b
-            if not _is_dev(vol_b):
-                d_b = self.ctx.to_device(np.ascontiguousarray(vol_b, np.float32), np.float32)
-                tmp.append(d_b)
+        with self._staging(vol_b) as st:
+            d_b = st.source(vol_b)
             with registration.Registrar(self.ctx) as rg:
-                reg = rg.register(d_a, d_b, upsample=upsample, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean, passes=2,
+                reg = rg.register(vol_a, d_b, upsample=upsample, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean, passes=2,
                                   shape=sv)
-                d_s = rg.shift_volume(d_b, reg.shift, shape=sv)
-            tmp.append(d_s)
-            t = self.shell_sums(d_a, d_s, 3, shape=sv, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean)[0]
-        finally:
-            for d in tmp:
-                d.free()
+                d_s = rg.shift_volume(d_b, reg.shift, out=st.scratch(sv), shape=sv)
+            t = self.shell_sums(vol_a, d_s, 3, shape=sv, mask=mask, edge=edge, radius=radius, subtract_mean=subtract_mean)[0]
         curve = FSCCurve(t[0], t[1], t[2], t[3], max(sv), voxel_size)
         curve.shift = tuple(float(v) for v in reg.shift)
         return curve
@@ -266,9 +235,10 @@ class Resolution(HandleOwner):
         count, row_elems = int(count), int(row_elems)
         if count and int(first) + (count - 1) * int(step) >= d_src.size // row_elems:
             raise ValueError("take_rows: the rows asked for are not in the buffer")
-        out = self.ctx.empty((count * row_elems,), np.float32)
-        self.handle.take_rows(self.ctx.stream(), d_src.ptr, row_elems, first, step, count, out.ptr)
-        return out
+        with self._staging(d_src) as st:
+            out = st.dest((count * row_elems,))
+            self.handle.take_rows(self.ctx.stream(), d_src.ptr, row_elems, first, step, count, out.ptr)
+            return st.result(out)
 
 
 def fsc(vol_a, vol_b, voxel_size=1.0, mask="sphere", edge=6, radius=None, subtract_mean=True, ctx=None, shape=None, register=False,

@@ -36,7 +36,7 @@ import numpy as np
 
 from . import _cor_lib
 from ._cor_lib import CorUnsupported  # noqa: F401  (re-exported)
-from ._ops import HandleOwner, _is_dev
+from ._ops import HandleOwner, _is_dev, stack_shape
 
 DEFAULT_SCRATCH = 2 << 30
 
@@ -144,15 +144,7 @@ class RotationAxis(HandleOwner):
     def load(self, proj, angles=None, rows=None, shape=None, timed=False):
         """Gather and prefilter the detector rows `rows` (default the middle one) of proj (n, nx, nz); returns (rows, n used, nx)
         (and the pass times with `timed`)."""
-        own = tuple(proj.shape) if _is_dev(proj) else np.shape(proj)
-        shape = tuple(int(v) for v in (own if shape is None else shape))
-        if len(shape) != 3:
-            raise ValueError("find_center: proj must be (n, nx, nz) (give `shape` for a flat device buffer), got shape %s" % (shape,))
-        if int(np.prod(shape)) != int(np.prod(own)):
-            raise ValueError("find_center: proj holds %d values, not the %d of shape %s" % (int(np.prod(own)), int(np.prod(shape)), shape))
-        if _is_dev(proj) and np.dtype(proj.dtype) != np.float32:
-            raise ValueError("find_center: proj must be float32 on the device, got %s" % proj.dtype)
-        n_p, nx, nz = shape
+        n_p, nx, nz = stack_shape(proj, shape, "find_center")
         n = angle_span(angles, n_p)
         rows = np.array([nz // 2] if rows is None else rows, np.int64).ravel()
         if rows.size < 1 or rows.min() < 0 or rows.max() >= nz:
@@ -162,19 +154,12 @@ class RotationAxis(HandleOwner):
         _cor_lib.check_shape(n, nx, rows.size)                      # CorUnsupported before a context, a handle or a launch
         self._ready(proj)
         ctx, h = self.ctx, self.handle
-        tmp = None
-        try:
-            if _is_dev(proj):
-                d_p, nz_d, rows_d = proj, nz, rows
-            else:                                                    # only the rows searched are uploaded
-                host = np.ascontiguousarray(np.asarray(proj, np.float32)[:n, :, rows])
-                d_p = tmp = ctx.to_device(host, np.float32)
-                nz_d, rows_d, n_p = rows.size, np.arange(rows.size), n
-            ms = h.load_rows(ctx.stream(), d_p.ptr, n_p, nx, nz_d, 0, n, rows_d, timed=timed)
-        finally:
-            if tmp is not None:
-                ctx.sync()                                           # the gather reads it
-                tmp.free()
+        with self._staging(proj) as st:
+            src, nz_d, rows_d = proj, nz, rows
+            if not st.dev:                                           # only the rows searched are uploaded
+                src, nz_d, rows_d, n_p = np.asarray(proj, np.float32)[:n, :, rows], rows.size, np.arange(rows.size), n
+            d_p = st.source(src)
+            ms = h.load_rows(ctx.stream(), d_p.ptr, n_p, nx, nz_d, 0, n, rows_d, timed=timed)      # the gather reads the upload: its free waits
         return (rows, n, nx, ms) if timed else (rows, n, nx)
 
     def metric(self, slices, ts, ratio=0.5, drop=20, max_scratch_bytes=DEFAULT_SCRATCH, timed=False):

@@ -87,15 +87,7 @@ class Components(object):
                 for k in order]
 
 
-def _shape3(a, shape, dtypes, what):
-    s = tuple(int(n) for n in (shape if shape is not None else a.shape))
-    if len(s) != 3:
-        raise ValueError("%s: need a 3-D array [nx][ny][nz], not shape %r (a flat DeviceArray: pass shape=)" % (what, s))
-    if int(np.prod(s, dtype=np.int64)) != int(a.size):
-        raise ValueError("%s: shape %r does not hold %d elements" % (what, s, a.size))
-    if np.dtype(a.dtype) not in [np.dtype(d) for d in dtypes]:
-        raise ValueError("%s: need %s, not %s" % (what, " or ".join(np.dtype(d).name for d in dtypes), a.dtype))
-    return s
+_shape3 = _ops.volume_shape
 
 
 def _count(n, what):
@@ -139,21 +131,6 @@ class Segmenter(_ops.HandleOwner):
     def device_bytes(self):
         return 0 if self.handle is None else self.handle.device_bytes()
 
-    # ---- plumbing
-    def _up(self, a, dtype):
-        """-> (a on the device, whether that is a temporary upload)."""
-        if _ops._is_dev(a):
-            return a, False
-        return self.ctx.to_device(a, dtype), True
-
-    def _down(self, dev, d_out, out, s):
-        """A device result stays; a host input's result comes down (into `out`) and its device array goes."""
-        if dev:
-            return d_out
-        host = d_out.download(out.reshape(s) if out is not None else None)
-        d_out.free()
-        return host if out is None else out
-
     # ---- the operations
     def otsu(self, vol, classes=2, bins=4096, range=None, region=None, shape=None):
         """otsu_threshold of the histogram of `vol` over `region`, taken on the device (postprocess.histogram)."""
@@ -178,21 +155,12 @@ class Segmenter(_ops.HandleOwner):
         _check_out(out, vol, np.uint8, "threshold")
         _seg_lib.check_shape(*s)
         self._ready(vol)
-        dev = _ops._is_dev(vol)
-        d, tmp = self._up(vol, np.float32)
-        d_out = None
-        try:
-            d_out = out if (dev and out is not None) else self.ctx.empty(s, np.uint8)
+        with self._staging(vol) as st:
+            d = st.source(vol)
+            d_out = st.dest(s, np.uint8, out)
             self.handle.threshold(self.ctx.stream(), d.ptr, s[0], s[1], s[2], r4, None if lo is None else np.float32(lo),
                                   None if hi is None else np.float32(hi), d_out.ptr)
-            return self._down(dev, d_out, out, s)
-        except Exception:
-            if d_out is not None and d_out is not out:
-                d_out.free()
-            raise
-        finally:
-            if tmp:
-                d.free()
+            return st.result(d_out, out)
 
     def label(self, mask, connectivity=1, out=None, shape=None):
         """-> (labels int32, n).  mask: uint8 or bool, non-zero is foreground.  connectivity 1, 2, 3: 6, 18, 26 neighbours."""
@@ -202,20 +170,11 @@ class Segmenter(_ops.HandleOwner):
         _check_out(out, mask, np.int32, "label")
         _seg_lib.check_shape(*s)
         self._ready(mask)
-        dev = _ops._is_dev(mask)
-        d, tmp = self._up(mask, np.uint8)
-        d_out = None
-        try:
-            d_out = out if (dev and out is not None) else self.ctx.empty(s, np.int32)
+        with self._staging(mask) as st:
+            d = st.source(mask, np.uint8)
+            d_out = st.dest(s, np.int32, out)
             n = self.handle.label(self.ctx.stream(), d.ptr, s[0], s[1], s[2], int(connectivity), d_out.ptr)
-            return self._down(dev, d_out, out, s), n
-        except Exception:
-            if d_out is not None and d_out is not out:
-                d_out.free()
-            raise
-        finally:
-            if tmp:
-                d.free()
+            return st.result(d_out, out), n
 
     def measure(self, labels, n, vol=None, shape=None):
         """-> Components over 1 ... n.  vol: None, or the float32 volume of the same shape and kind (host or device) as labels."""
@@ -232,15 +191,10 @@ class Segmenter(_ops.HandleOwner):
             return Components(np.zeros(0, np.int64), np.zeros((0, 6), np.int32), np.zeros((0, 3), np.int64),
                               *((e, e.copy(), np.zeros(0, np.float64)) if vol is not None else ()))
         self._ready(labels)
-        d, tmp = self._up(labels, np.int32)
-        d_v, tmp_v = (None, False) if vol is None else self._up(vol, np.float32)
-        try:
-            return Components(*self.handle.measure(self.ctx.stream(), d.ptr, None if d_v is None else d_v.ptr, s[0], s[1], s[2], n))
-        finally:
-            if tmp:
-                d.free()
-            if tmp_v:
-                d_v.free()
+        with self._staging(labels) as st:
+            d = st.source(labels, np.int32)
+            v_ptr = None if vol is None else st.source(vol).ptr
+            return Components(*self.handle.measure(self.ctx.stream(), d.ptr, v_ptr, s[0], s[1], s[2], n))
 
     def remove_small(self, labels, n, min_size, out=None, shape=None):
         """-> (labels, n_kept): components of fewer than min_size voxels become 0, the others 1 ... n_kept in their order.  out may be
@@ -250,23 +204,11 @@ class Segmenter(_ops.HandleOwner):
         _check_out(out, labels, np.int32, "remove_small")
         _seg_lib.check_shape(*s)
         self._ready(labels)
-        dev = _ops._is_dev(labels)
-        d, tmp = self._up(labels, np.int32)
-        d_out = None
-        try:
-            d_out = d if tmp else (out if out is not None else self.ctx.empty(s, np.int32))      # a temporary upload: in place
+        with self._staging(labels) as st:
+            d = st.source(labels, np.int32)
+            d_out = st.dest(s, np.int32, out, inplace=d)         # a temporary upload: in place
             kept = self.handle.remove_small(self.ctx.stream(), d.ptr, s[0], s[1], s[2], n, min_size, d_out.ptr)
-            if dev:
-                return d_out, kept
-            host = d_out.download(out.reshape(s) if out is not None else None)
-            return (host.reshape(s) if out is None else out), kept
-        except Exception:
-            if dev and d_out is not None and d_out is not out:
-                d_out.free()
-            raise
-        finally:
-            if tmp:
-                d.free()
+            return st.result(d_out, out, s), kept
 
     def largest(self, labels, n, shape=None):
         """-> the uint8 mask of the component with the most voxels, the lowest label among equals; all zeros when n = 0."""
@@ -274,18 +216,11 @@ class Segmenter(_ops.HandleOwner):
         n = _count(n, "largest: n")
         _seg_lib.check_shape(*s)
         self._ready(labels)
-        dev = _ops._is_dev(labels)
-        d, tmp = self._up(labels, np.int32)
-        d_out = self.ctx.empty(s, np.uint8)
-        try:
+        with self._staging(labels) as st:
+            d = st.source(labels, np.int32)
+            d_out = st.dest(s, np.uint8)
             self.handle.largest(self.ctx.stream(), d.ptr, s[0], s[1], s[2], n, d_out.ptr)
-            return self._down(dev, d_out, None, s)
-        except Exception:
-            d_out.free()
-            raise
-        finally:
-            if tmp:
-                d.free()
+            return st.result(d_out)
 
 
 def check_shape(nx, ny, nz):
@@ -293,28 +228,26 @@ def check_shape(nx, ny, nz):
     _seg_lib.check_shape(nx, ny, nz)
 
 
-def _with(ctx, like, fn):
-    if ctx is None and _ops._is_dev(like):
-        ctx = like.ctx
-    with Segmenter(ctx) as s:
-        return fn(s)
-
-
 def threshold(vol, lo=None, hi=None, region=None, out=None, ctx=None, shape=None):
-    return _with(ctx, vol, lambda s: s.threshold(vol, lo, hi, region, out, shape=shape))
+    with Segmenter(ctx) as s:                                # without a ctx: a device array's (_ops.HandleOwner)
+        return s.threshold(vol, lo, hi, region, out, shape=shape)
 
 
 def label(mask, connectivity=1, out=None, ctx=None, shape=None):
-    return _with(ctx, mask, lambda s: s.label(mask, connectivity, out, shape=shape))
+    with Segmenter(ctx) as s:
+        return s.label(mask, connectivity, out, shape=shape)
 
 
 def measure(labels, n, vol=None, ctx=None, shape=None):
-    return _with(ctx, labels, lambda s: s.measure(labels, n, vol, shape=shape))
+    with Segmenter(ctx) as s:
+        return s.measure(labels, n, vol, shape=shape)
 
 
 def remove_small(labels, n, min_size, out=None, ctx=None, shape=None):
-    return _with(ctx, labels, lambda s: s.remove_small(labels, n, min_size, out, shape=shape))
+    with Segmenter(ctx) as s:
+        return s.remove_small(labels, n, min_size, out, shape=shape)
 
 
 def largest(labels, n, ctx=None, shape=None):
-    return _with(ctx, labels, lambda s: s.largest(labels, n, shape=shape))
+    with Segmenter(ctx) as s:
+        return s.largest(labels, n, shape=shape)
