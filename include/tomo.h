@@ -118,6 +118,12 @@ TOMO_API int tomo_sync(tomo_ctx *ctx);
  *                 (|cos phi| + |sin phi|) / step < 2.99.  Detector-x pitch = step = voxel meets both at any phi (sum <= sqrt 2); so does
  *                 every COARSER detector (pitch 1.25, 2, ...).  A finer one qualifies per pose: at det_dx = 0.8 only within 10 degrees of
  *                 an axis, so one call can run both kernels; at det_dx < 0.69 never
+ *   "adj_gather_dma" 1 (default): a gather adjoint launch loads its sinogram rows straight into LDS (buffer_load ... lds into two row
+ *                 buffers in turn; no staging stores, 13 rows per projection instead of 14) when its samples sit on detector rows exactly
+ *                 in every pose (integer z offsets: tau == 0), three samples per row suffice ((|cos phi| + |sin phi|) / step < 1.49) and
+ *                 (|cos phi| + |sin phi|) / det_dx < 1.427 in every pose -- the nominal scan; waves whose 64 planes can leave the detector
+ *                 keep the register loop inside that launch.  Other launches, and value 0: rows through registers.  Same sums, same bits.
+ *                 Profiled as "k_adj_gather_flat(dma)" (tomo_profile_get("k_adj_gather_flat") counts both).  Other values are TOMO_ERR_ARG
  *   "reuse_staged_volume" 1: the caller vouches that the volume passed to tomo_proj_grad / tomo_cost_grad / the ray-driven
  *                 forward has not changed since the previous such call with the same pointer, so its zero-padded staging
  *                 copy is reused (alignment loops evaluate hundreds of poses against one volume); default 0

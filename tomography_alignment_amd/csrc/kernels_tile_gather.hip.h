@@ -22,7 +22,8 @@
 //      z chunk of the tile: the four waves of a work-group (four z chunks) each compute it for every fourth projection and
 //      share it through a triple-buffered LDS table, one barrier per four projections;
 //   2. lane = PLANE: the z-lerped sinogram rows the tile can touch (<= 14) are loaded once (coalesced) into wave-private LDS
-//      rows (pitch 68 dwords: 16-byte aligned plane quads, lanes reading different rows hit different bank quads);
+//      rows (pitch 68 dwords: 16-byte aligned plane quads, lanes reading different rows hit different bank quads) -- through registers,
+//      or, where nothing is to be done to them on the way (tau = 0, all planes on the detector), straight into LDS (DMA = 1, below);
 //   3. lane = COLUMN again, 64 plane accumulators per lane (statically indexed registers, as plane pairs): per four planes
 //      3 ds_read_b128 at row(lane) + immediate plane offset and 6 v_pk_fma_f32 with the lane's own W0..W2 -- no broadcasts, no
 //      address arithmetic.
@@ -175,14 +176,25 @@ __device__ __forceinline__ void gather_update_store(float *__restrict__ dst, con
     }
 }
 
-template <int NJ, int UPD>      // NJ: samples per row that can reach a column: 3 for step >= 0.95 voxel, 6 for step >= 0.475; UPD: the store is the SIRT update
+// DMA = 1 (NJ = 3 only; the host launches it when every pose has tau = 0 and the plan's largest |m00| + |m01| is below GDMA_EA: adjoint_tiles,
+// tomo_project.hip): the sinogram rows go STRAIGHT into LDS (buffer_load_dword ... lds), into two row buffers in turn -- with tau = 0 and all
+// 64 planes of the wave on the detector the staging pass only copied a loaded 256-byte row to base + 4 * lane, which is what a direct-to-LDS
+// load writes by itself (a row of 256 bytes inside a pitch of 272: no wave-instruction crosses a row).  No staging stores, no staged
+// registers; the rows of projection ip + 1 fly while ip accumulates from the other buffer.  Both loops keep GDMA_ROWS = 13 rows per
+// projection: 7 (|m00| + |m01|) < 9.99 leaves i0 at most 11 values over the tile's 8 x 8 columns, + 2.  A wave whose planes can leave the
+// detector under some projection takes the register loop (into the first buffer) for all projections.
+#define GDMA_ROWS 13
+#define GDMA_EA 1.427
+template <int NJ, int UPD, int DMA = 0>      // NJ: samples per row that can reach a column: 3 for step >= 0.95 voxel, 6 for step >= 0.475; UPD: the store is the SIRT update
 __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(const GfC *__restrict__ cs, int n_proj, const float *__restrict__ proj,
                                                                  float *__restrict__ vol, TomoGeomC g, int xs, int xe, int patched,
                                                                  const unsigned char *__restrict__ zflags, int zc_lo, int zc_hi, const int *__restrict__ zshift,
                                                                  const float *__restrict__ upd_v, const float *__restrict__ upd_gt, int positivity,
                                                                  double *__restrict__ upd_err)
 {
-    __shared__ __attribute__((aligned(16))) float rows[GWAVES][GROWS * GPITCH];
+    static_assert(DMA == 0 || NJ == 3, "the direct-to-LDS loop is built for NJ = 3 only");
+    constexpr int NR = DMA ? GDMA_ROWS : GROWS;         // rows loaded per projection
+    __shared__ __attribute__((aligned(16))) float rows[GWAVES][NR * GPITCH];
     __shared__ float4 wtab[3][GWAVES][64];          // [group mod 3][projection of the group][column] = (i0, W0, W1, W2)
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -322,8 +334,8 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         const __amdgpu_buffer_rsrc_t srs =                                                                                 \
             __builtin_amdgcn_make_buffer_rsrc((void *)(proj + (size_t)cn.slot * n_det), 0, (int)det_bytes, 0x00020000);    \
         const uint32_t o0 = (uint32_t)min(max(iz0, 0), g.ndz - 1) * 4u;                                                    \
-        const uint32_t rowoff = (uint32_t)min(max(ix_lo_n + min(lane, GROWS - 1), 0), g.ndx - 1) * pitch4;                 \
-        _Pragma("unroll") for (int r = 0; r < GROWS; ++r)                                                                  \
+        const uint32_t rowoff = (uint32_t)min(max(ix_lo_n + min(lane, NR - 1), 0), g.ndx - 1) * pitch4;                    \
+        _Pragma("unroll") for (int r = 0; r < NR; ++r)                                                                     \
             y0v[r] = G_ROW_LOAD(srs, o0, (uint32_t)__builtin_amdgcn_readlane((int)rowoff, r));                             \
         /* the plane below (iz0 - 1) is the neighbouring lane's value (DPP shift when used); lane 0 has no neighbour: one  */ \
         /* more load, lane r fetching row r at the wave's first plane - 1 -- 15 loads per projection instead of 28      */ \
@@ -333,15 +345,25 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         }                                                                                                                  \
     }
 #define G_ZLERP(MASKED, TAU)                                                                                                      \
-    _Pragma("unroll") for (int r = 0; r < GROWS; ++r) {                                                                           \
-        float y1 = dpp_shr1_f(y0v[r]);                                            /* lane l <- lane l - 1: y(ix, iz0 - 1) for l >= 1 */ \
+    _Pragma("unroll") for (int r = 0; r < NR; ++r) {                                                                              \
+        float y1 = dpp_shr1_f(y0v[r]);                                           /* lane l <- lane l - 1: y(ix, iz0 - 1) for l >= 1 */ \
         asm("v_writelane_b32 %0, %1, 0" : "+v"(y1) : "s"(__builtin_amdgcn_readlane(__builtin_bit_cast(int, yedge), r)));   /* lane 0 <- row r's edge value */ \
         const float a0 = (MASKED) ? select_lanes(y0v[r], m0) : y0v[r], a1 = (MASKED) ? select_lanes(y1, m1) : y1;                \
         wrows[r * GPITCH + lane] = fmaf((TAU), a1 - a0, a0);                                                                      \
     }
     // (no per-row validity test: a row outside the detector was loaded from a clamped, valid address and every lane's
     //  weight for it is 0 (G_TABLE); rows past the last one a lane needs are never read)
-#define G_STAGE(IPX)                                                                                                       \
+#ifdef TOMO_ABLATE_GATHER_STAGE     /* measurement builds only: the nominal scan's staging stores gone -- the loads are kept alive by NR - 1 adds and */
+#define G_STAGE_COPY                /* ONE row is stored (wrong sums; loads, VALU and reads as before): profiles/adj_dma_before_after.md               */ \
+    {                                                                                                                      \
+        float ysum = y0v[0];                                                                                               \
+        _Pragma("unroll") for (int r = 1; r < NR; ++r) ysum += y0v[r];                                                     \
+        wrows[lane] = ysum;                                                                                                \
+    }
+#else
+#define G_STAGE_COPY _Pragma("unroll") for (int r = 0; r < NR; ++r) wrows[r * GPITCH + lane] = y0v[r];
+#endif
+#define G_STAGE(IPX)                                                                                                      \
     {                                                                                                                      \
         const GfC &cn = cs[IPX];                                                                                           \
         const int iz0 = Zl - cn.zc, iz1 = iz0 - 1;                                                                         \
@@ -349,33 +371,129 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         const unsigned long long m1 = __builtin_amdgcn_ballot_w64(iz1 >= 0) & __builtin_amdgcn_ballot_w64(iz1 < g.ndz);    \
         if (cn.tau == 0.f) {            /* samples sit exactly on detector rows (integer z shift: the nominal geometry before */ \
             if (m0 == ~0ull) {          /* alignment): Yz = y -- no neighbour plane, no lerp (fma(0, a1 - a0, a0) = a0)      */ \
-                _Pragma("unroll") for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = y0v[r];    /* all 64 planes on the detector: no select either */ \
+                G_STAGE_COPY            /* all 64 planes on the detector: no select either */                              \
             } else {                                                                                                       \
-                _Pragma("unroll") for (int r = 0; r < GROWS; ++r) wrows[r * GPITCH + lane] = select_lanes(y0v[r], m0);     \
+                _Pragma("unroll") for (int r = 0; r < NR; ++r) wrows[r * GPITCH + lane] = select_lanes(y0v[r], m0);        \
             }                                                                                                              \
         }                                                                                                                  \
         else if ((m0 & m1) == ~0ull) { G_ZLERP(false, cn.tau) }     /* all 64 planes and their lower neighbours on the detector: the usual case */ \
         else { G_ZLERP(true, cn.tau) }                                                                                     \
     }
 #define G_HIT(T) (__any((T).y != 0.f || (T).z != 0.f || (T).w != 0.f))      /* else this projection's rays miss the tile */
+    // ---- 3. accumulate, lane = column: its three rows start at slot0; plane p is an immediate offset.  The LDS rows WR were
+    //         written by (or, DMA, loaded for) this same wave, no other wave touches them.
+    //         plane QUADS with ds_read_b128 (round 2): 256 B/clk where ds_read_b32 moves 128 B/clk -- the kernel was LDS-bound
+    //         (SQ_LDS_IDX_ACTIVE = 0.79 of its cycles) on 3 x 64 dword reads per projection.
+    //         two quads of reads in flight: quad p + 4 is issued before quad p is used (24 temporaries; with one quad in
+    //         flight a wave had 6 packed FMAs to cover each LDS round trip).
+    //         plane pairs as packed FMAs (v_pk_fma_f32: two planes per instruction at 0.83 of the scalar rate).
+    //         The sched_barrier keeps the reads from all being hoisted to the top (192 temporaries).
+#define G_ACCUM(WR)                                                                                                        \
+    {                                                                                                                      \
+        const int i0 = __builtin_bit_cast(int, t.x);                                                                       \
+        const float W0 = t.y, W1 = t.z, W2 = t.w;                                                                          \
+        const int slot0 = min(max(i0 - ix_lo, 0), NR - 3);      /* an 8 x 8 column tile touches <= 13 rows (7 (|cos| + |sin|) + 3); clamped for safety */ \
+        const float4 *q = (const float4 *)__builtin_assume_aligned((WR) + slot0 * GPITCH, 16);                             \
+        float4 n0 = q[0], n1 = q[GPITCH / 4], n2 = q[2 * GPITCH / 4];                                                      \
+        _Pragma("unroll") for (int p = 0; p < 64; p += 4) {                                                                \
+            const float4 r0 = n0, r1 = n1, r2 = n2;                                                                        \
+            if (p + 4 < 64) { n0 = q[(p + 4) / 4]; n1 = q[(GPITCH + p + 4) / 4]; n2 = q[(2 * GPITCH + p + 4) / 4]; }       \
+            acc2[p / 2] = W2 * f32x2{r2.x, r2.y} + (W1 * f32x2{r1.x, r1.y} + (W0 * f32x2{r0.x, r0.y} + acc2[p / 2]));      \
+            acc2[p / 2 + 1] = W2 * f32x2{r2.z, r2.w} + (W1 * f32x2{r1.z, r1.w} + (W0 * f32x2{r0.z, r0.w} + acc2[p / 2 + 1])); \
+            __builtin_amdgcn_sched_barrier(0);                                                                             \
+        }                                                                                                                  \
+    }
     const int n_grp = (n_proj + nl - 1) / nl;
     int buf = 0;                                                        // table buffer of the current group (three in rotation)
     float4 t = {0.f, 0.f, 0.f, 0.f};                                    // the projection whose rows are in the LDS rows
     int ix_lo = 0;
     bool hit = false;
-    if (n_grp > 0) {
+    bool reg_loop = true;
+    if constexpr (DMA != 0) {
+        // ---- the direct-to-LDS loop.  Wave-uniform and decided once: all 64 planes on the detector under every projection (the register
+        //      loop below otherwise, from the start and for all projections: nothing is ordered between the two mechanisms).  Both kinds of
+        //      wave of a work-group meet at the same barriers, one per group of nl projections.
+        __shared__ __attribute__((aligned(16))) float rows_b[GWAVES][NR * GPITCH];     // a second OBJECT, never an index: the compiler's counted vmcnt rests on telling the two apart
+        if (z0 - zc_hi >= 0 && z0 + 63 - zc_lo < g.ndz && n_grp > 0) {
+            reg_loop = false;
+            float *const wrows_b = rows_b[wv];
+            // G_DMA_ISSUE: G_SETUP with the LDS row as the loads' destination (LDS address = the row's base, wave-uniform in M0, + 4 * lane)
+#define G_DMA_ISSUE(IPX, BUF, SLOT, DST)                                                                                   \
+            {                                                                                                              \
+                tn = wtab[BUF][SLOT][lane];                                                                                \
+                hit_n = G_HIT(tn);                                                                                         \
+                const int i0s = __builtin_bit_cast(int, tn.x);                                                             \
+                ix_lo_n = __builtin_amdgcn_readfirstlane(gwave_min_i32(i0s));                                              \
+                const GfC &cn = cs[IPX];                                                                                   \
+                const __amdgpu_buffer_rsrc_t srs =                                                                         \
+                    __builtin_amdgcn_make_buffer_rsrc((void *)(proj + (size_t)cn.slot * n_det), 0, (int)det_bytes, 0x00020000); \
+                const uint32_t o0 = (uint32_t)min(max(Zl - cn.zc, 0), g.ndz - 1) * 4u;                                     \
+                const uint32_t rowoff = (uint32_t)min(max(ix_lo_n + min(lane, NR - 1), 0), g.ndx - 1) * pitch4;            \
+                _Pragma("unroll") for (int r = 0; r < NR; ++r)                                                             \
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(srs, (__attribute__((address_space(3))) void *)((DST) + r * GPITCH), 4, (int)o0, \
+                                                             __builtin_amdgcn_readlane((int)rowoff, r), 0, 0);             \
+            }
+            // the tables are published behind lgkmcnt(0) and a RAW barrier: __syncthreads() would drain the loads in flight (vmcnt(0))
+#define G_DMA_BARRIER                                                                                                      \
+            {                                                                                                              \
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                         \
+                __builtin_amdgcn_s_barrier();                                                                              \
+                asm volatile("" ::: "memory");                                                                             \
+            }
+            // One pass: (a group starts: next group's tables, barrier;) issue the rows of projection IP + 1 into NXT; accumulate IP from CUR.
+            // The loads are unconditional -- the last pass fetches its own rows once more -- so that every accumulate sees the same queue:
+            // its own NR loads landed, NR younger ones in flight (a counted vmcnt).  NXT's last readers are done: the table read above
+            // the loads returns behind them (LDS answers a wave in order) and the loads' addresses wait for it.
+#define G_DMA_PASS(IP, CUR, NXT)                                                                                           \
+            {                                                                                                              \
+                if ((IP) == g1) {                                                                                          \
+                    if ((IP) > 0) buf = nbuf;                                                                              \
+                    nbuf = buf == 2 ? 0 : buf + 1;                                                                         \
+                    g0 = (IP); g1 = min(n_proj, g0 + nl);                                                                  \
+                    if (g0 + nl < n_proj) G_TABLE(g0 + nl + rk, nbuf, rk)                                                  \
+                    G_DMA_BARRIER                                                                                          \
+                }                                                                                                          \
+                {                                                                                                          \
+                    const int ipn = min((IP) + 1, n_proj - 1);                                                             \
+                    const bool same = ipn < g1;                                                                            \
+                    const int sbuf = same ? buf : nbuf, sslot = same ? ipn - g0 : 0;                                       \
+                    G_DMA_ISSUE(ipn, sbuf, sslot, NXT)                                                                     \
+                }                                                                                                          \
+                if (hit) G_ACCUM(CUR)                                                                                      \
+                hit = hit_n; t = tn; ix_lo = ix_lo_n;                                                                      \
+            }
+            G_TABLE(rk, 0, rk)                                          // group 0
+            __syncthreads();                                            // (no load in flight yet)
+            float4 tn;
+            int ix_lo_n = 0;
+            bool hit_n;
+            G_DMA_ISSUE(0, 0, 0, wrows)
+            hit = hit_n; t = tn; ix_lo = ix_lo_n;
+            int g0 = 0, g1 = 0, nbuf = 0;
+            for (int ip = 0; ip < n_proj; ip += 2) {                    // by two: each pass names its buffers statically
+                G_DMA_PASS(ip, wrows, wrows_b)
+                if (ip + 1 >= n_proj) break;
+                G_DMA_PASS(ip + 1, wrows_b, wrows)
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the last pass's loads: nothing may land in LDS after the wave has ended
+#undef G_DMA_ISSUE
+#undef G_DMA_BARRIER
+#undef G_DMA_PASS
+        }
+    }
+    if (reg_loop && n_grp > 0) {
         G_TABLE(rk, 0, rk)                                              // group 0
         __syncthreads();
         float4 tn;
         int ix_lo_n = 0;
         bool hit_n;
-        float y0v[GROWS], yedge = 0.f;                                  // yedge: lane r holds row r one plane below the wave's first
+        float y0v[NR], yedge = 0.f;                                     // yedge: lane r holds row r one plane below the wave's first
         G_SETUP(0, 0, 0)
         hit = hit_n;
         if (hit) G_STAGE(0)
         t = tn; ix_lo = ix_lo_n;
     }
-    for (int grp = 0; grp < n_grp; ++grp) {
+    for (int grp = 0; reg_loop && grp < n_grp; ++grp) {
         const int nbuf = buf == 2 ? 0 : buf + 1;
         if (grp + 1 < n_grp) G_TABLE((grp + 1) * nl + rk, nbuf, rk)     // next group's tables: a third buffer, nobody reads it yet
         __syncthreads();                                                // ... and everybody is done with group grp - 1's buffer
@@ -384,35 +502,14 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
             float4 tn = t;
             int ix_lo_n = ix_lo;
             bool hit_n = false;
-            float y0v[GROWS], yedge = 0.f;
+            float y0v[NR], yedge = 0.f;
             const bool more = ip + 1 < n_proj;
             if (more) {
                 const bool same = ip + 1 < g1;                              // else the next group's table, already published
                 const int sbuf = same ? buf : nbuf, sslot = same ? ip + 1 - g0 : 0;
                 G_SETUP(ip + 1, sbuf, sslot)
             }
-            // ---- 3. accumulate, lane = column: its three rows start at slot0; plane p is an immediate offset.  The LDS rows were
-            //         written by this same wave (LDS operations of a wave execute in order), no other wave touches them.
-            if (hit) {
-                const int i0 = __builtin_bit_cast(int, t.x);
-                const float W0 = t.y, W1 = t.z, W2 = t.w;
-                const int slot0 = min(max(i0 - ix_lo, 0), GROWS - 3);       // an 8 x 8 column tile touches <= 13 rows (7 (|cos| + |sin|) + 3); clamped for safety
-                // plane QUADS with ds_read_b128 (round 2): 256 B/clk where ds_read_b32 moves 128 B/clk -- the kernel was LDS-bound
-                // (SQ_LDS_IDX_ACTIVE = 0.79 of its cycles) on 3 x 64 dword reads per projection
-                const float4 *q = (const float4 *)__builtin_assume_aligned(wrows + slot0 * GPITCH, 16);
-                // two quads of reads in flight: quad p + 4 is issued before quad p is used (24 temporaries; with one quad in
-                // flight a wave had 6 packed FMAs to cover each LDS round trip)
-                float4 n0 = q[0], n1 = q[GPITCH / 4], n2 = q[2 * GPITCH / 4];
-#pragma unroll
-                for (int p = 0; p < 64; p += 4) {
-                    const float4 r0 = n0, r1 = n1, r2 = n2;
-                    if (p + 4 < 64) { n0 = q[(p + 4) / 4]; n1 = q[(GPITCH + p + 4) / 4]; n2 = q[(2 * GPITCH + p + 4) / 4]; }
-                    // plane pairs as packed FMAs (v_pk_fma_f32: two planes per instruction at 0.83 of the scalar rate)
-                    acc2[p / 2] = W2 * f32x2{r2.x, r2.y} + (W1 * f32x2{r1.x, r1.y} + (W0 * f32x2{r0.x, r0.y} + acc2[p / 2]));
-                    acc2[p / 2 + 1] = W2 * f32x2{r2.z, r2.w} + (W1 * f32x2{r1.z, r1.w} + (W0 * f32x2{r0.z, r0.w} + acc2[p / 2 + 1]));
-                    __builtin_amdgcn_sched_barrier(0);                       // keeps the reads from all being hoisted to the top (192 temporaries)
-                }
-            }
+            if (hit) G_ACCUM(wrows)
             // ---- 2b. the rows loaded above, z-lerped into the wave's LDS rows (lane = plane)
             hit = hit_n;
             if (hit) G_STAGE(ip + 1)
@@ -420,6 +517,8 @@ __global__ __launch_bounds__(GWAVES * 64, 16 / GWAVES) void k_adj_gather_flat(co
         }
         buf = nbuf;
     }
+#undef G_ACCUM
+#undef G_STAGE_COPY
 #undef G_TABLE
 #undef G_ROW_LOAD
 #undef G_SETUP

@@ -36,6 +36,8 @@ struct TilePlan {
     int n_flat = 0, n_gather = 0;       // untilted projections, and how many of them are gather-eligible
     double eb_max = 0.0;                // largest |m10| + |m11| of the gather-eligible projections (picks NJ)
     int zc_lo = 0, zc_hi = 0;           // range of the gather-eligible projections' integer z offsets (GfC::zc)
+    double ea_max = 0.0;                // largest |m00| + |m01| of the gather-eligible projections, and whether all of them have tau == 0:
+    bool tau_zero = true;               // what the direct-to-LDS adjoint (option "adj_gather_dma") asks of a plan
     size_t gf_off = 0, fg_off = 0;      // byte offsets into the staging buffer
     int fg_n[4] = {0, 0, 0, 0};
     bool fg_ok = false;                 // every gather-eligible projection also meets the gather forward's bounds
@@ -114,6 +116,7 @@ struct tomo_ctx {
     int tile_flat = 1;      // 1: untilted projections take the flat tile kernels
     int fused_update = 1;     // 1: tomo_adjoint_update folds the SIRT update into the gather adjoint's store when all its poses take that kernel; 0: it always declines (the caller's two calls)
     int adj_flat_gather = 1;  // 1: untilted unit lattices take the gather-form adjoint (k_adj_gather_flat) instead of the LDS-atomic flat kernel
+    int adj_gather_dma = 1;   // 1 (default): a gather adjoint with three samples per row, tau == 0 in every pose and |m00| + |m01| < 1.427 loads its sinogram rows straight into LDS (k_adj_gather_flat<3, UPD, 1>); 0: always through registers
     int fwd_gather_patch = 1; // work-group order of k_fwd_gather_flat: 0 plain (group, row tile) order, 1 (default) XCD patches from FWD_PATCH_MIN patches up, 2 patches at any size
     int fwd_flat_gather = 1;  // 1 (default): whole-volume forward calls ALL of whose poses take the gather adjoint (three samples per row) take the gather-form forward (k_fwd_gather_flat: no atomics, same bits every run); other calls, and 0: the flat forward below
     int fwd_flat_ztiles = 2;  // 2 (default): the flat forward of a volume of two or more z tiles runs over blocks of two z-adjacent 64-plane images, live blocks only (k_fwd_flat_tab); 1, and volumes of one z tile: one tile per work-group (k_tile_flat<true>)

@@ -193,6 +193,10 @@ extern "C" int tomo_set_option(tomo_ctx *ctx, const char *key, int value)
     else if (!strcmp(key, "comm_test_copy_eighths")) ctx->comm_test_copy_eighths = value < 0 ? 0 : value;
     else if (!strcmp(key, "comm_test_copy_wgs")) ctx->comm_test_copy_wgs = value < 0 ? 0 : value;
     else if (!strcmp(key, "adj_flat_gather")) ctx->adj_flat_gather = value;
+    else if (!strcmp(key, "adj_gather_dma")) {
+        if (value < 0 || value > 1) return tomo_fail(ctx, TOMO_ERR_ARG, "adj_gather_dma: 0 or 1");
+        ctx->adj_gather_dma = value;
+    }
     else if (!strcmp(key, "fused_update")) ctx->fused_update = value;
     else if (!strcmp(key, "fwd_flat_ztiles")) ctx->fwd_flat_ztiles = value;
     else if (!strcmp(key, "fwd_flat_gather")) ctx->fwd_flat_gather = value;

@@ -196,6 +196,8 @@ static int stage_tile_consts(tomo_ctx *ctx, const double *h_poses, int n_proj, c
             p.eb_max = std::max(p.eb_max, eb);
             p.zc_lo = std::min(p.zc_lo, (int)q.zc);
             p.zc_hi = std::max(p.zc_hi, (int)q.zc);
+            p.ea_max = std::max(p.ea_max, ea);
+            p.tau_zero = p.tau_zero && q.tau == 0.f;
         } else
             (untilted ? flat : gen).push_back(a);
     }
@@ -482,12 +484,23 @@ static int adjoint_tiles(tomo_ctx *ctx, const double *h_poses, int n_proj, const
             const float *u_v = upd ? upd->v : nullptr, *u_gt = upd ? upd->gt : nullptr;
             const int u_pos = upd ? upd->positivity : 0;
             if (upd && upd->gt) TOMO_HIP(ctx, hipMemsetAsync(ctx->d_red, 0, sizeof(double), ctx->stream));      // the slot k_update sums into (tomo_vec_update)
-#define GATHER_LAUNCH(NJ, UPD)                                                                                                                       \
-    TOMO_LAUNCH(ctx, "k_adj_gather_flat", (k_adj_gather_flat<NJ, UPD>), ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, d_vol, g, xs, xe, patched, \
-                (const unsigned char *)head.zf, zc_lo, zc_hi, (const int *)head.zshift, u_v, u_gt, u_pos, ctx->d_red)
-            // NJ = 6: finer sampling along the rays (step down to ~0.475 voxel): six samples per row can reach a column
-            if (plan->eb_max < 1.49) { if (upd) GATHER_LAUNCH(3, 1); else GATHER_LAUNCH(3, 0); }
-            else { if (upd) GATHER_LAUNCH(6, 1); else GATHER_LAUNCH(6, 0); }
+#define GATHER_LAUNCH(NJ, UPD, DMA)                                                                                                                  \
+    TOMO_LAUNCH(ctx, (DMA) ? "k_adj_gather_flat(dma)" : "k_adj_gather_flat", (k_adj_gather_flat<NJ, UPD, DMA>), ggrid, dim3(GWAVES * 64), 0, d_gfc, n_gather, d_proj, \
+                d_vol, g, xs, xe, patched, (const unsigned char *)head.zf, zc_lo, zc_hi, (const int *)head.zshift, u_v, u_gt, u_pos, ctx->d_red)
+            // NJ = 6: finer sampling along the rays (step down to ~0.475 voxel): six samples per row can reach a column.
+            // DMA (option "adj_gather_dma"): sinogram rows straight into LDS -- every pose on detector rows exactly (tau == 0) and the
+            // tile's 13-row bound (kernels_tile_gather.hip.h: GDMA_ROWS).  Profiled as "k_adj_gather_flat(dma)": tomo_profile_get of the
+            // plain name counts both, the full name only these.
+#ifdef TOMO_ABLATE_GATHER_STAGE     /* measurement builds only: what is ablated is the register kernel's staging */
+            const bool dma = false;
+#else
+            const bool dma = ctx->adj_gather_dma != 0 && plan->tau_zero && plan->ea_max < GDMA_EA;
+#endif
+            if (plan->eb_max < 1.49) {
+                if (dma) { if (upd) GATHER_LAUNCH(3, 1, 1); else GATHER_LAUNCH(3, 0, 1); }
+                else { if (upd) GATHER_LAUNCH(3, 1, 0); else GATHER_LAUNCH(3, 0, 0); }
+            }
+            else { if (upd) GATHER_LAUNCH(6, 1, 0); else GATHER_LAUNCH(6, 0, 0); }
 #undef GATHER_LAUNCH
         }
     }

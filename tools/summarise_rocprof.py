@@ -40,6 +40,8 @@ def short(name):
         return "k_fwd_tile"
     if k.startswith("k_tile<false"):
         return "k_adj_tile"
+    if k.startswith("k_adj_gather_flat<"):   # k_adj_gather_flat<NJ, UPD, DMA>: DMA = 1 loads its rows straight into LDS
+        return "k_adj_gather_flat"
     return ALIAS.get(k, k)
 
 
