@@ -23,6 +23,10 @@ class Staging(object):
         self._owned.append(d)
         return d
 
+    def adopt(self, d):
+        """A device array made elsewhere during the call (by another owner's operation) becomes the scope's to free."""
+        return self._own(d)
+
     def source(self, a, dtype=np.float32):
         """A DeviceArray as it is; a host array uploaded (contiguous, of `dtype`; None: its own) as a temporary of the scope."""
         if _is_dev(a):

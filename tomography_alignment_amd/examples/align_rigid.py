@@ -265,13 +265,17 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
         kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None, export=None,
-        export_dtype=np.uint8, register_truth=False, segment=False):
+        export_dtype=np.uint8, register_truth=False, segment=False, morphology=False):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     segment        True: after the last outer iteration the reconstruction is segmented where it lies in HBM (_segmentation: Otsu's
                    threshold over the cylinder, threshold, label with 6 neighbours, measure; rank 0 of a sharded run) and the last
                    history entry gains `segmentation` = {"threshold", "n_components", "foreground_fraction", "largest_fraction"};
                    with `export` as well, export/labels_meta.json holds the same figures and the table of at most the 1000 largest
                    components.  With False (the default) nothing of the run changes.
+    morphology     True (with segment): `segmentation` gains "max_inscribed_radius", the largest distance of a mask voxel to the
+                   background or the outside of the volume in voxels (morphology.distance, "background"), and "closed_porosity",
+                   the voxels fill_holes adds over foreground plus those (0 without foreground); labels_meta.json holds them too.
+                   Nothing else of the run changes.
     register_truth True, and the data carry a phantom: every history entry gains `truth_shift` and `rmse_registered` (_truth_entry), the
                    RMSE after the gauge translation between reconstruction and phantom is taken out; `rmse` stays as it is.
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
@@ -287,6 +291,8 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     Returns (rec or None when not `download`, alpha, beta, xyz, history) -- with `return_loop` a sixth element, the OuterLoop itself
     (`loop.d_rec`: the reconstruction where it lies in HBM, `loop.solver`, `loop.d_b`).  Nothing is kept alive behind the caller's back:
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
+    if morphology and not segment:
+        raise ValueError("run: morphology=True goes with segment=True")
     cor = resolve_cor(data, cor, comm, getattr(backend, "ctx", None), verbose)
     xyz0 = resolve_prealign(data, prealign, comm, getattr(backend, "ctx", None), verbose)
     start = {} if xyz0 is None else {"base": _base_of(xyz0)}
@@ -309,18 +315,19 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     if segment and loop.d_rec is not None and loop.rank == 0:
         if not history:
             history.append({})
-        history[-1]["segmentation"] = _segmentation(loop, export, verbose)
+        history[-1]["segmentation"] = _segmentation(loop, export, verbose, morphology=morphology)
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
 
 
-def _segmentation(loop, export=None, verbose=False, limit=1000):
+def _segmentation(loop, export=None, verbose=False, limit=1000, morphology=False):
     """The reconstruction (loop.d_rec, not written) split into its connected objects on the device: Otsu's threshold of the 4096-bin
     histogram over the reconstruction cylinder, the mask v >= threshold inside the cylinder, its components with 6 neighbours and their
     measures; only the tables come to the host.  -> {"threshold", "n_components", "foreground_fraction" (of the cylinder's voxels),
     "largest_fraction" (of the foreground; 0 without one)}.  export: a directory; labels_meta.json there holds the same and
-    "components", the `limit` largest as {"label", "count", "bbox", "centroid"}."""
+    "components", the `limit` largest as {"label", "count", "bbox", "centroid"}.  morphology: also "max_inscribed_radius" and
+    "closed_porosity" (_mask_morphology), taken from the same mask before it is freed."""
     import json
     import os
 
@@ -331,6 +338,7 @@ def _segmentation(loop, export=None, verbose=False, limit=1000):
         t, = seg.otsu(loop.d_rec, 2, 4096, None, "cylinder", shape=shape)
         d_mask = seg.threshold(loop.d_rec, lo=t, region="cylinder", shape=shape)
         d_labels, n = seg.label(d_mask, 1, shape=shape)
+        extra = _mask_morphology(loop, d_mask, shape) if morphology else None
         d_mask.free()
         comp = seg.measure(d_labels, n, shape=shape)
         d_labels.free()
@@ -339,6 +347,9 @@ def _segmentation(loop, export=None, verbose=False, limit=1000):
     inside = int(np.count_nonzero(a[:, None] ** 2 + b[None, :] ** 2 <= region_r4("cylinder", shape[0], shape[1]))) * shape[2]
     out = {"threshold": float(t), "n_components": int(n), "foreground_fraction": fg / float(inside),
            "largest_fraction": float(comp.count.max()) / fg if n else 0.0}
+    if extra is not None:
+        radius, filled = extra
+        out.update(max_inscribed_radius=radius, closed_porosity=filled / float(fg + filled) if fg else 0.0)
     if export is not None:
         os.makedirs(export, exist_ok=True)
         with open(os.path.join(export, "labels_meta.json"), "w") as f:
@@ -346,6 +357,20 @@ def _segmentation(loop, export=None, verbose=False, limit=1000):
     if verbose:
         print({"segmentation": out})
     return out
+
+
+def _mask_morphology(loop, d_mask, shape):
+    """-> (the largest distance of a voxel of the device mask to its background or the outside of the volume, in voxels; the number of
+    voxels fill_holes adds to it).  Only the two numbers come to the host."""
+    from .. import morphology as morph_mod
+    from .. import postprocess
+    with morph_mod.Morphology(loop.ctx) as mo:
+        d_dist = mo.distance(d_mask, "background", shape=shape)
+        radius = float(postprocess.statistics(d_dist, ctx=loop.ctx, shape=shape).max)
+        d_dist.free()
+        d_filled, filled = mo.fill_holes(d_mask, return_count=True, shape=shape)
+        d_filled.free()
+    return radius, int(filled)
 
 
 def _fsc_entry(loop, res):
@@ -565,6 +590,8 @@ def main():
     ap.add_argument("--segment", action="store_true", help="segment the reconstruction on the GPU after the last outer iteration: Otsu's "
                     "threshold over the cylinder, connected components with 6 neighbours and their measures (segment; --levels 1); with "
                     "--export, DIR/labels_meta.json holds the component table")
+    ap.add_argument("--morphology", action="store_true", help="with --segment: also the largest inscribed radius of the mask (the exact "
+                    "Euclidean distance transform) and its closed porosity (hole filling) on the GPU (morphology)")
     ap.add_argument("--register-truth", action="store_true", help="with a phantom in the data: also report the RMSE after the reconstruction "
                     "is registered to the phantom (truth_shift, rmse_registered); --levels 1 only")
     a = ap.parse_args()
@@ -573,6 +600,8 @@ def main():
         ap.error("--export goes with --levels 1")
     if a.segment and a.levels != 1:
         ap.error("--segment goes with --levels 1")
+    if a.morphology and not a.segment:
+        ap.error("--morphology goes with --segment")
     if a.prealign not in (None, "moment", "profile", "file"):
         ap.error("--prealign must be moment, profile or file")
     import os
@@ -586,7 +615,7 @@ def main():
     prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
         run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign, export=a.export,
-            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth, segment=a.segment)
+            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth, segment=a.segment, morphology=a.morphology)
     else:
         run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:
