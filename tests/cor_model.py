@@ -223,6 +223,10 @@ def gap(m):
 
 SHAPES = [(60, 48), (90, 65), (45, 96), (37, 50), (24, 33)]      # (n, nx); the first four are the GPU parity cases
 PARITY_SHAPES = SHAPES[:4]
+# GPU parity cases whose wedge is wider than one wave of k_reduce: a row of the spectrum is summed over 2 <= ku <= min(w, nx / 2) by 64
+# lanes, so a second pass needs min(w, nx / 2) >= 66, hence nx >= 132 and, with ratio 0.5, a row frequency |kv| >= 103, hence n >= 103
+# (tests/test_gpu_rotation_axis.py asserts it of every shape here).  (24, 136) would not do: its noisy case separates by 38 x 16 d32 only.
+PARITY_SHAPES_WIDE = [(110, 140), (112, 200)]
 OFFSETS = [0.0, 3.25, -5.5, 7.75]
 NOISE_SEED = 2
 

@@ -9,6 +9,17 @@ from oracle import oracle as orc
 
 GPU_SHAPES = [(3, 5, 7), (2, 33, 65), (5, 70, 130), (1, 129, 513), (4, 64, 256)]        # (n, nx, nz) of tests/test_gpu_consistency.py
 
+# Past the first chunk of 1024 rows (k_marginals' blockIdx.y >= 1, k_fold's sums over chunks) and, for 256 < nz <= 512, two row groups
+# of 64 columns with two waves along z each:
+GPU_SHAPES_WIDE = [
+    (2, 5, 257),        # two row groups; the second z wave has a single live element
+    (2, 131, 511),      # two row groups, the 4-byte path, two x tiles, the x tail inside the second row group
+    (2, 70, 512),       # two row groups, the 16-byte path, the upper boundary of the split
+    (2, 4, 1025),       # two chunks, chunk 1 holds one element
+    (2, 5, 1029),       # two chunks, the 4-byte path
+    (1, 130, 2052),     # three chunks, the 16-byte path, two x tiles
+]
+
 
 # ------------------------------------------------------------------------------------------------------------------ the marginals
 

@@ -17,8 +17,29 @@ pytestmark = pytest.mark.gpu
 
 # one lane (3, 5, 7); the 4-byte path with a z tail past a wave (2, 33, 65); an x tail past a tile of 128 and a z tail past two waves
 # (5, 70, 130 is the 4-byte path, 130 = 2 * 64 + 2); several tiles, n = 1, nz odd (1, 129, 513); the 16-byte path (4, 64, 256)
-SHAPES = mm.GPU_SHAPES
+# and past them (mm.GPU_SHAPES_WIDE): two row groups of a work-group (256 < nz <= 512) on both load paths, with one element in the
+# second wave and with an x tail in the second group; two and three chunks of z, with one element in the last and on both load paths
+SHAPES = mm.GPU_SHAPES + mm.GPU_SHAPES_WIDE
 IDS = ["%dx%dx%d" % s for s in SHAPES]
+
+
+def _chunks(nz):
+    return -(-nz // _mom_lib.CHUNK_Z)
+
+
+def _two_groups(nz):
+    """groups_of of csrc/mom/tomo_mom.hip gives two row groups, of two waves of 256 z each, for these nz."""
+    return 256 < nz <= 512
+
+
+def test_the_shapes_reach_a_third_chunk_both_row_group_splits_and_a_second_tile():
+    """Host only: the list reaches what its comment claims, so a change of the library's constants fails here and not silently."""
+    assert any(_chunks(nz) >= 3 for _, _, nz in SHAPES) and any(_chunks(nz) == 2 for _, _, nz in SHAPES)
+    assert any(_chunks(nz) >= 2 and nz % 4 == 0 for _, _, nz in SHAPES) and any(_chunks(nz) >= 2 and nz % 4 for _, _, nz in SHAPES)
+    assert any(_two_groups(nz) and nz % 4 for _, _, nz in SHAPES) and any(_two_groups(nz) and nz % 4 == 0 for _, _, nz in SHAPES)
+    assert any(nx > _mom_lib.TILE_X for _, nx, _ in SHAPES)
+    assert any(nx > _mom_lib.TILE_X and _chunks(nz) >= 2 for _, nx, nz in SHAPES) and any(nx > _mom_lib.TILE_X and _two_groups(nz) for _, nx, nz in SHAPES)
+    assert all(_chunks(s[2]) >= 2 or _two_groups(s[2]) for s in BIT_SHAPES[2:])
 
 
 @pytest.fixture(scope="module")
@@ -85,9 +106,15 @@ def test_floor_window_and_non_finite_values(cons, shape):
     tail_x, tail_z = nx - 1, nz - 1                                   # past the last full tile, wave and 16-byte group where there is one
     planted = [((0, 0, 0), np.nan), ((n - 1, nx - 1, nz - 1), np.inf), ((n // 2, tail_x, nz // 2), -np.inf), ((0, nx // 2, tail_z), np.nan),
                ((n - 1, 0, min(1, nz - 1)), np.inf)]
+    windows = [None, (1, nz - 1), (nz // 2, nz // 2 + 1), (0, 1), (nz - 1, nz), (2, min(nz, 5))]
+    # windows that cut at the boundary of the first chunk or of the first wave of a row group, so that one chunk or wave takes the
+    # path of a wave with nothing inside the window while its neighbour is live; non-finite values on either side of that boundary
+    edge = _mom_lib.CHUNK_Z if _chunks(nz) > 1 else 256 if _two_groups(nz) else None
+    if edge is not None:
+        windows += [(edge, edge + 1), (edge - 1, edge + 1), (0, edge), (edge, nz)]
+        planted += [((0, 0, edge), -np.inf), ((n - 1, nx // 2, edge - 1), np.nan), ((0, nx - 1, min(edge + 1, nz - 1)), np.inf)]
     for idx, v in planted:
         p[idx] = v
-    windows = [None, (1, nz - 1), (nz // 2, nz // 2 + 1), (0, 1), (nz - 1, nz), (2, min(nz, 5))]
     checked = 0
     for floor in (None, 0.0, 17.5, -100.0):
         for zr in windows:
@@ -108,7 +135,11 @@ def test_floor_window_and_non_finite_values(cons, shape):
 
 # ------------------------------------------------------------------------------------------------------------------- determinism
 
-@pytest.mark.parametrize("shape", [(5, 70, 130), (4, 64, 256)], ids=["4-byte loads", "16-byte loads"])
+# the last two are 16-byte shapes whose misaligned run takes the 4-byte loads across a chunk boundary and across the row-group split
+BIT_SHAPES = [(5, 70, 130), (4, 64, 256), (3, 5, 1028), (3, 70, 512)]
+
+
+@pytest.mark.parametrize("shape", BIT_SHAPES, ids=["4-byte loads", "16-byte loads", "two chunks", "two row groups"])
 def test_budgets_handles_sub_stacks_and_paths_give_the_same_bits(ctx, cons, shape):
     n, nx, nz = shape
     p = (np.random.default_rng(4).standard_normal(shape) * 2.0 + 0.5).astype(np.float32)

@@ -4,7 +4,8 @@ float64, the apply step bit for bit -- each stage fed the GPU's own output of th
 preprocess.normalize_dynamic end to end on generate_data's drifting beam, and examples/preprocess --dynamic-flat.
 
 Shapes: frames of 37 x 45 (odd, no multiple of a bin factor, of 4 or of a tile) and 130 x 270 (several tiles of the cost kernel with
-halos in both directions, 9 to 10 groups of chunks of the Gram kernel, three tiles of the apply kernel's transpose in z and five in x)."""
+halos in both directions, 9 to 10 groups of chunks of the Gram kernel, three tiles of the apply kernel's transpose in z and five in x).
+Five frames, and for the apply kernel 16, 17 and 33 as well: one, two and three of its groups of 16 frames."""
 import numpy as np
 import pytest
 
@@ -45,9 +46,10 @@ def dff(ctx):
 _CASES = {}
 
 
-def case(rows, cols, K, dtype):
-    """Host data of one shape, computed once: K flats whose beam moves (three smooth modes above the noise), darks, N frames."""
-    key = (rows, cols, K, np.dtype(dtype))
+def case(rows, cols, K, dtype, n=N):
+    """Host data of one shape, computed once: K flats whose beam moves (three smooth modes above the noise), darks, n frames (the
+    frames are drawn last, so the flats and darks do not depend on n)."""
+    key = (rows, cols, K, np.dtype(dtype), n)
     if key not in _CASES:
         rng = np.random.default_rng(rows * 1000 + cols + K)
         z, x = np.arange(rows)[:, None] / rows - 0.5, np.arange(cols)[None, :] / cols - 0.5
@@ -60,7 +62,7 @@ def case(rows, cols, K, dtype):
         dark_mean = 100 + 2 * rng.standard_normal((rows, cols))
         flats = rng.poisson(4000 * gain * beam(K)) + dark_mean
         darks = rng.poisson(np.broadcast_to(dark_mean, (3, rows, cols)))
-        frames = rng.poisson(4000 * gain * beam(N) * rng.uniform(0.2, 1.0, (N, rows, cols))) + dark_mean
+        frames = rng.poisson(4000 * gain * beam(n) * rng.uniform(0.2, 1.0, (n, rows, cols))) + dark_mean
         frames[:, 1, 2] = 0                                              # below the dark
         if np.dtype(dtype) == np.uint16:
             flats, darks, frames = (np.clip(np.rint(a), 0, 65535).astype(np.uint16) for a in (flats, darks, frames))
@@ -325,15 +327,26 @@ def test_cost_refuses_what_is_not_loaded(ctx, dff):
 
 # ---------------------------------------------------------------------------------------------------------------------- (e) apply
 
-@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
-@pytest.mark.parametrize("rows, cols, K, m", [(37, 45, 17, 3), (37, 45, 17, 8), (37, 45, 2, 1), (130, 270, 17, 3), (130, 270, 3, 0)])
-def test_apply_is_the_model_bit_for_bit(ctx, pre, rows, cols, K, m, dtype):
-    """Random weights, with and without crop and cutoff.  The ratio (minus_log=False) equals the model's bit for bit.  With the -log the
-    result equals, bit for bit, the device's own -log (Preprocessor.minus_log, the same expression) of the model's ratio: the device's
-    logf and numpy's differ in the last bit of some values, which tests/test_gpu_preprocess.py bounds by 2e-6 and so does this."""
-    c = case(rows, cols, K, dtype)
+# k_apply keeps a tile's flat and dark in registers across NORM_FR = 16 frames (csrc/dff/tomo_dff.hip); normalize_dynamic hands it all
+# frames in one call, so the second work-group along the frames begins at frame 16: one full group, one more frame, two groups and one.
+NORM_FR = 16
+MANY_FRAMES = [16, 17, 33]
+APPLY_CASES_MANY = [(37, 45, 3, 2, n) for n in MANY_FRAMES] + [(130, 270, 3, 1, 17)]
+
+
+def test_the_frame_counts_reach_past_the_first_frame_group():
+    """Host only: a full group, a second group that is not full, and a third."""
+    assert any(n == NORM_FR for n in MANY_FRAMES) and any(NORM_FR < n < 2 * NORM_FR for n in MANY_FRAMES) and any(n > 2 * NORM_FR for n in MANY_FRAMES)
+    assert all(n in MANY_FRAMES for _, _, _, _, n in APPLY_CASES_MANY) and N < NORM_FR
+
+
+def apply_against_the_model(pre, c, K, m):
+    """The body of the apply tests on the case c, whose frame count is its own: the weights are random per frame, so a frame that read
+    another frame's weights, or wrote another frame's output, does not pass.  Returns the number of values compared bit for bit."""
+    n, rows, cols = c["frames"].shape
     rng = np.random.default_rng(K + m)
-    W = rng.uniform(-2, 2, (N, m))
+    W = rng.uniform(-2, 2, (n, m))
+    compared = 0
     with pre.eigen_flats(c["flats"], c["darks"], n_eff=m) as ef:
         assert ef.n_eff == m and ef.eigenvalues.shape == (K,) and np.all(np.diff(ef.eigenvalues) <= 0)
         assert np.array_equal(ef.flat.download(), c["fbar"]) and np.array_equal(ef.dark.download(), c["dark"])
@@ -347,6 +360,7 @@ def test_apply_is_the_model_bit_for_bit(ctx, pre, rows, cols, K, m, dtype):
                 assert lin.shape == ref.shape and np.array_equal(lin.view(np.uint32), ref.view(np.uint32))
                 lg = pre.normalize_dynamic(c["frames"], ef, weights=W, **kw)
                 assert np.array_equal(lg.view(np.uint32), pre.minus_log(ref, min_ratio=1e-6).view(np.uint32))
+                compared += lin.size + lg.size
                 ref_log = dm.apply(c["frames"], c["fbar"], c["dark"], E, W, **kw)
                 assert np.all(np.isfinite(lg)) and np.all(np.abs(lg - ref_log) <= 2e-6 * np.maximum(1.0, np.abs(ref_log)))
         lg = pre.normalize_dynamic(c["frames"], ef, weights=W, min_ratio=0.3, cutoff=0.9)
@@ -355,18 +369,50 @@ def test_apply_is_the_model_bit_for_bit(ctx, pre, rows, cols, K, m, dtype):
         if m > 1:                                                        # fewer fields than the EigenFlats holds: the leading ones
             lin = pre.normalize_dynamic(c["frames"], ef, weights=W[:, :1], minus_log=False)
             assert np.array_equal(lin.view(np.uint32), dm.apply(c["frames"], c["fbar"], c["dark"], E[:1], W[:, :1], minus_log=False).view(np.uint32))
+    return compared
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+@pytest.mark.parametrize("rows, cols, K, m", [(37, 45, 17, 3), (37, 45, 17, 8), (37, 45, 2, 1), (130, 270, 17, 3), (130, 270, 3, 0)])
+def test_apply_is_the_model_bit_for_bit(ctx, pre, rows, cols, K, m, dtype):
+    """Random weights, with and without crop and cutoff.  The ratio (minus_log=False) equals the model's bit for bit.  With the -log the
+    result equals, bit for bit, the device's own -log (Preprocessor.minus_log, the same expression) of the model's ratio: the device's
+    logf and numpy's differ in the last bit of some values, which tests/test_gpu_preprocess.py bounds by 2e-6 and so does this."""
+    apply_against_the_model(pre, case(rows, cols, K, dtype), K, m)
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+@pytest.mark.parametrize("rows, cols, K, m, n", APPLY_CASES_MANY)
+def test_apply_past_the_first_frame_group_is_the_model_bit_for_bit(ctx, pre, rows, cols, K, m, n, dtype):
+    """The same body at 16, 17 and 33 frames: k_apply's second and third work-groups along the frames, whose weights, input and output
+    begin at frame 16 and 32."""
+    compared = apply_against_the_model(pre, case(rows, cols, K, dtype, n), K, m)
+    print("apply %dx%d K=%d m=%d %s, %d frames: 0 of %d values differ from the model" % (rows, cols, K, m, np.dtype(dtype).name, n, compared))
+
+
+def zero_weights_are_normalize(pre, c):
+    n, rows, cols = c["frames"].shape
+    for kw in (dict(), dict(cutoff=1.05, crop=((1, rows - 2), (3, cols))), dict(minus_log=False), dict(min_ratio=0.2, minus_log=True, cutoff=0.8)):
+        ref = pre.normalize(c["frames"], c["flats"], c["darks"], method="mean", **kw)
+        assert np.array_equal(ref.view(np.uint32), pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=0, **kw).view(np.uint32))
+        assert np.array_equal(ref.view(np.uint32), pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=3, weights=np.zeros((n, 3)), **kw).view(np.uint32))
+        res, W, nfev = pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=0, return_weights=True, **kw)
+        assert W.shape == (n, 0) and W.dtype == np.float64 and nfev == 0 and np.array_equal(ref.view(np.uint32), res.view(np.uint32))
+    return ref.size
 
 
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32])
 @pytest.mark.parametrize("rows, cols", SHAPES)
 def test_zero_weights_and_no_fields_are_normalize_bit_for_bit(ctx, pre, rows, cols, dtype):
-    c = case(rows, cols, 17, dtype)
-    for kw in (dict(), dict(cutoff=1.05, crop=((1, rows - 2), (3, cols))), dict(minus_log=False), dict(min_ratio=0.2, minus_log=True, cutoff=0.8)):
-        ref = pre.normalize(c["frames"], c["flats"], c["darks"], method="mean", **kw)
-        assert np.array_equal(ref.view(np.uint32), pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=0, **kw).view(np.uint32))
-        assert np.array_equal(ref.view(np.uint32), pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=3, weights=np.zeros((N, 3)), **kw).view(np.uint32))
-        res, W, nfev = pre.normalize_dynamic(c["frames"], c["flats"], c["darks"], n_eff=0, return_weights=True, **kw)
-        assert W.shape == (N, 0) and W.dtype == np.float64 and nfev == 0 and np.array_equal(ref.view(np.uint32), res.view(np.uint32))
+    zero_weights_are_normalize(pre, case(rows, cols, 17, dtype))
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+def test_zero_weights_and_no_fields_at_33_frames_are_normalize_bit_for_bit(ctx, pre, dtype):
+    """Three frame groups of k_apply against k_normalize, which tests/test_gpu_prep_paths.py holds to its model at such frame counts."""
+    assert MANY_FRAMES[-1] > 2 * NORM_FR
+    size = zero_weights_are_normalize(pre, case(37, 45, 17, dtype, MANY_FRAMES[-1]))
+    print("37x45 %s, %d frames: zero weights and no fields give normalize's %d values bit for bit" % (np.dtype(dtype).name, MANY_FRAMES[-1], size))
 
 
 def test_device_in_gives_device_out_and_out_is_honoured(ctx, pre):

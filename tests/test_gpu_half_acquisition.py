@@ -26,7 +26,7 @@ U32 = 2.0 ** -24
 CURVE_BOUND = 1e-10
 # The kernel rounds the four weights to float32 (u = 2^-24 each) and rounds once per product and per fma: b = fma(f, s1, (1 - f) s0)
 # errs by at most 3 u max|p| against float64 and out = fma(wA, a, (1 - wA) b) by 2 u more for its second term and 2 u for its first and
-# the sum: 7 u max|p|; the bound is 8 u max|p|.  Measured maximum on the MI355X: 2.03 u max|p|.
+# the sum: 7 u max|p|; the bound is 8 u max|p|.  Measured maximum on the MI355X: 2.36 u max|p| (at 16 x 1025 rows).
 STITCH_BOUND = 8 * U32
 
 
@@ -135,7 +135,43 @@ def _stitch_flat(ctx, half, p, c, offset):
         d_out.free()
 
 
-@pytest.mark.parametrize("nx,h,nz", [(16, 1, 1), (16, 4, 5), (16, 45, 8), (48, 4, 12), (48, 1, 8), (64, 4, 5), (64, 45, 12), (64, 1, 1)])
+# (nx, h, nz) of the stitch.  k_stitch puts zl lanes of four z along z (the rule of tomo_half_stitch, _zl below) and keeps 256 / zl columns
+# in flight; past 4 * 256 rows a second chunk of z (blockIdx.x >= 1) follows.  The first list stays within zl 1, 2 and 4.
+STITCH_SHAPES = [(16, 1, 1), (16, 4, 5), (16, 45, 8), (48, 4, 12), (48, 1, 8), (64, 4, 5), (64, 45, 12), (64, 1, 1)]
+STITCH_SHAPES_TALL = [
+    (16, 1, 20),        # zl 8
+    (16, 3, 30),        # zl 8, with a tail
+    (16, 1, 36),        # zl 16
+    (16, 1, 100),       # zl 32
+    (16, 3, 130),       # zl 64, with a tail
+    (16, 1, 260),       # zl 128
+    (48, 3, 516),       # zl 256: one column in flight, three column tiles
+    (16, 1, 1024),      # zl 256, exactly one chunk
+    (16, 3, 1025),      # two z chunks, the second holds one element
+    (48, 1, 1028),      # two z chunks, the 16-byte path
+    (48, 3, 2050),      # three z chunks, with a tail
+]
+
+
+def _zl(nz):
+    """Lanes along z of k_stitch, as tomo_half_stitch (csrc/half/tomo_half.hip) chooses them: a work-group has 256 lanes of four z."""
+    zl = 1
+    while zl < 256 and 4 * zl < nz:
+        zl *= 2
+    return zl
+
+
+def test_the_stitch_shapes_reach_every_lane_split_and_a_third_chunk():
+    """Host only: the lists above reach what they claim, so a change of the kernel's geometry fails here and not silently."""
+    nzs = [nz for _, _, nz in STITCH_SHAPES + STITCH_SHAPES_TALL]
+    chunks = {nz: -(-nz // (4 * _zl(nz))) for nz in nzs}
+    print("zl of the stitch cases %s; z chunks %s" % (sorted(set(_zl(nz) for nz in nzs)), sorted(set(chunks.values()))))
+    assert set(_zl(nz) for nz in nzs) == {1, 2, 4, 8, 16, 32, 64, 128, 256}
+    assert max(chunks.values()) >= 3
+    assert any(c > 1 and nz % 4 == 0 for nz, c in chunks.items()) and any(c > 1 and nz % 4 != 0 for nz, c in chunks.items())
+
+
+@pytest.mark.parametrize("nx,h,nz", STITCH_SHAPES + STITCH_SHAPES_TALL)
 def test_stitch_equals_the_model(ctx, half, nx, h, nz):
     """For every c of CENTRES[nx] -- both sides, integer and half-integer 2 c, fractional values, the detector centre and c = nx - 1,
     where g = 0 -- and for an aligned and a misaligned pair of pointers: the columns the first half alone supplies are its bits, every

@@ -16,7 +16,27 @@ from tomography_alignment_amd.utilities.geometry import Geometry
 
 pytestmark = pytest.mark.gpu
 
-BUILD_SHAPES = [(37, 50), (24, 33), (45, 96)]
+# k_prefilter starts its causal recursion from at most HORIZON = 128 terms (nx - 2 of them where the row is shorter) and moves a row
+# through LDS in tiles of TW = 64 columns.  (24, 130): nx - 2 is the horizon exactly, three tiles, the last of two columns; (24, 131):
+# one term is cut off, the last tile has three columns; (30, 200): 70 terms are cut off, four tiles, the last of eight columns.
+BUILD_SHAPES = [(37, 50), (24, 33), (45, 96), (24, 130), (24, 131), (30, 200)]
+PARITY_SHAPES_WIDE = cm.PARITY_SHAPES_WIDE
+
+
+def test_the_shape_lists_reach_the_truncated_start_and_a_second_pass_of_the_reduction():
+    """Host only.  The constants are those of csrc/cor/tomo_cor.hip: HORIZON = 128, TW = 64, and k_reduce's 64 lanes along ku from
+    ku = 2 on, whose second pass begins at ku = 66."""
+    horizon, tw, second_pass = 128, 64, 2 + 64
+    assert any(nx - 2 == horizon for _, nx in BUILD_SHAPES) and any(nx - 2 > horizon for _, nx in BUILD_SHAPES)
+    assert any(-(-nx // tw) == 3 and nx % tw for _, nx in BUILD_SHAPES) and any(-(-nx // tw) >= 4 and nx % tw for _, nx in BUILD_SHAPES)
+    for n, nx in PARITY_SHAPES_WIDE:
+        w, cut = cm.wedge(2 * n, nx)
+        widest = int(np.max(np.minimum(w, nx // 2)[~cut]))
+        print("(%d, %d): the widest uncut row of the wedge ends at ku = %d" % (n, nx, widest))
+        assert widest >= second_pass
+    for n, nx in cm.PARITY_SHAPES:                                      # and the narrow list stays what it was: one pass
+        w, cut = cm.wedge(2 * n, nx)
+        assert int(np.max(np.minimum(w, nx // 2)[~cut])) < second_pass
 
 
 @pytest.fixture(scope="module")
@@ -85,7 +105,7 @@ def test_build_spline_shifts_within_one_ulp(axis, n, nx):
 # -------------------------------------------------------------------------------------------------------- T3, T4: curves, result
 
 @pytest.mark.parametrize("noise", [0.0, 0.02])
-@pytest.mark.parametrize("n,nx", cm.PARITY_SHAPES)
+@pytest.mark.parametrize("n,nx", cm.PARITY_SHAPES + PARITY_SHAPES_WIDE)
 def test_metric_curves_and_offset_against_the_float64_model(axis, n, nx, noise):
     worst = 0.0
     for off in cm.OFFSETS:

@@ -22,7 +22,7 @@ found = cm.found
 
 
 def cases():
-    for n, nx in SHAPES:
+    for n, nx in SHAPES + cm.PARITY_SHAPES_WIDE:
         for off in OFFSETS:
             if (n, nx) == (24, 33) and abs(off) > 5.5:       # 2 |offset| reaches nx / 2 there
                 continue
@@ -102,7 +102,7 @@ def test_the_model_recovers_the_axis(n, nx, off):
 
 
 @pytest.mark.parametrize("noise", [0.0, 0.02])
-@pytest.mark.parametrize("n,nx", PARITY_SHAPES)
+@pytest.mark.parametrize("n,nx", PARITY_SHAPES + cm.PARITY_SHAPES_WIDE)
 def test_separation_condition_of_the_gpu_parity_cases(n, nx, noise):
     """An argmin comparison between the GPU and the model is fair only where rounding cannot decide it: the two smallest values of each
     curve are at least 50 x the GPU tolerance (16 d32) apart."""
