@@ -8,7 +8,7 @@ CXXFLAGS ?= -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -mun
             -Wall -Wno-unused-function -DTOMO_$(shell echo $(NAME) | tr a-z A-Z)_BUILD
 LDFLAGS ?= $(strip -shared $(LIBS))
 SRCS = tomo_$(NAME).hip
-HDRS = ../../../include/tomo_$(NAME).h ../tomo_side_host.h ../tomo_side_fft.h ../tomo_side_zgroups.h ../tomo_side_reduce.h ../tomo_side_lines.h
+HDRS = ../../../include/tomo_$(NAME).h ../tomo_side_host.h ../tomo_side_fft.h ../tomo_side_zgroups.h ../tomo_side_reduce.h ../tomo_side_lines.h ../tomo_side_tets.h
 OUT = ../../libtomo_$(NAME).so
 all: $(OUT)
 $(OUT): $(SRCS) $(HDRS)

@@ -265,7 +265,7 @@ def resolve_cor(data, cor, comm=None, ctx=None, verbose=False):
 
 def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, backend=None, align_kwargs=None, comm=None,
         kernel_names=None, download=True, return_loop=False, init="zero", fsc=False, cor=None, prealign=None, export=None,
-        export_dtype=np.uint8, register_truth=False, segment=False, morphology=False):
+        export_dtype=np.uint8, register_truth=False, segment=False, morphology=False, surface=False):
     """The loop of examples/align_rigid.py:36-52 (see OuterLoop for `data` and `comm`).
     segment        True: after the last outer iteration the reconstruction is segmented where it lies in HBM (_segmentation: Otsu's
                    threshold over the cylinder, threshold, label with 6 neighbours, measure; rank 0 of a sharded run) and the last
@@ -276,6 +276,10 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
                    background or the outside of the volume in voxels (morphology.distance, "background"), and "closed_porosity",
                    the voxels fill_holes adds over foreground plus those (0 without foreground); labels_meta.json holds them too.
                    Nothing else of the run changes.
+    surface        True (with segment): `segmentation` gains "surface_area", "enclosed_volume" and "specific_surface" (area over
+                   enclosed volume, 0 when the volume is not positive) of the isosurface of the reconstruction at the segmentation's
+                   threshold (mesh, border "closed"; voxel units); labels_meta.json holds them too, and with `export` the surface is
+                   written to export/surface.stl.  Nothing else of the run changes.
     register_truth True, and the data carry a phantom: every history entry gains `truth_shift` and `rmse_registered` (_truth_entry), the
                    RMSE after the gauge translation between reconstruction and phantom is taken out; `rmse` stays as it is.
     init           "zero" (default, the reference's) or "fbp": the first outer iteration's SIRT starts from the FBP at the current poses.
@@ -293,6 +297,8 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     until round 5 the loop was parked in `run.last_loop`, which pinned about six volume-sized buffers until the next call."""
     if morphology and not segment:
         raise ValueError("run: morphology=True goes with segment=True")
+    if surface and not segment:
+        raise ValueError("run: surface=True goes with segment=True")
     cor = resolve_cor(data, cor, comm, getattr(backend, "ctx", None), verbose)
     xyz0 = resolve_prealign(data, prealign, comm, getattr(backend, "ctx", None), verbose)
     start = {} if xyz0 is None else {"base": _base_of(xyz0)}
@@ -315,19 +321,20 @@ def run(data, n_outer=5, sirt_iters=50, bounds=DEFAULT_BOUNDS, verbose=True, bac
     if segment and loop.d_rec is not None and loop.rank == 0:
         if not history:
             history.append({})
-        history[-1]["segmentation"] = _segmentation(loop, export, verbose, morphology=morphology)
+        history[-1]["segmentation"] = _segmentation(loop, export, verbose, morphology=morphology, surface=surface)
     rec = loop.download() if (download and loop.d_rec is not None) else None
     out = (rec, loop.alpha_rec, loop.beta_rec, loop.xyz_rec, history)
     return out + (loop,) if return_loop else out
 
 
-def _segmentation(loop, export=None, verbose=False, limit=1000, morphology=False):
+def _segmentation(loop, export=None, verbose=False, limit=1000, morphology=False, surface=False):
     """The reconstruction (loop.d_rec, not written) split into its connected objects on the device: Otsu's threshold of the 4096-bin
     histogram over the reconstruction cylinder, the mask v >= threshold inside the cylinder, its components with 6 neighbours and their
     measures; only the tables come to the host.  -> {"threshold", "n_components", "foreground_fraction" (of the cylinder's voxels),
     "largest_fraction" (of the foreground; 0 without one)}.  export: a directory; labels_meta.json there holds the same and
     "components", the `limit` largest as {"label", "count", "bbox", "centroid"}.  morphology: also "max_inscribed_radius" and
-    "closed_porosity" (_mask_morphology), taken from the same mask before it is freed."""
+    "closed_porosity" (_mask_morphology), taken from the same mask before it is freed.  surface: also "surface_area", "enclosed_volume"
+    and "specific_surface" (_surface), from the reconstruction itself at the threshold; with export, surface.stl there."""
     import json
     import os
 
@@ -342,6 +349,7 @@ def _segmentation(loop, export=None, verbose=False, limit=1000, morphology=False
         d_mask.free()
         comp = seg.measure(d_labels, n, shape=shape)
         d_labels.free()
+    area = _surface(loop, float(t), shape, export) if surface else None
     fg = int(comp.count.sum())
     a, b = (2 * np.arange(k, dtype=np.int64) - k + 1 for k in shape[:2])          # the region's integer test (postprocess)
     inside = int(np.count_nonzero(a[:, None] ** 2 + b[None, :] ** 2 <= region_r4("cylinder", shape[0], shape[1]))) * shape[2]
@@ -350,6 +358,8 @@ def _segmentation(loop, export=None, verbose=False, limit=1000, morphology=False
     if extra is not None:
         radius, filled = extra
         out.update(max_inscribed_radius=radius, closed_porosity=filled / float(fg + filled) if fg else 0.0)
+    if area is not None:
+        out.update(surface_area=area[0], enclosed_volume=area[1], specific_surface=area[0] / area[1] if area[1] > 0 else 0.0)
     if export is not None:
         os.makedirs(export, exist_ok=True)
         with open(os.path.join(export, "labels_meta.json"), "w") as f:
@@ -371,6 +381,24 @@ def _mask_morphology(loop, d_mask, shape):
         d_filled, filled = mo.fill_holes(d_mask, return_count=True, shape=shape)
         d_filled.free()
     return radius, int(filled)
+
+
+def _surface(loop, level, shape, export=None):
+    """-> (area, enclosed volume) of the isosurface of the reconstruction (loop.d_rec, not written) at `level` with the closed border,
+    in voxel units.  Without export only the numbers come to the host; with it the triangles do, once, for export/surface.stl."""
+    import os
+
+    from .. import mesh as mesh_mod
+    with mesh_mod.MeshExtractor(loop.ctx) as mx:
+        if export is None:
+            m = mx.measure(loop.d_rec, level, "closed", shape=shape)
+            return float(m.area), float(m.volume)
+        s = mx.isosurface(loop.d_rec, level, "closed", shape=shape)
+        tri = s.triangles.download() if s.n else np.zeros((0, 3, 3), np.float32)
+        s.triangles.free()
+    os.makedirs(export, exist_ok=True)
+    mesh_mod.write_stl(os.path.join(export, "surface.stl"), tri)
+    return float(s.area), float(s.volume)
 
 
 def _fsc_entry(loop, res):
@@ -592,6 +620,9 @@ def main():
                     "--export, DIR/labels_meta.json holds the component table")
     ap.add_argument("--morphology", action="store_true", help="with --segment: also the largest inscribed radius of the mask (the exact "
                     "Euclidean distance transform) and its closed porosity (hole filling) on the GPU (morphology)")
+    ap.add_argument("--surface", action="store_true", help="with --segment: also the area and the enclosed volume of the isosurface of "
+                    "the reconstruction at the segmentation's threshold and their ratio, the specific surface, on the GPU (mesh); "
+                    "with --export the surface is written to surface.stl")
     ap.add_argument("--register-truth", action="store_true", help="with a phantom in the data: also report the RMSE after the reconstruction "
                     "is registered to the phantom (truth_shift, rmse_registered); --levels 1 only")
     a = ap.parse_args()
@@ -602,6 +633,8 @@ def main():
         ap.error("--segment goes with --levels 1")
     if a.morphology and not a.segment:
         ap.error("--morphology goes with --segment")
+    if a.surface and not a.segment:
+        ap.error("--surface goes with --segment")
     if a.prealign not in (None, "moment", "profile", "file"):
         ap.error("--prealign must be moment, profile or file")
     import os
@@ -615,7 +648,7 @@ def main():
     prealign = data["xyz0"] if a.prealign == "file" else a.prealign
     if a.levels == 1:
         run(data, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign, export=a.export,
-            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth, segment=a.segment, morphology=a.morphology)
+            export_dtype=np.dtype(a.export_dtype), register_truth=a.register_truth, segment=a.segment, morphology=a.morphology, surface=a.surface)
     else:
         run_multires(data, a.levels, a.outer, a.sirt_iters, comm=comm, init=a.init, fsc=a.fsc, cor=cor, prealign=prealign)
     if comm is not None:
