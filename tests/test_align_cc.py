@@ -1,30 +1,11 @@
-"""CPU tests of align/align_cc.py's host side: the C-ABI of libtomo_xcorr.so matches include/tomo_xcorr.h and the binding, the pcc
-stand-in (what the GPU module computes) recovers known sub-pixel shifts, and the image-axis-order filters are the reference's for
-square images."""
-import ctypes
-import os
-import re
-
+"""CPU tests of align/align_cc.py's host side: the pcc stand-in (what the GPU module computes) recovers known sub-pixel shifts, and the
+image-axis-order filters are the reference's for square images."""
 import numpy as np
 import pytest
 
 import pcc_standin as ps
-from conftest import ROOT
 
-from tomography_alignment_amd import _xcorr_lib
 from tomography_alignment_amd.align import align_cc
-
-
-def test_every_declared_symbol_is_exported_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "tomo_xcorr.h")).read()
-    declared = set(re.findall(r"^TOMO_API\s+[\w\s\*]*?\b(tomo_xcorr_\w+)\s*\(", hdr, flags=re.M))
-    assert len(declared) == 11, sorted(declared)
-    assert declared == set(_xcorr_lib.SIGNATURES), declared ^ set(_xcorr_lib.SIGNATURES)
-    assert os.path.exists(_xcorr_lib.LIB_PATH), "libtomo_xcorr.so not built"
-    lib = ctypes.CDLL(_xcorr_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), name
-    _xcorr_lib.load()
 
 
 @pytest.mark.parametrize("u", [1, 16, 100])

@@ -1,9 +1,8 @@
 """The consistency pre-alignment without a GPU: the estimator of align/consistency.py against the model of tests/mom_model.py on the same
 marginals, exact recovery of the shifts of analytic series, the CPU oracle's Shepp-Logan data at +-2 and +-10 px of jitter, the sign of
-axis_offset, the argument checks, that the data generator and the driver are what they were without the new options, and the binding of
-libtomo_mom.so (the assertions of tests/test_binding.py, for _mom_lib).  The marginals themselves are the GPU's business
-(tests/test_gpu_consistency.py); here they come from the model."""
-import ctypes
+axis_offset, the argument checks, that the data generator and the driver are what they were without the new options, and the handle-less
+calls of libtomo_mom.so.  The marginals themselves are the GPU's business (tests/test_gpu_consistency.py); here they come from the
+model."""
 import inspect
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 
 import mom_model as mm
 
-from tomography_alignment_amd import _binding, _lib, _mom_lib, rotation_axis
+from tomography_alignment_amd import _lib, _mom_lib, rotation_axis
 from tomography_alignment_amd.align import consistency
 from tomography_alignment_amd.examples import align_rigid, generate_data, preprocess
 
@@ -309,31 +308,6 @@ def test_pose_errors_report_the_gauge_fixed_error_beside_the_plain_one():
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_load_binds_the_whole_table_once():
-    lib = _mom_lib.load()
-    assert _mom_lib.load() is lib
-    assert _mom_lib.SIGNATURES
-    for sym, (res, args) in _mom_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_mom_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _mom_lib.load()
-    missing = str(tmp_path / "libtomo_mom.so")
-    monkeypatch.setattr(_mom_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "mom")
-    with pytest.raises(_lib.TomoError) as e:
-        _mom_lib.load()
-    text = str(e.value)
-    assert "libtomo_mom.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/mom`" in text
-    assert "mom" not in _binding._loaded
-    monkeypatch.undo()
-    assert _mom_lib.load() is _binding._loaded["mom"]
-
-
 def test_handle_less_calls_raise_in_the_common_format():
     assert issubclass(_mom_lib.MomUnsupported, _lib.TomoError) and consistency.MomUnsupported is _mom_lib.MomUnsupported
     for n, nx, nz, z0, z1 in ((0, 8, 8, 0, 8), (1, 0, 8, 0, 8), (1, 8, 0, 0, 0), (1, 8, 16385, 0, 8), (1, 8, 8, -1, 8), (1, 8, 8, 4, 4), (1, 8, 8, 0, 9)):
@@ -345,20 +319,6 @@ def test_handle_less_calls_raise_in_the_common_format():
         _mom_lib.batch(0, 64, 64)
     with pytest.raises(_mom_lib.MomUnsupported):
         _mom_lib.scratch_bytes(64, 16385)
-
-
-def test_no_device_means_no_handle():
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _mom_lib.MomHandle.__new__(_mom_lib.MomHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    h.close()
-    with pytest.raises(_lib.TomoError, match="mom handle closed"):
-        h.handle
 
 
 def test_batches_follow_the_budget():

@@ -1,21 +1,16 @@
 """Dynamic flat-field correction without a GPU: the numpy model of tests/dff_model.py (its gradient against finite differences, the
 eigenvalue rule and the gain over the conventional normalisation on generate_data's drifting beam), generate_data --beam-drift, the
-option parsing of both examples, the ctypes table against include/tomo_dff.h, and every refusal of preprocess.eigen_flats /
+option parsing of both examples, the library's refusals and batch rules, and every refusal of preprocess.eigen_flats /
 normalize_dynamic before a device is touched."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 import dff_model as dm
 import prep_model as pm
 
-from tomography_alignment_amd import _binding, _dff_lib, _lib, preprocess
+from tomography_alignment_amd import _dff_lib, preprocess
 from tomography_alignment_amd.examples import generate_data
 from tomography_alignment_amd.examples import preprocess as ex_pre
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -186,48 +181,9 @@ def test_examples_preprocess_dynamic_flat_arguments():
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_ctypes_table_lists_every_symbol_of_the_header():
-    text = open(os.path.join(ROOT, "include", "tomo_dff.h")).read()
-    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]+?\b(tomo_dff_\w+)\s*\(", text))
-    assert declared == set(_dff_lib.SIGNATURES)
-    for macro, value in (("MAX_FLATS", _dff_lib.MAX_FLATS), ("MAX_EFF", _dff_lib.MAX_EFF), ("MAX_BIN", _dff_lib.MAX_BIN), ("TILE_Z", _dff_lib.TILE_Z),
-                         ("TILE_X", _dff_lib.TILE_X), ("MAX_IDS", _dff_lib.MAX_IDS)):
-        assert int(re.search(r"#define TOMO_DFF_%s (\d+)" % macro, text).group(1)) == value, macro
-    assert (_dff_lib.MAX_FLATS, _dff_lib.MAX_EFF) == (128, 8) and preprocess.MAX_EFF == 8
-    assert int(re.search(r"TOMO_DFF_ERR_UNSUPPORTED = (\d+)", text).group(1)) == _dff_lib.ERR_UNSUPPORTED == 4
-    assert (int(re.search(r"TOMO_DFF_U16 = (\d+)", text).group(1)), int(re.search(r"TOMO_DFF_F32 = (\d+)", text).group(1))) == (_dff_lib.U16, _dff_lib.F32)
-    for name, (_, args) in _dff_lib.SIGNATURES.items():
-        decl = re.search(r"TOMO_API[^;]*\b%s\s*\(([^;]*)\);" % name, text, re.S).group(1)
-        n = 0 if decl.strip() == "void" else decl.count(",") + 1
-        assert n == len(args), name
-
-
-def test_load_binds_the_whole_table_once():
-    lib = _dff_lib.load()
-    assert _dff_lib.load() is lib
-    for sym, (res, args) in _dff_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_dff_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-    assert _dff_lib.DffHandle.NAME == "dff" and issubclass(_dff_lib.DffHandle, _binding.Handle)
-    assert issubclass(_dff_lib.DffUnsupported, _lib.TomoError) and preprocess.DffUnsupported is _dff_lib.DffUnsupported
-    import __graft_entry__ as entry
-    assert ("dff", "_dff_lib") in entry.LIBRARIES
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _dff_lib.load()
-    missing = str(tmp_path / "libtomo_dff.so")
-    monkeypatch.setattr(_dff_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "dff")
-    with pytest.raises(_lib.TomoError) as e:
-        _dff_lib.load()
-    text = str(e.value)
-    assert "libtomo_dff.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/dff`" in text
-    assert "dff" not in _binding._loaded
-    monkeypatch.undo()
-    assert _dff_lib.load() is _binding._loaded["dff"]
+def test_the_front_end_repeats_the_bindings_limits():
+    assert (_dff_lib.MAX_FLATS, _dff_lib.MAX_EFF, _dff_lib.ERR_UNSUPPORTED) == (128, 8, 4) and preprocess.MAX_EFF == 8
+    assert preprocess.DffUnsupported is _dff_lib.DffUnsupported
 
 
 def test_the_library_refuses_what_it_does_not_take_with_the_reason():
@@ -260,20 +216,6 @@ def test_batches_follow_the_budget_and_chunks_the_flats():
     for K in range(2, 129):
         C = _dff_lib.gram_chunk(K)
         assert C % 64 == 0 and 64 <= C <= 512 and (C == 64 or K * (C + 1) + C <= 8192)
-
-
-def test_no_device_means_no_handle():
-    import ctypes
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _dff_lib.DffHandle.__new__(_dff_lib.DffHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    with pytest.raises(_lib.TomoError, match="dff handle closed"):
-        h.handle
 
 
 # ---------------------------------------------------------------------------------------------------- refusals before any device

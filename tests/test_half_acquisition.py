@@ -1,10 +1,8 @@
 """Half-acquisition scans without a GPU: the numpy model of tests/half_model.py on analytic sinograms (the axis found, the stitch against
 the analytic pi sinogram, the shape and no-gap rules, left = mirrored right), the host half of the library (the stitch's column table
-against the model's), the ctypes table against include/tomo_half.h, every refusal of half_acquisition before a device is touched, and the
-options of both examples."""
+against the model's, its refusals and batch rule), every refusal of half_acquisition before a device is touched, and the options of
+both examples."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,11 +10,10 @@ import pytest
 import half_model as hm
 import mom_model as mm
 
-from tomography_alignment_amd import _binding, _half_lib, _lib, half_acquisition as ha
+from tomography_alignment_amd import _half_lib, half_acquisition as ha
 from tomography_alignment_amd.examples import generate_data
 from tomography_alignment_amd.examples import preprocess as ex_pre
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAUSSIANS = tuple(o for o in hm.OBJECTS if o[3] == "g")
 
 
@@ -150,50 +147,9 @@ def test_angles():
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_ctypes_table_lists_every_symbol_of_the_header():
-    text = open(os.path.join(ROOT, "include", "tomo_half.h")).read()
-    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]+?\b(tomo_half_\w+)\s*\(", text))
-    assert declared == set(_half_lib.SIGNATURES)
-    for macro, value in (("MAX_N", _half_lib.MAX_N), ("MIN_NX", _half_lib.MIN_NX), ("MAX_NX", _half_lib.MAX_NX), ("MAX_NZ", _half_lib.MAX_NZ),
-                         ("MAX_ROWS", _half_lib.MAX_ROWS), ("MIN_W", _half_lib.MIN_W), ("TILE_J", _half_lib.TILE_J), ("TILE_P", _half_lib.TILE_P),
-                         ("TILE_C", _half_lib.TILE_C)):
-        assert int(re.search(r"#define TOMO_HALF_%s (\d+)" % macro, text).group(1)) == value, macro
-    assert int(re.search(r"TOMO_HALF_ERR_UNSUPPORTED = (\d+)", text).group(1)) == _half_lib.ERR_UNSUPPORTED == 4
-    assert (int(re.search(r"TOMO_HALF_A_VALID = (\d+)", text).group(1)), int(re.search(r"TOMO_HALF_B_VALID = (\d+)", text).group(1))) \
-        == (_half_lib.A_VALID, _half_lib.B_VALID)
-    for name, (_, args) in _half_lib.SIGNATURES.items():
-        decl = re.search(r"TOMO_API[^;]*\b%s\s*\(([^;]*)\);" % name, text, re.S).group(1)
-        n = 0 if decl.strip() == "void" else decl.count(",") + 1
-        assert n == len(args), name
-    assert ctypes.sizeof(_half_lib.Column) == 32
-
-
-def test_load_binds_the_whole_table_once():
-    lib = _half_lib.load()
-    assert _half_lib.load() is lib
-    for sym, (res, args) in _half_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_half_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-    assert _half_lib.HalfHandle.NAME == "half" and issubclass(_half_lib.HalfHandle, _binding.Handle)
-    assert issubclass(_half_lib.HalfUnsupported, _lib.TomoError) and ha.HalfUnsupported is _half_lib.HalfUnsupported
-    import __graft_entry__ as entry
-    assert ("half", "_half_lib") in entry.LIBRARIES
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _half_lib.load()
-    missing = str(tmp_path / "libtomo_half.so")
-    monkeypatch.setattr(_half_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "half")
-    with pytest.raises(_lib.TomoError) as e:
-        _half_lib.load()
-    text = str(e.value)
-    assert "libtomo_half.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/half`" in text
-    assert "half" not in _binding._loaded
-    monkeypatch.undo()
-    assert _half_lib.load() is _binding._loaded["half"]
+def test_a_column_of_the_stitch_table_is_32_bytes():
+    assert ctypes.sizeof(_half_lib.Column) == 32 and _half_lib.ERR_UNSUPPORTED == 4
+    assert ha.HalfUnsupported is _half_lib.HalfUnsupported
 
 
 def test_the_library_refuses_what_it_does_not_take_with_the_reason():
@@ -221,19 +177,6 @@ def test_batches_follow_the_budget():
     per = _half_lib.scratch_bytes(64, 12)
     assert _half_lib.batch(5, 64, 12, 0) == 5 and _half_lib.batch(5, 64, 12, 1) == 1 and _half_lib.batch(5, 64, 12, per) == 1
     assert _half_lib.batch(5, 64, 12, 2 * per + 3) == 2 and _half_lib.batch(5, 64, 12, 100 * per) == 5
-
-
-def test_no_device_means_no_handle():
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _half_lib.HalfHandle.__new__(_half_lib.HalfHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    with pytest.raises(_lib.TomoError, match="half handle closed"):
-        h.handle
 
 
 # ---------------------------------------------------------------------------------------------------- refusals before any device

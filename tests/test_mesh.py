@@ -1,7 +1,8 @@
 """mesh without a GPU: the model of tests/mesh_model.py on its own (closed surfaces on random volumes, masks, voxels equal to the level
 and voxels that are not finite; the sign of the volume; masks against their float32 form; the two borders; the ball of the issue
 against the sphere), the tables of csrc/tomo_side_tets.h against tools/tets_table.py, the STL writer byte for byte, the argument
-checks of every public function, check_shape, and the binding against the header.  Every test prints what it measured."""
+checks of every public function, check_shape, and what the binding mirrors of the header under names of its own.  Every test prints
+what it measured."""
 import os
 import re
 import struct
@@ -11,10 +12,10 @@ import sys
 import numpy as np
 import pytest
 
+import abi
 import mesh_model as mm
 
-import __graft_entry__ as entry
-from tomography_alignment_amd import _binding, _lib, _mesh_lib, mesh
+from tomography_alignment_amd import _lib, _mesh_lib, mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = ((1, 1, 1), (1, 4, 5), (4, 1, 5), (2, 2, 2), (5, 6, 7), (9, 4, 11))
@@ -223,68 +224,14 @@ def test_check_shape_needs_no_device():
 # ------------------------------------------------------------------------------------------------------------------- the binding
 
 def test_the_binding_covers_the_header():
-    with open(os.path.join(ROOT, "include", "tomo_mesh.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]*?\b(tomo_mesh_\w+)\s*\(", text))
-    lib = _mesh_lib.load()
-    print("%d symbols declared, %d bound" % (len(declared), len(_mesh_lib.SIGNATURES)))
-    assert declared == set(_mesh_lib.SIGNATURES) and len(declared) == 8
-    for name, (res, args) in _mesh_lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    consts = dict((k, int(v)) for k, v in re.findall(r"#define\s+TOMO_MESH_(\w+)\s+\(?(\d+)\b", text))
-    assert consts["MAX_DIM"] == _mesh_lib.MAX_DIM and consts["MAX_VOXELS"] == _mesh_lib.MAX_VOXELS
-    assert consts["MAX_TRIANGLES"] == _mesh_lib.MAX_TRIANGLES
-    assert (consts["BRICK_X"], consts["BRICK_Y"], consts["BRICK_Z"]) == _mesh_lib.BRICK and consts["GROUP"] == _mesh_lib.GROUP
-    assert consts["GROUP"] == _mesh_lib.BRICK[1] * _mesh_lib.BRICK[2]
-    assert consts["KEEP_BYTES"] << 20 == _mesh_lib.KEEP_BYTES             # written (16 << 20)
-    assert (consts["F32"], consts["U8"]) == (_mesh_lib.F32, _mesh_lib.U8)
-    assert {"open": consts["OPEN"], "closed": consts["CLOSED"]} == _mesh_lib.BORDERS
-    codes = dict(re.findall(r"TOMO_MESH_ERR_(\w+) = (\d+)", text))
-    assert int(codes["UNSUPPORTED"]) == _mesh_lib.ERR_UNSUPPORTED and int(codes["CAPACITY"]) == _mesh_lib.ERR_CAPACITY
-    assert issubclass(_mesh_lib.MeshHandle, _mesh_lib.Handle) and _mesh_lib.MeshHandle.NAME == "mesh"
-    assert ("mesh", "_mesh_lib") in entry.LIBRARIES
-
-
-def test_load_binds_the_whole_table_once():
-    lib = _mesh_lib.load()
-    assert _mesh_lib.load() is lib and _mesh_lib.SIGNATURES
-    for sym, (res, args) in _mesh_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_mesh_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _mesh_lib.load()
-    missing = str(tmp_path / "libtomo_mesh.so")
-    monkeypatch.setattr(_mesh_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "mesh")
-    with pytest.raises(_lib.TomoError) as e:
-        _mesh_lib.load()
-    text = str(e.value)
-    assert "libtomo_mesh.so not built" in text and missing in text and "`make -C tomography_alignment_amd/csrc/mesh`" in text
-    assert "mesh" not in _binding._loaded
-    monkeypatch.undo()
-    assert _mesh_lib.load() is _binding._loaded["mesh"]
+    """What _mesh_lib mirrors under a name of its own; tests/test_binding.py holds everything else against the header."""
+    c = abi.parse_header(abi.header_path("mesh")).constants
+    assert (c["TOMO_MESH_BRICK_X"], c["TOMO_MESH_BRICK_Y"], c["TOMO_MESH_BRICK_Z"]) == _mesh_lib.BRICK
+    assert c["TOMO_MESH_GROUP"] == _mesh_lib.GROUP == _mesh_lib.BRICK[1] * _mesh_lib.BRICK[2]
+    assert {"open": c["TOMO_MESH_OPEN"], "closed": c["TOMO_MESH_CLOSED"]} == _mesh_lib.BORDERS
 
 
 def test_errors_are_one_family_and_in_the_common_format():
     assert issubclass(_mesh_lib.MeshUnsupported, _lib.TomoError)
     with pytest.raises(_mesh_lib.MeshUnsupported, match=r"^libtomo_mesh error 4: tomo_mesh"):
         _mesh_lib.check_shape(0, 1, 1)
-
-
-def test_no_device_means_no_handle():
-    import ctypes
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _mesh_lib.MeshHandle.__new__(_mesh_lib.MeshHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    h.close()
-    with pytest.raises(_lib.TomoError, match="mesh handle closed"):
-        h.handle

@@ -1,19 +1,13 @@
 """morphology without a GPU: the model of tests/morph_model.py against the brute force over all background voxels and against
 scipy.ndimage (distance_transform_edt, binary_erosion for both border values, binary_dilation, binary_opening, binary_closing,
-binary_fill_holes), the argument checks of every public function, check_shape, ball_r2, and the binding against the header.  Every
-test prints what it measured."""
-import os
-import re
-
+binary_fill_holes), the argument checks of every public function, check_shape and ball_r2.  Every test prints what it measured."""
 import numpy as np
 import pytest
 
 import morph_model as mm
 
-import __graft_entry__ as entry
 from tomography_alignment_amd import _morph_lib, morphology
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BORDERS = ("ignore", "background")
 
 
@@ -152,20 +146,5 @@ def test_check_shape_needs_no_device():
     print("16385 on each axis and 2^31 voxels refused, 2^31 - 2^20 accepted")
 
 
-def test_the_binding_covers_the_header():
-    with open(os.path.join(ROOT, "include", "tomo_morph.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]*?\b(tomo_morph_\w+)\s*\(", text))
-    lib = _morph_lib.load()
-    print("%d symbols declared, %d bound" % (len(declared), len(_morph_lib.SIGNATURES)))
-    assert declared == set(_morph_lib.SIGNATURES) and len(declared) == 17
-    for name, (res, args) in _morph_lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    consts = dict((k, int(v)) for k, v in re.findall(r"#define\s+TOMO_MORPH_(\w+)\s+\(?(\d+)\b", text))
-    assert consts["MAX_DIM"] == _morph_lib.MAX_DIM and consts["MAX_VOXELS"] == _morph_lib.MAX_VOXELS and consts["INF"] == _morph_lib.INF
-    assert (consts["W"], consts["MAX_WQ"], consts["GROUP"], consts["LINE_LIMIT"]) == (_morph_lib.W, _morph_lib.MAX_WQ, _morph_lib.GROUP, _morph_lib.LINE_LIMIT)
-    assert consts["KEEP_BYTES"] << 20 == _morph_lib.KEEP_BYTES            # written (16 << 20)
+def test_no_squared_distance_reaches_the_value_of_no_background():
     assert 3 * (_morph_lib.MAX_DIM - 1) ** 2 < _morph_lib.INF == morphology.INF == 2 ** 31 - 1
-    assert issubclass(_morph_lib.MorphHandle, _morph_lib.Handle) and _morph_lib.MorphHandle.NAME == "morph"
-    assert ("morph", "_morph_lib") in entry.LIBRARIES

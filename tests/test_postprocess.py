@@ -1,6 +1,6 @@
 """postprocess without a GPU: the numpy model (tests/vol_model.py) against independent numpy, Histogram.window on hand-made counts, the
-binding of libtomo_vol.so (the assertions tests/test_binding.py makes for the other libraries) and the argument errors that Python raises
-before any device use.  Needs the built library, no GPU.  Every test prints the figures it measured."""
+shape check of libtomo_vol.so and the argument errors that Python raises before any device use.  Needs the built library, no GPU.  Every
+test prints the figures it measured."""
 import ctypes
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 
 import vol_model as vm
 
-from tomography_alignment_amd import _binding, _lib, _vol_lib, postprocess
+from tomography_alignment_amd import _vol_lib, postprocess
 
 
 # ------------------------------------------------------------------------------------------------------ the model against independent numpy
@@ -111,53 +111,14 @@ def test_window_on_hand_made_counts():
 
 # ------------------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_load_binds_the_whole_table_once():
-    lib = _vol_lib.load()
-    assert _vol_lib.load() is lib and len(_vol_lib.SIGNATURES) == 14
-    for sym, (res, args) in _vol_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_vol_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-    assert ctypes.sizeof(_vol_lib.StatsStruct) == 40
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _vol_lib.load()
-    missing = str(tmp_path / "libtomo_vol.so")
-    monkeypatch.setattr(_vol_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "vol")
-    with pytest.raises(_lib.TomoError) as e:
-        _vol_lib.load()
-    text = str(e.value)
-    assert "libtomo_vol.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/vol`" in text
-    assert "vol" not in _binding._loaded
-    monkeypatch.undo()
-    assert _vol_lib.load() is _binding._loaded["vol"]
-
-
 def test_the_error_class_and_the_shape_check_without_a_device():
-    assert issubclass(_vol_lib.VolUnsupported, _lib.TomoError) and postprocess.VolUnsupported is _vol_lib.VolUnsupported
+    assert postprocess.VolUnsupported is _vol_lib.VolUnsupported and ctypes.sizeof(_vol_lib.StatsStruct) == 40
     _vol_lib.check_shape(1, 1, 1)
     _vol_lib.check_shape(_vol_lib.MAX_DIM, _vol_lib.MAX_DIM, 8)
     _vol_lib.check_shape(2, 1, 2 ** 30 + 192)
     for s in [(0, 4, 4), (4, 0, 4), (4, 4, 0), (_vol_lib.MAX_DIM + 1, 4, 4), (4, _vol_lib.MAX_DIM + 1, 4), (4, 4, _vol_lib.MAX_NZ + 1), (-3, 4, 4)]:
         with pytest.raises(_vol_lib.VolUnsupported, match=r"^libtomo_vol error 4: tomo_vol: a volume of "):
             _vol_lib.check_shape(*s)
-
-
-def test_no_device_means_no_handle():
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _vol_lib.VolHandle.__new__(_vol_lib.VolHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    h.close()
-    with pytest.raises(_lib.TomoError, match="vol handle closed"):
-        h.handle
 
 
 # ------------------------------------------------------------------------------------------- argument errors, before any device use

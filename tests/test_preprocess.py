@@ -1,14 +1,10 @@
 """CPU tests of tomography_alignment_amd/preprocess.py: the numpy models (tests/prep_model.py), their pinned effect, argument validation
-before any launch, the ctypes table against include/tomo_prep.h, and the argument handling of examples/preprocess.py."""
-import os
-import re
-
+before any launch, and the argument handling of examples/preprocess.py."""
 import numpy as np
 import pytest
 from scipy import ndimage
 
 import prep_model as pm
-from conftest import ROOT
 
 from tomography_alignment_amd import _prep_lib, preprocess
 from tomography_alignment_amd.examples import generate_data
@@ -111,14 +107,6 @@ def test_normalize_arguments_are_checked_before_any_launch():
         preprocess.normalize(fr[0], ok, ok)
     with pytest.raises(_prep_lib.PrepUnsupported):
         preprocess.reference_frames(np.zeros((65, 4, 5), np.uint16), ok, method="median")
-
-
-def test_ctypes_table_matches_the_header():
-    hdr = open(os.path.join(ROOT, "include", "tomo_prep.h")).read()
-    declared = set(re.findall(r"TOMO_API\s+[\w\s\*]+?\b(tomo_prep_\w+)\s*\(", hdr))
-    assert declared == set(_prep_lib.SIGNATURES)
-    for name, value in (("TOMO_PREP_MAX_NPROJ", _prep_lib.MAX_NPROJ), ("TOMO_PREP_ERR_UNSUPPORTED", _prep_lib.ERR_UNSUPPORTED)):
-        assert re.search(r"%s\s*=?\s*%d\b" % (name, value), hdr), name
 
 
 def test_example_cli_arguments():

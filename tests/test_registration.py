@@ -1,14 +1,12 @@
 """Volume registration without a GPU: the numpy model tests/vreg_model.py against a brute-force evaluation of the upsampled sum, against
 planted shifts and against np.roll; the wrap and Nyquist rules; the arithmetic of registration.Registration; the argument checks of
-registration.py that need no device; and the binding of libtomo_vreg.so (the assertions of tests/test_binding.py, for _vreg_lib)."""
-import ctypes
-
+registration.py that need no device; and the refusals of libtomo_vreg.so's handle-less calls."""
 import numpy as np
 import pytest
 
 import vreg_model as vm
 
-from tomography_alignment_amd import _binding, _lib, _vreg_lib, registration, resolution
+from tomography_alignment_amd import _lib, _vreg_lib, registration, resolution
 
 SHAPES = [(6, 5, 8), (17, 12, 10), (20, 17, 13), (33, 20, 18)]
 
@@ -132,31 +130,6 @@ def test_argument_checks_need_no_device():
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_load_binds_the_whole_table_once():
-    lib = _vreg_lib.load()
-    assert _vreg_lib.load() is lib
-    assert _vreg_lib.SIGNATURES
-    for sym, (res, args) in _vreg_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_vreg_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _vreg_lib.load()
-    missing = str(tmp_path / "libtomo_vreg.so")
-    monkeypatch.setattr(_vreg_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "vreg")
-    with pytest.raises(_lib.TomoError) as e:
-        _vreg_lib.load()
-    text = str(e.value)
-    assert "libtomo_vreg.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/vreg`" in text
-    assert "vreg" not in _binding._loaded
-    monkeypatch.undo()
-    assert _vreg_lib.load() is _binding._loaded["vreg"]
-
-
 def test_handle_less_calls_raise_in_the_common_format():
     assert issubclass(_vreg_lib.VregUnsupported, _lib.TomoError) and registration.VregUnsupported is _vreg_lib.VregUnsupported
     for shape in ((1, 8, 8), (8, 2049, 8), (8, 8, 0), (2048, 2048, 1024)):
@@ -165,17 +138,3 @@ def test_handle_less_calls_raise_in_the_common_format():
     with pytest.raises(_vreg_lib.VregUnsupported, match=r"^libtomo_vreg error 4: tomo_vreg: upsample"):
         _vreg_lib.check(8, 8, 8, 101)
     _vreg_lib.check(2048, 2048, 511, 100)                           # 2^31 - 2^22 values: the largest legal volumes are fine
-
-
-def test_no_device_means_no_handle():
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _vreg_lib.VregHandle.__new__(_vreg_lib.VregHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    h.close()
-    with pytest.raises(_lib.TomoError, match="vreg handle closed"):
-        h.handle

@@ -1,9 +1,7 @@
 """The rotation-axis search without a GPU: the numpy model of tests/cor_model.py against scipy and against itself (half-spectrum against
 the full transform, the mask's symmetries), that it recovers the axis of analytic ellipse sinograms, the separation condition every GPU
-parity case of tests/test_gpu_rotation_axis.py relies on, the argument and angle checks of rotation_axis, and the binding of
-libtomo_cor.so (the assertions of tests/test_binding.py, for _cor_lib)."""
-import ctypes
-
+parity case of tests/test_gpu_rotation_axis.py relies on, the argument and angle checks of rotation_axis, and the handle-less calls of
+libtomo_cor.so."""
 import numpy as np
 import pytest
 import scipy.ndimage
@@ -12,7 +10,7 @@ import cor_model as cm
 
 from oracle import oracle as orc
 
-from tomography_alignment_amd import _binding, _cor_lib, _lib, rotation_axis
+from tomography_alignment_amd import _cor_lib, _lib, rotation_axis
 from tomography_alignment_amd.examples import generate_data
 
 SHAPES, PARITY_SHAPES, OFFSETS = cm.SHAPES, cm.PARITY_SHAPES, cm.OFFSETS
@@ -217,31 +215,6 @@ def test_generate_data_without_an_offset_is_what_it_was(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
 
-def test_load_binds_the_whole_table_once():
-    lib = _cor_lib.load()
-    assert _cor_lib.load() is lib
-    assert _cor_lib.SIGNATURES
-    for sym, (res, args) in _cor_lib.SIGNATURES.items():
-        assert sym.startswith("tomo_cor_"), sym
-        fn = getattr(lib, sym)
-        assert fn.restype is res and list(fn.argtypes) == list(args), sym
-
-
-def test_a_missing_library_is_named_with_its_build_command(monkeypatch, tmp_path):
-    _cor_lib.load()
-    missing = str(tmp_path / "libtomo_cor.so")
-    monkeypatch.setattr(_cor_lib, "LIB_PATH", missing)
-    monkeypatch.delitem(_binding._loaded, "cor")
-    with pytest.raises(_lib.TomoError) as e:
-        _cor_lib.load()
-    text = str(e.value)
-    assert "libtomo_cor.so not built" in text and missing in text
-    assert "`make -C tomography_alignment_amd/csrc/cor`" in text
-    assert "cor" not in _binding._loaded
-    monkeypatch.undo()
-    assert _cor_lib.load() is _binding._loaded["cor"]
-
-
 def test_handle_less_calls_raise_in_the_common_format():
     assert issubclass(_cor_lib.CorUnsupported, _lib.TomoError) and rotation_axis.CorUnsupported is _cor_lib.CorUnsupported
     for n, nx, ns in ((7, 64, 1), (64, 15, 1), (8193, 64, 1), (64, 8193, 1), (64, 64, 4097)):
@@ -254,20 +227,6 @@ def test_handle_less_calls_raise_in_the_common_format():
     # a shape beyond the limits is refused by the public call before it asks for a context
     with pytest.raises(_cor_lib.CorUnsupported):
         rotation_axis.find_center(np.zeros((8200, 64, 1), np.float32), smin=-5, smax=5)
-
-
-def test_no_device_means_no_handle():
-    n = ctypes.c_int(0)
-    if _lib.load().tomo_device_count(ctypes.byref(n)) == 0 and n.value > 0:
-        pytest.skip("a GPU is present")
-    h = _cor_lib.CorHandle.__new__(_cor_lib.CorHandle)
-    with pytest.raises(_lib.TomoError):
-        h.__init__(0)
-    assert h._h is None
-    h.close()
-    h.close()
-    with pytest.raises(_lib.TomoError, match="cor handle closed"):
-        h.handle
 
 
 @pytest.mark.parametrize("n,nx", [(24, 33), (37, 50), (45, 96), (900, 2048), (8, 16)])

